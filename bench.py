@@ -1,6 +1,6 @@
 """bench.py -- self-play moves/sec of the batched engine (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1: one rank per GPU over RCCL.  Either the caller starts the ranks (`python -m torch.distributed.run --nproc-per-node N
 bench.py --gpus N ...`: WORLD_SIZE must then equal N) or, when WORLD_SIZE is not set, bench.py re-executes itself under
@@ -24,7 +24,8 @@ from staggered random openings, then rounds run until every slot has committed >
 (a fresh tree needs 26 rounds to its first move; afterwards inherited sub-trees of different sizes de-phase the slots), so that
 move completions are spread evenly over rounds and a 20-round window measures the same moves/s as a 300-round one.  The timed
 region always contains at least two harvests + gathers (every min(--harvest-every, --steps / 2) rounds).
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  --dump-outputs DIR also writes what the timed path handed its caller after the last timed step as
+DIR/<name>.npy (see step_outputs / dump_outputs); the inputs depend on the arguments only, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -107,6 +108,8 @@ def parse_args(argv=None):
                     help="skip the sub-tree-reuse-off companion measurement (fresh_tree_moves_per_s, SURVEY 8d's upper-work variant)")
     ap.add_argument("--no-miopen-find", action="store_true", help="disable torch.backends.cudnn.benchmark (MIOpen find) for the convs")
     ap.add_argument("--split-round", action="store_true", help="diagnostic: launch expand/backup and select as two kernels and time each")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last one as DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
     ap.add_argument("--launch-check", action="store_true",
                     help="only rendezvous the ranks (RCCL on GPUs, gloo without a device), print the world size that joined and exit")
     return ap.parse_args(argv)
@@ -165,6 +168,7 @@ def barrier(world, dev):
 
 
 HG_MS = []  # wall-clock of every harvest + gather of this rank, measured from an idle stream (the rounds queued before it have drained)
+LAST_GATHER = []  # the (states, pi, z, games) the latest harvest + gather returned on this rank (none on a rank other than dst)
 
 
 def harvest_and_gather(act):
@@ -176,6 +180,7 @@ def harvest_and_gather(act):
     st, pi, z, games = act.harvest_tensors()
     res = gather_samples(st, pi, z, games, dst=0)
     HG_MS.append((time.perf_counter() - t0) * 1e3)
+    LAST_GATHER[:] = [] if res is None else [res]
     return 0 if res is None else int(res[0].shape[0])
 
 
@@ -221,7 +226,7 @@ def timed(act, args, world, dev, warmup, steps):
     evs = [tuple(torch.cuda.Event(enable_timing=True) for _ in range(4)) for _ in range(steps)] if dev.type == "cuda" else [None] * steps
     gathered = 0
     barrier(world, dev)
-    del HG_MS[:]
+    del HG_MS[:], LAST_GATHER[:]
     t0 = time.perf_counter()
     for i in range(steps):
         act.run_round(evs[i])
@@ -229,6 +234,49 @@ def timed(act, args, world, dev, warmup, steps):
             gathered += harvest_and_gather(act)
     barrier(world, dev)
     return time.perf_counter() - t0, act.counters(), evs, gathered
+
+
+DUMP_BUDGET = 64 << 20  # bytes, all files of one --dump-outputs together
+
+
+def step_outputs(act):
+    """What the timed path hands its caller after its last step, as host arrays: the evaluator's `priors` [G*P, A] / `values` [G*P] for
+    that round's leaf batch (what the next expand/backup consumes), every game's `status` row [G, 8] and `root_q` [G, 2] (Engine.status),
+    and the samples of the last harvest + gather of the timed region (`samples_states` / `_pi` / `_z` / `_games`; on the gather's
+    destination rank only).  Floating arrays keep their dtype; integers become float32 (8 / 16 bit) or float64 (wider), exactly."""
+    e = act.engine
+    st, q = e.status()
+    out = {"priors": e.priors, "values": e.values, "status": st, "root_q": q}
+    if LAST_GATHER:
+        out.update(zip(("samples_states", "samples_pi", "samples_z", "samples_games"), LAST_GATHER[0]))
+    arrays = {}
+    for k, v in out.items():
+        a = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float32 if a.dtype.itemsize <= 2 and a.dtype.kind in "biu" else np.float64)
+        arrays[k] = a
+    return arrays
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET, seed=0):
+    """arrays -> out_dir/<name>.npy.  Over `budget` bytes in all, every array keeps the same seeded fraction of its rows (arrays with the
+    same row count keep the same rows, e.g. priors and values) and <name>_rows.npy (float64) lists the rows kept.  Returns the paths."""
+    os.makedirs(out_dir, exist_ok=True)
+    hdr = 256  # an .npy header is 128 bytes; twice that per file, for the array and its row list
+    total = sum(a.nbytes for a in arrays.values())
+    frac = 1.0
+    if total + hdr * len(arrays) > budget:
+        frac = (budget - 2 * hdr * len(arrays)) / sum(a.nbytes + 8 * (a.shape[0] if a.ndim else 1) for a in arrays.values())
+    paths = []
+    for name, a in arrays.items():
+        if frac < 1.0 and a.ndim and a.shape[0] > 1:
+            rows = np.sort(np.random.default_rng(seed).choice(a.shape[0], int(a.shape[0] * frac), replace=False))
+            a = a[rows]
+            paths.append(os.path.join(out_dir, f"{name}_rows.npy"))
+            np.save(paths[-1], rows.astype(np.float64))
+        paths.append(os.path.join(out_dir, f"{name}.npy"))
+        np.save(paths[-1], np.ascontiguousarray(a))
+    return paths
 
 
 def reduce_totals(cnt, elapsed, world, dev):
@@ -696,6 +744,11 @@ def main(argv=None):
     elapsed, cnt, evs, samples_at_root = timed(actor, args, world, dev, args.warmup, args.steps)
     # range record of the HEADLINE actor's evaluator over pre-roll + warm-up + timed region, read before anything else touches the network
     erange = evaluator_range(actor)
+    if args.dump_outputs:  # the headline actor's last timed step, before the kernel replay or a companion runs anything
+        outs = step_outputs(actor)
+        if world > 1:
+            outs = {f"{k}_rank{rank}": v for k, v in outs.items()}
+        dump_outputs(args.dump_outputs, outs, budget=DUMP_BUDGET // world)  # every rank writes its own share of the 64 MB
     bk_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in evs]))  # expand/backup + end-of-move kernels
     k_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in evs]))   # select kernel (the dominant hand-written kernel)
     nn_ms = float(np.mean([e[2].elapsed_time(e[3]) for e in evs]))
