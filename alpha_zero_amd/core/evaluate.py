@@ -133,7 +133,7 @@ class DeviceEvaluator:
     def _state_key(self):
         i = self.inf  # everything a captured forward bakes in besides the (in-place updated) weight tensors
         return (id(i), getattr(i, "act_shift", 0), getattr(i, "act_calibrated", True), getattr(i, "split_fallback_reason", None),
-                getattr(i, "stem_fallback_reason", None), getattr(i, "use_split_tower", None), getattr(i, "use_fused_block", None))
+                getattr(i, "use_split_tower", None), getattr(i, "use_fused_block", None))
 
     def device_eval_into(self, x, priors_out, values_out):
         """The evaluator between an engine's own tensors: x = its feature rows, outputs written in place into its priors / values (fp32).

@@ -13,9 +13,11 @@ the fp32-class split-precision stem / tower / heads (default: the reference's pr
 other shapes fall back to the library's convolutions (MIOpen) + the fused azsp_bias_act epilogue,
 announced by `evaluator_path` and a RuntimeWarning.
 """
-from typing import Tuple
-
+import ctypes
+import math
+import warnings
 from contextlib import nullcontext as _nullcontext
+from typing import Tuple
 
 import torch
 import torch.nn.functional as F
@@ -101,9 +103,33 @@ def widen_network(net: "AlphaZeroNet", num_filters: int) -> "AlphaZeroNet":
 
 F16_MAX = 65504.0
 
-# tower widths with hand-written evaluator kernels per (board size, stem padding); dtype class "fp32" = the split-precision kernels,
-# "lowp" = the bf16 / f16 tiled kernels (see InferenceNet.supports_split_features / supports_tiled_features)
-KERNEL_WIDTHS = {"fp32": {(9, 1): (64, 128), (13, 3): (64,)}, "lowp": {(9, 1): (64, 128), (13, 3): (64,), (19, 1): (256,)}}
+# Which network shapes have hand-written kernels: every shape decision of InferenceNet is derived from these tables.
+# (filters, board, stem pad) -> element types whose WHOLE evaluator (stem, tower, heads) runs on libazsp kernels: "fp32" = the
+# split-precision family (the reference's precision class), "bf16" / "f16" = the tiled family.  Their towers run on (filters, tower
+# planes) with tower planes = board + 2 * (pad - 1) (network.py:101-105: the Gomoku stem pads by 3, 13x13 boards -> 17x17 planes).
+EVAL_KERNELS = {(128, 9, 1): ("fp32", "bf16", "f16"), (64, 9, 1): ("fp32", "bf16"), (64, 13, 3): ("fp32", "bf16"), (256, 19, 1): ("bf16",)}
+F16_HEADS = (82, 128)  # the f16 variants exist for 82 actions and 128 fully connected units only
+FUSED_BLOCK_SHAPES = ((64, 17), (64, 9))  # (filters, tower planes) with one launch per ResNetBlock (azsp_resblock_tiled / _split)
+FC_TILES = ((3, 2), (3, 4), (6, 2), (6, 4), (12, 8))  # (actions, fully connected units) in 32-wide tiles that azsp_fc_heads takes
+_DT_CLASS = {torch.float32: "fp32", torch.bfloat16: "bf16", torch.float16: "f16"}
+
+
+def _planes(board, pad):
+    return board + 2 * (pad - 1)
+
+
+def _fc_tiles(actions, fc_width):
+    return (actions + 31) // 32, (fc_width + 31) // 32
+
+
+def _stream(t):
+    """The current stream of t's device for a libazsp call (None on the host twin's CPU tensors)."""
+    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream) if t.is_cuda else None
+
+
+def _ck(rc, what):
+    if rc != 0:
+        raise RuntimeError(f"{what} failed with code {rc}")
 
 
 # widening multiplies the tower's FLOPs by (w / f)^2; the hand-written kernels are 4.5 - 5x the library's fp32 convolutions (measured: 40 -> 64 =
@@ -118,12 +144,12 @@ def widen_for_kernels(net: "AlphaZeroNet", board_size: int, dtype):
     widths (13x13 Gomoku: 10 x 40, training_gomoku.py:37-38) reach the kernels by default instead of the library fallback; the price is
     the extra FLOPs of the wider tower (40 -> 64: 2.56x), still 1.7x faster than the library's fp32 convolutions at the true width.
     Returns (network, note) with note = '' or a description for `evaluator_path`."""
-    cls = "fp32" if dtype == torch.float32 else "lowp"
-    pad = net.conv_block[0].padding[0]
-    widths = KERNEL_WIDTHS[cls].get((board_size, pad), ())
-    f = net.conv_block[0].out_channels
-    if dtype == torch.float16:  # the f16 variants exist for the 9x9 x 128 evaluator with 82 actions and 128 fully connected units only
+    if dtype == torch.float16:  # the f16 variants exist for one evaluator only (F16_HEADS): nothing to widen to
         return net, ""
+    cls = "fp32" if dtype == torch.float32 else "bf16"
+    pad = net.conv_block[0].padding[0]
+    widths = [f for (f, n, p), dts in EVAL_KERNELS.items() if (n, p) == (board_size, pad) and cls in dts]
+    f = net.conv_block[0].out_channels
     if f in widths or not widths or f > max(widths):
         return net, ""
     w = min(v for v in widths if v >= f)
@@ -151,6 +177,10 @@ def _fold(conv: nn.Conv2d, bn: nn.BatchNorm2d):
     return conv.weight * s.view(-1, 1, 1, 1), bn.bias - bn.running_mean * s
 
 
+def _frozen(t):
+    return nn.Parameter(t, requires_grad=False)
+
+
 class InferenceNet(nn.Module):
     """Frozen, BN-folded, channels-last copy of an AlphaZeroNet for the engine's leaf batches."""
 
@@ -167,121 +197,122 @@ class InferenceNet(nn.Module):
         self.use_fused_block = True  # 64-filter towers: azsp_resblock_tiled instead of two azsp_conv3x3_tiled launches per block
         self.use_split_tower = True  # fp32 networks: azsp_conv3x3_split (hi + lo f16 pairs, three MFMA products) instead of the library
         self.use_split_heads = True  # ... and azsp_split_features / azsp_stem_split / azsp_head_split around it (whole evaluator hand-written)
+        self.use_fused_fc = True
         self.mf = torch.channels_last if channels_last else torch.contiguous_format
         self.stem_pad = net.conv_block[0].padding[0]
+        self.filters = net.conv_block[0].out_channels
+        self.n_blocks = len(net.res_blocks)
+        # fp32-class path: every activation is carried as v * 2^-act_shift (an exact rescaling of a ReLU + skip tower, see set_act_shift)
+        self.act_shift, self.act_calibrated, self.act_max_abs = 0, False, 0.0
+        self.split_fallback_reason = ""  # set when the fp32-class kernels are given up for this network (library fp32 instead)
+        self._scratch_cache = {}
         with torch.no_grad():
             convs = [_fold(net.conv_block[0], net.conv_block[1])]
             for blk in net.res_blocks:
                 convs.append(_fold(blk.conv_block1[0], blk.conv_block1[1]))
                 convs.append(_fold(blk.conv_block2[0], blk.conv_block2[1]))
-            self.n_blocks = len(net.res_blocks)
-            # hand-written MFMA convolutions (azsp_conv3x3_tiled): weights as [tap = ky*3+kx][cout][cin] bf16, bias fp32
-            self.filters = net.conv_block[0].out_channels
-            # element format of the tiled kernels: bf16 (default) or f16 (dtype = torch.float16: azsp_*_f16, same MFMA rate, 3 more significand bits)
-            pk = self.pack_dtype = torch.float16 if dtype == torch.float16 else torch.bfloat16
-            self.wp = nn.ParameterList([nn.Parameter(w.permute(2, 3, 0, 1).reshape(9, w.shape[0], w.shape[1]).to(pk).contiguous(),
-                                                     requires_grad=False) for w, _ in convs[1:]])
-            self.b32 = nn.ParameterList([nn.Parameter(b.float().contiguous(), requires_grad=False) for _, b in convs[1:]])
-            # fp32-class path: every activation is carried as v * 2^-act_shift (an exact rescaling of a ReLU + skip tower, see set_act_shift)
-            self.act_shift, self.act_calibrated, self.act_max_abs = 0, False, 0.0
-            self.split_fallback_reason = ""  # set when the fp32-class kernels are given up for this network (library fp32 instead)
-            self.stem_fallback_reason = ""   # set when only the split STEM cannot carry this network (library stem + heads around the split tower)
-            if dtype == torch.float32:  # split-precision tower (azsp_conv3x3_split)
-                try:
-                    packed = [split_weights_f16(w) for w, _ in convs[1:]]
-                except ValueError as e:  # a folded tower weight the f16-pair format cannot carry: this network runs on the library
-                    packed = [torch.zeros(2, 9, w.shape[0], w.shape[1], dtype=torch.float16) for w, _ in convs[1:]]
-                    self.split_fallback_reason = str(e).split(";")[0]
-                self.wsp = nn.ParameterList([nn.Parameter(p, requires_grad=False) for p in packed])
-                # tower biases as the split kernels see them: b * 2^-act_shift (set_act_shift); b32 keeps the unscaled values
-                self.b_sp = nn.ParameterList([nn.Parameter(b.float().clone().contiguous(), requires_grad=False) for _, b in convs[1:]])
-                # this network's own range record (include/azsp.h: range_rec_dev): [events, bits of the largest |v|]
-                self.register_buffer("range_rec", torch.zeros(2, dtype=torch.int32), persistent=False)
-            self.w = nn.ParameterList([nn.Parameter(w.to(dtype).contiguous(memory_format=self.mf), requires_grad=False) for w, _ in convs])
-            self.b = nn.ParameterList([nn.Parameter(b.to(dtype), requires_grad=False) for _, b in convs])
-            # stem for the tiled path (azsp_stem_tiled): [tap][cout][32 in], input channels 17.. zero
+            self._pack_library(net, convs)
+            self._pack_tiled(net, convs)
+            if dtype == torch.float32:
+                self._pack_split(net, convs)
+
+    def _pack_library(self, net, convs):
+        """Weights of the library path (PyTorch convolutions and Linear layers in self.dtype) and the fp32 1x1 head weights."""
+        self.w = nn.ParameterList([_frozen(w.to(self.dtype).contiguous(memory_format=self.mf)) for w, _ in convs])
+        self.b = nn.ParameterList([_frozen(b.to(self.dtype)) for _, b in convs])
+        pw, pb = _fold(net.policy_head[0], net.policy_head[1])
+        vw, vb = _fold(net.value_head[0], net.value_head[1])
+        self.npol, self.nval = pw.shape[0], vw.shape[0]
+        # both 1x1 heads share one convolution (2 policy planes + 1 value plane)
+        self.head_w32 = _frozen(torch.cat([pw, vw], 0).reshape(pw.shape[0] + vw.shape[0], -1).float().contiguous())
+        self.head_b32 = _frozen(torch.cat([pb, vb], 0).float().contiguous())
+        self.head_w = _frozen(torch.cat([pw, vw], 0).to(self.dtype).contiguous(memory_format=self.mf))
+        self.head_b = _frozen(torch.cat([pb, vb], 0).to(self.dtype))
+        self.pol_fc_w, self.pol_fc_b = _frozen(net.policy_head[4].weight.to(self.dtype)), _frozen(net.policy_head[4].bias.to(self.dtype))
+        self.val_fc1_w, self.val_fc1_b = _frozen(net.value_head[4].weight.to(self.dtype)), _frozen(net.value_head[4].bias.to(self.dtype))
+        self.val_fc2_w, self.val_fc2_b = _frozen(net.value_head[6].weight.to(self.dtype)), _frozen(net.value_head[6].bias.to(self.dtype))
+        self.num_actions, self.fc_width = net.policy_head[4].weight.shape[0], net.value_head[4].weight.shape[0]
+        self.fc_b2 = float(net.value_head[6].bias.item())
+
+    def _pack_tiled(self, net, convs):
+        """The tiled kernels' packing (azsp_conv3x3_tiled / azsp_stem_tiled / azsp_fc_heads): weights as [tap = ky*3+kx][cout][cin] in
+        pack_dtype -- bf16, or f16 for dtype = torch.float16 (azsp_*_f16: same MFMA rate, 3 more significand bits) -- biases fp32.
+        b32 is also the unscaled source of the split kernels' biases."""
+        pk = self.pack_dtype = torch.float16 if self.dtype == torch.float16 else torch.bfloat16
+        self.wp = nn.ParameterList([_frozen(w.permute(2, 3, 0, 1).reshape(9, w.shape[0], w.shape[1]).to(pk).contiguous()) for w, _ in convs[1:]])
+        self.b32 = nn.ParameterList([_frozen(b.float().contiguous()) for _, b in convs[1:]])
+        # stem (azsp_stem_tiled; the split stem too): [tap][cout][32 in], input channels 17.. zero
+        sw = convs[0][0]
+        self.stem_ok = sw.shape[1] <= 32 and sw.shape[2] == 3 and sw.shape[3] == 3 and self.stem_pad in (1, 3)
+        if self.stem_ok:
+            swp = torch.zeros(9, sw.shape[0], 32)
+            swp[:, :, : sw.shape[1]] = sw.permute(2, 3, 0, 1).reshape(9, sw.shape[0], sw.shape[1])
+            self.stem_wp = _frozen(swp.to(pk).contiguous())
+            self.stem_b32 = _frozen(convs[0][1].float().contiguous())
+
+        # zero-padded copies for azsp_fc_heads: weights [ceil32(out)][ceil16(in)] in pack_dtype, biases / last layer fp32
+        def _pad_w(wt):
+            out = torch.zeros((wt.shape[0] + 31) // 32 * 32, (wt.shape[1] + 15) // 16 * 16)
+            out[: wt.shape[0], : wt.shape[1]] = wt
+            return _frozen(out.to(pk).contiguous())
+
+        def _pad_v(v):
+            out = torch.zeros((v.numel() + 31) // 32 * 32)
+            out[: v.numel()] = v.reshape(-1)
+            return _frozen(out.float().contiguous())
+
+        self.fc_wp, self.fc_bp = _pad_w(net.policy_head[4].weight), _pad_v(net.policy_head[4].bias)
+        self.fc_w1, self.fc_b1 = _pad_w(net.value_head[4].weight), _pad_v(net.value_head[4].bias)
+        self.fc_w2 = _pad_v(net.value_head[6].weight)
+
+    def _pack_split(self, net, convs):
+        """fp32 networks: the split-precision packing (split_weights_f16) of the tower and the stem, the heads' fp32 weights, and the
+        stem's initial activation shift.  A folded weight the f16 pairs cannot carry gives the fp32-class kernels up for this network
+        (split_fallback_reason: the library's fp32 convolutions instead)."""
+        try:
+            packed = [split_weights_f16(w) for w, _ in convs[1:]]
+        except ValueError as e:  # a folded tower weight the f16-pair format cannot carry: this network runs on the library
+            packed = [torch.zeros(2, 9, w.shape[0], w.shape[1], dtype=torch.float16) for w, _ in convs[1:]]
+            self.split_fallback_reason = str(e).split(";")[0]
+        self.wsp = nn.ParameterList([_frozen(p) for p in packed])
+        # tower biases as the split kernels see them: b * 2^-act_shift (set_act_shift); b32 keeps the unscaled values
+        self.b_sp = nn.ParameterList([_frozen(b.float().clone().contiguous()) for _, b in convs[1:]])
+        # this network's own range record (include/azsp.h: range_rec_dev): [events, bits of the largest |v|]
+        self.register_buffer("range_rec", torch.zeros(2, dtype=torch.int32), persistent=False)
+        k0 = 0
+        if self.stem_ok:  # azsp_stem_split: [plane][tap][cout][32 in] f16, input channels 17.. zero
             sw = convs[0][0]
-            self.stem_ok = sw.shape[1] <= 32 and sw.shape[2] == 3 and sw.shape[3] == 3 and self.stem_pad in (1, 3)
-            if self.stem_ok:
-                swp = torch.zeros(9, sw.shape[0], 32)
-                swp[:, :, : sw.shape[1]] = sw.permute(2, 3, 0, 1).reshape(9, sw.shape[0], sw.shape[1])
-                self.stem_wp = nn.Parameter(swp.to(pk).contiguous(), requires_grad=False)
-                self.stem_b32 = nn.Parameter(convs[0][1].float().contiguous(), requires_grad=False)
-                if dtype == torch.float32:  # azsp_stem_split: [plane][tap][cout][32 in] f16, input channels 17.. zero
-                    sw32 = torch.zeros(sw.shape[0], 32, 3, 3)
-                    sw32[:, : sw.shape[1]] = sw
-                    self.register_buffer("stem_w32", sw32.float().contiguous(), persistent=False)  # unscaled source of stem_wsp
-                    # loud stem weights (|w| > 65504) are carried by an initial activation shift; beyond MAX_ACT_SHIFT: library fp32
-                    wmax = float(sw32.abs().max()) if bool(torch.isfinite(sw32).all()) else float("inf")
-                    k0 = 0
-                    while wmax * 2.0 ** -k0 > F16_MAX and k0 <= self.MAX_ACT_SHIFT:
-                        k0 += 1
-                    if k0 > self.MAX_ACT_SHIFT:
-                        # The split STEM cannot carry these weights (recorded separately: stem_fallback_reason).  The tower is given up WITH
-                        # it although its own weights may be ordinary (ADVICE r5 asked to keep it): folded stem weights beyond
-                        # 65504 * 2^MAX_ACT_SHIFT = 3.4e7 on 0 / 1 input planes mean stem outputs of that size, which the tower's f16 pairs
-                        # cannot carry at any allowed scale -- and the tower-only path has no calibration pass that would find out before
-                        # it clamps (test_gpu_network_beyond_the_format_falls_back_to_library_fp32 is exactly this network).
-                        self.stem_fallback_reason = f"folded stem weights reach {wmax:.3g}: beyond the f16-pair format"
-                        self.split_fallback_reason = self.split_fallback_reason or self.stem_fallback_reason
-                        k0 = 0
-                    self.stem_wsp = nn.Parameter(split_weights_f16(sw32 * 2.0 ** -k0) if not (self.split_fallback_reason or self.stem_fallback_reason)
-                                                 else torch.zeros(2, 9, sw.shape[0], 32, dtype=torch.float16), requires_grad=False)
-                    self.stem_b_sp = nn.Parameter(convs[0][1].float().clone().contiguous(), requires_grad=False)
-                    self._initial_act_shift = k0
-            pw, pb = _fold(net.policy_head[0], net.policy_head[1])
-            vw, vb = _fold(net.value_head[0], net.value_head[1])
-            self.npol, self.nval = pw.shape[0], vw.shape[0]
-            self.head_w32 = nn.Parameter(torch.cat([pw, vw], 0).reshape(pw.shape[0] + vw.shape[0], -1).float().contiguous(), requires_grad=False)
-            if dtype == torch.float32:  # azsp_head_split reads head_w32 * 2^act_shift (undoes the activation scale exactly)
-                self.head_w_sp = nn.Parameter(self.head_w32.detach().clone(), requires_grad=False)
-                if getattr(self, "_initial_act_shift", 0) and not (self.split_fallback_reason or self.stem_fallback_reason):
-                    self.set_act_shift(self._initial_act_shift)
-            self.head_b32 = nn.Parameter(torch.cat([pb, vb], 0).float().contiguous(), requires_grad=False)
-            # both 1x1 heads share one convolution (2 policy planes + 1 value plane)
-            self.head_w = nn.Parameter(torch.cat([pw, vw], 0).to(dtype).contiguous(memory_format=self.mf), requires_grad=False)
-            self.head_b = nn.Parameter(torch.cat([pb, vb], 0).to(dtype), requires_grad=False)
-            self.pol_fc_w = nn.Parameter(net.policy_head[4].weight.to(dtype), requires_grad=False)
-            self.pol_fc_b = nn.Parameter(net.policy_head[4].bias.to(dtype), requires_grad=False)
-            self.val_fc1_w = nn.Parameter(net.value_head[4].weight.to(dtype), requires_grad=False)
-            self.val_fc1_b = nn.Parameter(net.value_head[4].bias.to(dtype), requires_grad=False)
-            self.val_fc2_w = nn.Parameter(net.value_head[6].weight.to(dtype), requires_grad=False)
-            self.val_fc2_b = nn.Parameter(net.value_head[6].bias.to(dtype), requires_grad=False)
-            # zero-padded copies for azsp_fc_heads: weights [ceil32(out)][ceil16(in)] bf16, biases / last layer fp32
-            def _pad_w(wt):
-                out = torch.zeros((wt.shape[0] + 31) // 32 * 32, (wt.shape[1] + 15) // 16 * 16)
-                out[: wt.shape[0], : wt.shape[1]] = wt
-                return nn.Parameter(out.to(pk).contiguous(), requires_grad=False)
+            sw32 = torch.zeros(sw.shape[0], 32, 3, 3)
+            sw32[:, : sw.shape[1]] = sw
+            self.register_buffer("stem_w32", sw32.float().contiguous(), persistent=False)  # unscaled source of stem_wsp
+            # loud stem weights (|w| > 65504) are carried by an initial activation shift; beyond MAX_ACT_SHIFT: library fp32
+            wmax = float(sw32.abs().max()) if bool(torch.isfinite(sw32).all()) else float("inf")
+            while wmax * 2.0 ** -k0 > F16_MAX and k0 <= self.MAX_ACT_SHIFT:
+                k0 += 1
+            if k0 > self.MAX_ACT_SHIFT:
+                # The tower is given up with the stem although its own weights may be ordinary: folded stem weights beyond
+                # 65504 * 2^MAX_ACT_SHIFT = 3.4e7 on 0 / 1 input planes mean stem outputs of that size, which the tower's f16 pairs
+                # cannot carry at any allowed scale (test_gpu_network_beyond_the_format_falls_back_to_library_fp32 is exactly this network).
+                self.split_fallback_reason = self.split_fallback_reason or f"folded stem weights reach {wmax:.3g}: beyond the f16-pair format"
+                k0 = 0
+            self.stem_wsp = _frozen(split_weights_f16(sw32 * 2.0 ** -k0) if not self.split_fallback_reason
+                                    else torch.zeros(2, 9, sw.shape[0], 32, dtype=torch.float16))
+            self.stem_b_sp = _frozen(convs[0][1].float().clone().contiguous())
+        self.head_w_sp = _frozen(self.head_w32.detach().clone())  # azsp_head_split reads head_w32 * 2^act_shift (undoes the activation scale)
+        # azsp_head_split: fp32 Linear weights transposed [inputs][outputs]
+        self.pol_fc_wt = _frozen(net.policy_head[4].weight.float().t().contiguous())
+        self.val_fc1_wt = _frozen(net.value_head[4].weight.float().t().contiguous())
+        self.pol_fc_b32 = _frozen(net.policy_head[4].bias.float().contiguous())
+        self.val_fc1_b32 = _frozen(net.value_head[4].bias.float().contiguous())
+        self.val_fc2_w32 = _frozen(net.value_head[6].weight.float().reshape(-1).contiguous())
+        if k0 and not self.split_fallback_reason:
+            self.set_act_shift(k0)
 
-            def _pad_v(v):
-                out = torch.zeros((v.numel() + 31) // 32 * 32)
-                out[: v.numel()] = v.reshape(-1)
-                return nn.Parameter(out.float().contiguous(), requires_grad=False)
-
-            self.fc_wp, self.fc_bp = _pad_w(net.policy_head[4].weight), _pad_v(net.policy_head[4].bias)
-            self.fc_w1, self.fc_b1 = _pad_w(net.value_head[4].weight), _pad_v(net.value_head[4].bias)
-            self.fc_w2, self.fc_b2 = _pad_v(net.value_head[6].weight), float(net.value_head[6].bias.item())
-            self.num_actions, self.fc_width = net.policy_head[4].weight.shape[0], net.value_head[4].weight.shape[0]
-            if dtype == torch.float32:  # azsp_head_split: fp32 Linear weights transposed [inputs][outputs]
-                self.pol_fc_wt = nn.Parameter(net.policy_head[4].weight.float().t().contiguous(), requires_grad=False)
-                self.val_fc1_wt = nn.Parameter(net.value_head[4].weight.float().t().contiguous(), requires_grad=False)
-                self.pol_fc_b32 = nn.Parameter(net.policy_head[4].bias.float().contiguous(), requires_grad=False)
-                self.val_fc1_b32 = nn.Parameter(net.value_head[4].bias.float().contiguous(), requires_grad=False)
-                self.val_fc2_w32 = nn.Parameter(net.value_head[6].weight.float().reshape(-1).contiguous(), requires_grad=False)
-            self.use_fused_fc = True
-
-    def _tiled_tower_ok(self, x):
-        """Shapes with a weight-stationary tower kernel (azsp_conv3x3_tiled / azsp_resblock_tiled): 9x9 planes x 128 filters (Go 9x9),
-        17x17 planes x 64 filters (the 13x13 Gomoku network after its pad-3 stem), 9x9 planes x 64 filters (the reference's 9x9_12b64
-        run) and 19x19 planes x 256 filters (the jumbo Go network)."""
-        return (self.binding is not None and self.use_fused_conv and self.use_tiled_tower and x.is_cuda and x.dtype == torch.bfloat16
-                and x.shape[2] == x.shape[3] and (x.shape[1], x.shape[2]) in ((128, 9), (64, 17), (64, 9), (256, 19))
-                and x.is_contiguous(memory_format=torch.channels_last))
-
-    SPLIT_TOWER_SHAPES = ((128, 9), (64, 9), (64, 17))          # (filters, tower planes) with a weight-stationary azsp_conv3x3_split kernel
-    SPLIT_TOWER_ANY_PLANES = (64, 128, 256)                     # filters of the wave-per-tile kernel (csrc/az_conv_spg.h): planes 3 .. 64
-    SPLIT_FUSED_SHAPES = ((64, 17), (64, 9))                    # ... with a one-launch-per-block kernel (azsp_resblock_split)
-    SPLIT_EVAL_SHAPES = ((128, 9, 1), (64, 9, 1), (64, 13, 3))  # (filters, board, stem pad) whose whole evaluator runs on the split kernels
+    SPLIT_EVAL_SHAPES = tuple(s for s, dts in EVAL_KERNELS.items() if "fp32" in dts)  # (filters, board, stem pad): whole split evaluator
+    SPLIT_TOWER_SHAPES = tuple((f, _planes(n, p)) for f, n, p in SPLIT_EVAL_SHAPES)    # (filters, tower planes): weight-stationary split tower
+    SPLIT_TOWER_ANY_PLANES = (64, 128, 256)  # filters of the wave-per-tile split kernel (csrc/az_conv_spg.h): planes 3 .. 64
+    SPLIT_FUSED_SHAPES = FUSED_BLOCK_SHAPES
+    TILED_TOWER_SHAPES = frozenset((f, _planes(n, p)) for (f, n, p), dts in EVAL_KERNELS.items() if "bf16" in dts)
 
     @classmethod
     def split_tower_shape(cls, filters, planes):
@@ -289,41 +320,57 @@ class InferenceNet(nn.Module):
         64 / 128 / 256 filters (k_conv3x3_spg: the reference's 19x19 x 256 jumbo tower at its own precision, training_go_jumbo.py:46-47)."""
         return (filters, planes) in cls.SPLIT_TOWER_SHAPES or (filters in cls.SPLIT_TOWER_ANY_PLANES and 3 <= planes <= 64)
 
-    def _split_tower_ok(self, x):
-        """fp32 networks with 64 / 128 / 256 filters: the tower runs on azsp_conv3x3_split (include/azsp.h) -- the reference's precision
-        class (pipeline.py:91-123 evaluates in fp32) on the f16 matrix cores: the weight-stationary kernels on 9x9 planes with 128 or
-        64 filters and on 17x17 planes with 64 filters (the 13x13 Gomoku tower), the wave-per-tile kernel on every other plane size."""
-        return (self.binding is not None and self.use_fused_conv and self.use_split_tower and x.is_cuda and x.dtype == torch.float32
-                and self.dtype == torch.float32 and x.shape[2] == x.shape[3] and self.split_tower_shape(x.shape[1], x.shape[2])
-                and not self.split_fallback_reason and x.is_contiguous(memory_format=torch.channels_last))
+    def _path(self, board_size, device):
+        """The evaluator the forward of this network runs on `device`: (path, fused block, wave-per-tile) with path one of
+        'tiled'       the whole evaluator on the tiled bf16 / f16 kernels (azsp_stem_tiled -> tower -> azsp_head_tiled),
+        'tiled_tower' the tiled tower behind a library stem and heads,
+        'split'       the whole fp32 evaluator on the split-precision kernels (azsp_stem_split -> azsp_conv3x3_split tower -> azsp_head_split),
+        'split_tower' the split tower behind a library fp32 stem and heads,
+        'library'     library convolutions + the azsp_bias_act epilogue;
+        fused block: the tower runs one launch per ResNetBlock; wave-per-tile: the split tower runs k_conv3x3_spg."""
+        dt, tower = _DT_CLASS.get(self.dtype), (self.filters, _planes(board_size, self.stem_pad))
+        fused = self.use_fused_block and tower in FUSED_BLOCK_SHAPES
+        on = self.binding is not None and torch.device(device).type == "cuda" and self.use_fused_conv
+        whole = (on and dt in EVAL_KERNELS.get((self.filters, board_size, self.stem_pad), ()) and self.stem_ok
+                 and self.npol + self.nval == 3)
+        if dt in ("bf16", "f16") and on and self.use_tiled_tower:
+            if whole and (dt == "bf16" or (self.num_actions, self.fc_width) == F16_HEADS):
+                return "tiled", fused and dt == "bf16", False
+            if dt == "bf16" and tower in self.TILED_TOWER_SHAPES:
+                return "tiled_tower", fused, False
+        if dt == "fp32" and on and self.use_split_tower and not self.split_fallback_reason:
+            if whole and self.use_split_heads:
+                return "split", fused, False
+            if self.split_tower_shape(*tower):
+                return "split_tower", fused, tower not in self.SPLIT_TOWER_SHAPES
+        return "library", False, False
 
     def supports_split_features(self, board_size, device):
         """True when the WHOLE fp32 evaluator runs on the split-precision kernels (azsp_split_features -> azsp_stem_split ->
-        azsp_conv3x3_split tower -> azsp_head_split): fp32 networks, 9x9 Go with 128 or 64 filters (pad-1 stem), 13x13 Gomoku with 64
-        filters (pad-3 stem, 17x17 planes)."""
-        return (self.binding is not None and torch.device(device).type == "cuda" and self.dtype == torch.float32 and self.use_fused_conv
-                and self.use_split_tower and self.use_split_heads and self.stem_ok and self.npol + self.nval == 3
-                and not self.split_fallback_reason and not self.stem_fallback_reason
-                and (self.filters, board_size, self.stem_pad) in self.SPLIT_EVAL_SHAPES)
+        azsp_conv3x3_split tower -> azsp_head_split): the EVAL_KERNELS shapes of fp32 networks."""
+        return self._path(board_size, device)[0] == "split"
+
+    def _scratch(self, kind, slot, key, make):
+        """Scratch memory of one `kind` ('split' | 'tiled' | 'head') per `slot`: callers whose forwards must not share scratch use
+        different slots (slot 0: the engine-facing forward, the one SelfPlayActor captures in a hipGraph -- its buffers must never be
+        freed by another caller of the same InferenceNet; slot 3: every other call -- evaluation games, drop-in eval_func wrappers,
+        tests; slots 1-2: the half-batch experiment of tools/overlap_actor.py).  A slot holds one `key` (size, device) at a time: a
+        call with another key frees the slot's entry before make() allocates the new one."""
+        if self._scratch_cache.get((kind, slot), (key,))[0] != key:
+            del self._scratch_cache[(kind, slot)]
+        if (kind, slot) not in self._scratch_cache:
+            self._scratch_cache[(kind, slot)] = (key, make())
+        return self._scratch_cache[(kind, slot)][1]
 
     def _split_buffers(self, B, S, C, device, slot=0, board_size=None):
-        """Scratch of the split-precision evaluator per `slot` (the scheme of _tiled_buffers): three rotating tower buffers, the output
-        rows and -- only for callers that hand over fp32 planes (board_size given) -- the stem's feature buffer, sized with the BOARD
-        (13 at Gomoku, not the 17 of the tower planes); the engine-facing forward passes the engine's own AZSP_FEAT_F16_SPLIT tensor and
-        never allocates it.  A slot holds one batch size at a time; slot 0 is the engine-facing forward (the one SelfPlayActor captures
-        in a hipGraph -- its buffers must never be freed by another caller of the same InferenceNet), slot 3 every other call
-        (evaluation games, drop-in eval_func wrappers, tests)."""
+        """[three rotating tower buffers, feature buffer, priors, values] of the split-precision evaluator.  The stem's feature buffer is
+        allocated only for callers that hand over fp32 planes (board_size given), sized with the BOARD (13 at Gomoku, not the 17 of the
+        tower planes); the engine-facing forward passes the engine's own AZSP_FEAT_F16_SPLIT tensor and never allocates it."""
         dll = self.binding.dll
         nb = dll.azsp_split_bytes(B, S, C) // 2
-        cache = self.__dict__.setdefault("_split_cache", {})
-        key = (slot, B, S, str(device))
-        if key not in cache:
-            for k in [k for k in cache if k[0] == slot]:
-                del cache[k]
-            cache[key] = [[torch.zeros(nb, dtype=torch.float16, device=device) for _ in range(3)], None,
-                          torch.empty((B, self.num_actions), dtype=torch.float32, device=device),
-                          torch.empty((B,), dtype=torch.float32, device=device)]
-        ent = cache[key]
+        ent = self._scratch("split", slot, (B, S, str(device)), lambda: [
+            [torch.zeros(nb, dtype=torch.float16, device=device) for _ in range(3)], None,
+            torch.empty((B, self.num_actions), dtype=torch.float32, device=device), torch.empty((B,), dtype=torch.float32, device=device)])
         if board_size is not None and ent[1] is None:
             ent[1] = torch.zeros(dll.azsp_split_bytes(B, board_size, 32) // 2, dtype=torch.float16, device=device)
         return ent
@@ -333,24 +380,20 @@ class InferenceNet(nn.Module):
         """planes: observation planes [B,17,N,N] fp32, contiguous NCHW (the engine's AZSP_FEAT_F32 features) -- or, with
         split_features = (rows, board_size), the engine's AZSP_FEAT_F16_SPLIT tensor itself (the stem's input layout: no conversion
         launch).  The whole evaluator at the reference's precision class (pipeline.py:91-123 evaluates in fp32) on hand-written kernels.
-        slot: scratch buffers to use (see _split_buffers); None = 0 when the outputs go to caller tensors (the engine's forward), 3 otherwise.
+        slot: scratch buffers to use (see _scratch); None = 0 when the outputs go to caller tensors (the engine's forward), 3 otherwise.
         probe: optional callback(buffer, B) after the stem and after every tower convolution (calibrate_activation_scale)."""
-        import ctypes
-
+        if slot is None:
+            slot = 0 if priors_out is not None else 3
         if not self.act_calibrated and probe is None and planes.is_cuda and not torch.cuda.is_current_stream_capturing():
-            self.calibrate_activation_scale(planes, split_features=split_features, slot=slot if slot is not None else (0 if priors_out is not None else 3))
+            self.calibrate_activation_scale(planes, split_features=split_features, slot=slot)
             if self.split_fallback_reason:  # the calibration gave the fp32-class kernels up for this network: library fp32 convolutions
                 return self._forward_after_split_fallback(planes, priors_out, values_out, split_features)
-        dll, ck = self.binding.dll, self._ck
-        st = ctypes.c_void_p(torch.cuda.current_stream(planes.device).cuda_stream) if planes.is_cuda else None  # (host twin: CPU tensors)
+        dll, st = self.binding.dll, _stream(planes)
         if split_features is not None:
             B, n = split_features
         else:
             B, cin, n, _ = planes.shape
-        C = self.filters
-        S = n + 2 * (self.stem_pad - 1)  # planes of the tower (network.py:101-105: the Gomoku stem pads by 3)
-        if slot is None:
-            slot = 0 if priors_out is not None else 3
+        C, S = self.filters, _planes(n, self.stem_pad)
         (a, m, o), feat, pri_buf, v_buf = self._split_buffers(B, S, C, planes.device, slot, board_size=None if split_features is not None else n)
         self._split = (a, m, o, B)  # marks that the split kernels ran (tests); bench.py replays the tower on slot 0's buffers
         rr = self._range_ptr(planes.device)
@@ -358,10 +401,10 @@ class InferenceNet(nn.Module):
             assert planes.dtype == torch.float16 and planes.numel() >= dll.azsp_split_bytes(B, n, 32) // 2
             feat = planes
         else:
-            ck(dll.azsp_split_features(planes.data_ptr(), feat.data_ptr(), B, n, cin, rr, st), "azsp_split_features")
+            _ck(dll.azsp_split_features(planes.data_ptr(), feat.data_ptr(), B, n, cin, rr, st), "azsp_split_features")
         # engine-written features are 0 / 1 planes (exact f16 values, lo plane never written): the stem skips the lo plane (identical result)
         stem = dll.azsp_stem_split_exact if split_features is not None else dll.azsp_stem_split
-        ck(stem(feat.data_ptr(), self.stem_wsp.data_ptr(), self.stem_b_sp.data_ptr(), a.data_ptr(), B, n, C, self.stem_pad, 1, rr, st), "azsp_stem_split")
+        _ck(stem(feat.data_ptr(), self.stem_wsp.data_ptr(), self.stem_b_sp.data_ptr(), a.data_ptr(), B, n, C, self.stem_pad, 1, rr, st), "azsp_stem_split")
         if probe is not None:
             probe(a, B)
         a = self._blocks_split(a, m, o, B, S, C, st, rr, probe)
@@ -369,9 +412,9 @@ class InferenceNet(nn.Module):
             return None
         pri = priors_out if priors_out is not None else pri_buf
         v = values_out if values_out is not None else v_buf
-        ck(dll.azsp_head_split(a.data_ptr(), self.head_w_sp.data_ptr(), self.head_b32.data_ptr(), self.pol_fc_wt.data_ptr(), self.pol_fc_b32.data_ptr(),
-                               self.val_fc1_wt.data_ptr(), self.val_fc1_b32.data_ptr(), self.val_fc2_w32.data_ptr(), ctypes.c_float(self.fc_b2),
-                               pri.data_ptr(), v.data_ptr(), B, S, C, self.num_actions, self.fc_width, self.npol, st), "azsp_head_split")
+        _ck(dll.azsp_head_split(a.data_ptr(), self.head_w_sp.data_ptr(), self.head_b32.data_ptr(), self.pol_fc_wt.data_ptr(), self.pol_fc_b32.data_ptr(),
+                                self.val_fc1_wt.data_ptr(), self.val_fc1_b32.data_ptr(), self.val_fc2_w32.data_ptr(), ctypes.c_float(self.fc_b2),
+                                pri.data_ptr(), v.data_ptr(), B, S, C, self.num_actions, self.fc_width, self.npol, st), "azsp_head_split")
         return (pri, v) if priors_out is not None else (pri.clone(), v.clone())  # the cached output buffers are reused by the next call
 
     def _range_ptr(self, device):
@@ -387,14 +430,12 @@ class InferenceNet(nn.Module):
         value beyond f16's finite range (clamped to +-65504 where the reference's fp32 network would carry it) since the last reset,
         and the largest such |v| in the kernels' own (scaled) units: multiply by 2^act_shift for the network's units.  Synchronises
         the stream.  Another InferenceNet in the same process has its own record."""
-        import ctypes
-
         ev, mx = ctypes.c_uint32(0), ctypes.c_float(0.0)
         rec = self.range_rec.data_ptr() if self.range_rec.is_cuda else None
-        if rec is not None and stream is None:
-            stream = ctypes.c_void_p(torch.cuda.current_stream(self.range_rec.device).cuda_stream)
+        if stream is None:
+            stream = _stream(self.range_rec)
         with torch.cuda.device(self.range_rec.device) if rec is not None else _nullcontext():
-            self._ck(self.binding.dll.azsp_split_range_read(rec, ctypes.byref(ev), ctypes.byref(mx), int(bool(reset)), stream), "azsp_split_range_read")
+            _ck(self.binding.dll.azsp_split_range_read(rec, ctypes.byref(ev), ctypes.byref(mx), int(bool(reset)), stream), "azsp_split_range_read")
         return int(ev.value), float(mx.value)
 
     def poll_range(self, planes=None):
@@ -405,8 +446,6 @@ class InferenceNet(nn.Module):
             return 0
         ev, mx = self.split_range_status(reset=True)
         if ev:
-            import warnings
-
             old = self.act_shift
             if planes is not None and self.supports_split_features(planes.shape[2], planes.device):
                 self.set_act_shift(min(self.MAX_ACT_SHIFT, old + 2))
@@ -414,8 +453,6 @@ class InferenceNet(nn.Module):
             else:
                 # the split tower behind a library stem / heads (or no batch given): no layer-by-layer calibration pass -- raise the scale
                 # by what the record shows (a lower bound: clamped values hide the true maximum) + 16x, as SelfPlayActor does
-                import math
-
                 k = min(self.MAX_ACT_SHIFT, old + max(2, math.ceil(math.log2(max(mx, F16_MAX) / F16_MAX)) + 4))
                 if k > old:
                     self.set_act_shift(k)
@@ -443,7 +480,7 @@ class InferenceNet(nn.Module):
             raise ValueError(f"act_shift {k} out of range")
         dn, up = 2.0 ** -k, 2.0 ** k
         if self.stem_ok:
-            if self.split_fallback_reason or self.stem_fallback_reason or float(self.stem_w32.abs().max()) * dn > F16_MAX:
+            if self.split_fallback_reason or float(self.stem_w32.abs().max()) * dn > F16_MAX:
                 # the split stem is out of use (library fallback), or the scaled stem weights do not fit the f16 pairs (a stem that
                 # needed an initial shift, being reset to 0 on the way to the library): nothing may read stem_wsp -- zero it, never raise
                 self.stem_wsp.zero_()
@@ -462,8 +499,6 @@ class InferenceNet(nn.Module):
         (never lowers it).  If that needs more than MAX_ACT_SHIFT the fp32-class kernels are given up for this network
         (split_fallback_reason; the caller's forward then runs the library's fp32 convolutions and `evaluator_path` says so).
         Returns (act_shift, largest |activation| in the network's own units).  Leaves the range record clean.  Not capturable."""
-        import math
-
         if planes.is_cuda and torch.cuda.is_current_stream_capturing():
             raise RuntimeError("calibrate_activation_scale cannot run inside a hipGraph capture")
         self.act_calibrated = True  # (set first: forward_split below must not recurse)
@@ -512,23 +547,23 @@ class InferenceNet(nn.Module):
 
     def _blocks_split(self, a, m, o, B, S, C, st, rr=None, probe=None):
         """All residual blocks on split-layout buffers; returns the buffer holding the tower output."""
-        dll, ck = self.binding.dll, self._ck
-        if self.use_fused_block and (C, S) in self.SPLIT_FUSED_SHAPES and probe is None:
+        dll = self.binding.dll
+        if self.use_fused_block and (C, S) in FUSED_BLOCK_SHAPES and probe is None:
             # 64 filters on 17x17 planes (13x13 Gomoku) or 9x9 planes (9x9 Go, two boards per tile): one launch per ResNetBlock, the intermediate
             # activation stays in LDS (azsp_resblock_split: two tensor passes through HBM per block instead of five; bit-identical to the
             # two launches below)
             for i in range(self.n_blocks):
-                ck(dll.azsp_resblock_split(a.data_ptr(), self.wsp[2 * i].data_ptr(), self.b_sp[2 * i].data_ptr(), self.wsp[2 * i + 1].data_ptr(),
-                                           self.b_sp[2 * i + 1].data_ptr(), o.data_ptr(), B, S, C, rr, st), "azsp_resblock_split")
+                _ck(dll.azsp_resblock_split(a.data_ptr(), self.wsp[2 * i].data_ptr(), self.b_sp[2 * i].data_ptr(), self.wsp[2 * i + 1].data_ptr(),
+                                            self.b_sp[2 * i + 1].data_ptr(), o.data_ptr(), B, S, C, rr, st), "azsp_resblock_split")
                 a, o = o, a
             return a
         for i in range(self.n_blocks):
-            ck(dll.azsp_conv3x3_split(a.data_ptr(), self.wsp[2 * i].data_ptr(), self.b_sp[2 * i].data_ptr(), None, m.data_ptr(), B, S, C, 1, rr, st),
-               "azsp_conv3x3_split")
+            _ck(dll.azsp_conv3x3_split(a.data_ptr(), self.wsp[2 * i].data_ptr(), self.b_sp[2 * i].data_ptr(), None, m.data_ptr(), B, S, C, 1, rr, st),
+                "azsp_conv3x3_split")
             if probe is not None:
                 probe(m, B)
-            ck(dll.azsp_conv3x3_split(m.data_ptr(), self.wsp[2 * i + 1].data_ptr(), self.b_sp[2 * i + 1].data_ptr(), a.data_ptr(), o.data_ptr(),
-                                      B, S, C, 1, rr, st), "azsp_conv3x3_split")
+            _ck(dll.azsp_conv3x3_split(m.data_ptr(), self.wsp[2 * i + 1].data_ptr(), self.b_sp[2 * i + 1].data_ptr(), a.data_ptr(), o.data_ptr(),
+                                       B, S, C, 1, rr, st), "azsp_conv3x3_split")
             if probe is not None:
                 probe(o, B)
             a, o = o, a
@@ -542,14 +577,10 @@ class InferenceNet(nn.Module):
     def _epilogue(self, y, bias, res=None):
         """relu(y + bias [+ res]) in place on a channels-last activation."""
         if self.binding is not None and y.is_cuda and y.is_contiguous(memory_format=torch.channels_last) and y.shape[1] % 8 == 0:
-            import ctypes
-
             B, C, H, W = y.shape
             dt = {torch.float32: 1, torch.bfloat16: 2, torch.float16: 3}[y.dtype]
-            rc = self.binding.dll.azsp_bias_act(y.data_ptr(), bias.data_ptr(), res.data_ptr() if res is not None else None, B * H * W, C,
-                                                dt, 1, ctypes.c_void_p(torch.cuda.current_stream(y.device).cuda_stream))
-            if rc != 0:
-                raise RuntimeError(f"azsp_bias_act failed with code {rc}")
+            _ck(self.binding.dll.azsp_bias_act(y.data_ptr(), bias.data_ptr(), res.data_ptr() if res is not None else None, B * H * W, C,
+                                               dt, 1, _stream(y)), "azsp_bias_act")
             return y
         y.add_(bias.view(1, -1, 1, 1))
         if res is not None:
@@ -557,116 +588,87 @@ class InferenceNet(nn.Module):
         return F.relu_(y)
 
     def _tiled_buffers(self, B, S, C, device, slot=0):
-        """Three rotating tower buffers (block input, middle, block output) per `slot`: callers whose forwards must not share scratch
-        memory use different slots (slot 0: the actor's graph-captured forward; slot 3: forward_planes, i.e. evaluation games / drop-in
-        eval_func calls on the same InferenceNet; slots 1-2: the half-batch experiment of tools/overlap_actor.py)."""
+        """Three rotating tower buffers (block input, middle, block output) of the tiled kernels."""
         n = self.binding.dll.azsp_tiled_bytes(B, S, C) // 2
-        cache = self.__dict__.setdefault("_tiled_cache", {})
-        key = (slot, n, str(device))
-        if key not in cache:
-            for k in [k for k in cache if k[0] == slot]:  # a slot holds one size at a time
-                del cache[k]
-            cache[key] = [torch.zeros(n, dtype=self.pack_dtype, device=device) for _ in range(3)]
+        bufs = self._scratch("tiled", slot, (n, str(device)), lambda: [torch.zeros(n, dtype=self.pack_dtype, device=device) for _ in range(3)])
         if slot == 0:
-            self._tiled = cache[key]  # (bench.py replays the tower on the activations of the last full-batch forward)
-        return cache[key]
+            self._tiled = bufs  # (bench.py replays the tower on the activations of the last full-batch forward)
+        return bufs
 
     def _head_buffers(self, B, k1, k2, device, slot=0):
-        cache = self.__dict__.setdefault("_head_cache", {})
-        key = (slot, B, str(device))
-        if key not in cache:
-            for k in [k for k in cache if k[0] == slot]:
-                del cache[k]
-            cache[key] = (torch.zeros((B + 1, k1), dtype=self.pack_dtype, device=device), torch.zeros((B + 1, k2), dtype=self.pack_dtype, device=device),
-                          torch.empty((B, self.num_actions), dtype=torch.float32, device=device), torch.empty((B,), dtype=torch.float32, device=device))
-        return cache[key]
-
-    @staticmethod
-    def _ck(rc, what):
-        if rc != 0:
-            raise RuntimeError(f"{what} failed with code {rc}")
+        return self._scratch("head", slot, (B, str(device)), lambda: (
+            torch.zeros((B + 1, k1), dtype=self.pack_dtype, device=device), torch.zeros((B + 1, k2), dtype=self.pack_dtype, device=device),
+            torch.empty((B, self.num_actions), dtype=torch.float32, device=device), torch.empty((B,), dtype=torch.float32, device=device)))
 
     def _blocks_tiled(self, a, m, o, B, S, C, st):
         """All residual blocks on tiled buffers; returns the buffer holding the tower output."""
-        dll, ck = self.binding.dll, self._ck
+        dll = self.binding.dll
         conv = dll.azsp_conv3x3_tiled_f16 if self.pack_dtype == torch.float16 else dll.azsp_conv3x3_tiled
-        if self.use_fused_block and (C, S) in ((64, 17), (64, 9)) and self.pack_dtype != torch.float16:
+        if self.use_fused_block and (C, S) in FUSED_BLOCK_SHAPES and self.pack_dtype != torch.float16:
             # 64 filters: both filter banks of a block fit in a CU's registers -> one launch per ResNetBlock, intermediate in LDS
             for i in range(self.n_blocks):
-                ck(dll.azsp_resblock_tiled(a.data_ptr(), self.wp[2 * i].data_ptr(), self.b32[2 * i].data_ptr(), self.wp[2 * i + 1].data_ptr(),
-                                           self.b32[2 * i + 1].data_ptr(), o.data_ptr(), B, S, C, st), "azsp_resblock_tiled")
+                _ck(dll.azsp_resblock_tiled(a.data_ptr(), self.wp[2 * i].data_ptr(), self.b32[2 * i].data_ptr(), self.wp[2 * i + 1].data_ptr(),
+                                            self.b32[2 * i + 1].data_ptr(), o.data_ptr(), B, S, C, st), "azsp_resblock_tiled")
                 a, o = o, a
             return a
         for i in range(self.n_blocks):
-            ck(conv(a.data_ptr(), self.wp[2 * i].data_ptr(), self.b32[2 * i].data_ptr(), None, m.data_ptr(), B, S, C, 1, st), "azsp_conv3x3_tiled")
-            ck(conv(m.data_ptr(), self.wp[2 * i + 1].data_ptr(), self.b32[2 * i + 1].data_ptr(), a.data_ptr(), o.data_ptr(), B, S, C, 1, st),
-               "azsp_conv3x3_tiled")
+            _ck(conv(a.data_ptr(), self.wp[2 * i].data_ptr(), self.b32[2 * i].data_ptr(), None, m.data_ptr(), B, S, C, 1, st), "azsp_conv3x3_tiled")
+            _ck(conv(m.data_ptr(), self.wp[2 * i + 1].data_ptr(), self.b32[2 * i + 1].data_ptr(), a.data_ptr(), o.data_ptr(), B, S, C, 1, st),
+                "azsp_conv3x3_tiled")
             a, o = o, a
         return a
 
     def evaluator_path(self, board_size, device):
         """Which kernels the forward pass of this network runs on `device` -- reported by bench.py (`config.evaluator`) and logged
         once by SelfPlayActor, so that an unsupported shape never degrades silently to the library path."""
-        if self.supports_tiled_features(board_size, device):
+        path, fused, wave_per_tile = self._path(board_size, device)
+        if path == "tiled":
             return "hand-written: tiled stem / tower / head / FC kernels (libazsp)" + (", f16 activations and weights" if self.dtype == torch.float16 else "")
-        if torch.device(device).type == "cuda" and self.dtype == torch.bfloat16 and self.binding is not None:
-            s = board_size + 2 * (self.stem_pad - 1)
-            if (self.filters, s) in ((128, 9), (64, 17), (64, 9), (256, 19)):
-                return "hand-written tower (azsp_conv3x3_tiled) behind a library stem and heads"
-        if self.supports_split_features(board_size, device):
-            fused = self.use_fused_block and (self.filters, board_size + 2 * (self.stem_pad - 1)) in self.SPLIT_FUSED_SHAPES
+        if path == "tiled_tower":
+            return "hand-written tower (azsp_conv3x3_tiled) behind a library stem and heads"
+        if path == "split":
             tower = ("azsp_resblock_split: one launch per ResNetBlock, intermediate activation in LDS; " if fused else "azsp_conv3x3_split: ")
             return (f"fp32 class, hand-written: split-precision stem / tower ({tower}hi + lo f16 pairs, three MFMA products, "
                     "fp32 accumulation) / fp32 heads (libazsp)")
-        if torch.device(device).type == "cuda" and self.dtype == torch.float32 and self.binding is not None and self.use_split_tower and not self.split_fallback_reason:
-            if self.split_tower_shape(self.filters, board_size + 2 * (self.stem_pad - 1)):
-                kern = "" if (self.filters, board_size + 2 * (self.stem_pad - 1)) in self.SPLIT_TOWER_SHAPES else ", wave-per-tile kernel k_conv3x3_spg"
-                return (f"fp32 class: hand-written split-precision tower (azsp_conv3x3_split{kern}: hi + lo f16 pairs, three MFMA products, fp32 "
-                        "accumulation) behind a library fp32 stem and heads" + (f" ({self.stem_fallback_reason})" if self.stem_fallback_reason else ""))
-        if self.split_fallback_reason or self.stem_fallback_reason:
-            return ("library fp32 convolutions + azsp_bias_act epilogue (fp32-class kernels given up for this network: "
-                    f"{self.split_fallback_reason or self.stem_fallback_reason})")
+        if path == "split_tower":
+            kern = ", wave-per-tile kernel k_conv3x3_spg" if wave_per_tile else ""
+            return (f"fp32 class: hand-written split-precision tower (azsp_conv3x3_split{kern}: hi + lo f16 pairs, three MFMA products, fp32 "
+                    "accumulation) behind a library fp32 stem and heads")
+        if self.split_fallback_reason:
+            return f"library fp32 convolutions + azsp_bias_act epilogue (fp32-class kernels given up for this network: {self.split_fallback_reason})"
         return f"library convolutions + azsp_bias_act epilogue (no hand-written kernel for {self.filters} filters on {board_size}x{board_size}, {self.dtype})"
 
     def supports_tiled_features(self, board_size, device):
-        """True when the whole evaluator can run on the tiled layout (azsp_stem_tiled -> tower -> azsp_head_tiled): 9x9 Go with 128 or
-        64 filters (pad-1 stem), 13x13 Gomoku with 64 filters (pad-3 stem, 17x17 planes) and 19x19 Go with 256 filters."""
-        shape_ok = (self.filters, board_size, self.stem_pad) in ((128, 9, 1), (64, 9, 1), (64, 13, 3), (256, 19, 1))
-        if self.dtype == torch.float16:  # the f16 variants exist for the 9x9 x 128 evaluator (82 actions, 128 fully connected units)
-            shape_ok = (self.filters, board_size, self.stem_pad, self.num_actions, self.fc_width) == (128, 9, 1, 82, 128)
-        return (self.binding is not None and torch.device(device).type == "cuda" and self.dtype in (torch.bfloat16, torch.float16) and shape_ok
-                and self.stem_ok and self.npol + self.nval == 3 and self.use_fused_conv and self.use_tiled_tower)
+        """True when the whole evaluator runs on the tiled layout (azsp_stem_tiled -> tower -> azsp_head_tiled): the EVAL_KERNELS
+        shapes of bf16 networks and of f16 networks with F16_HEADS."""
+        return self._path(board_size, device)[0] == "tiled"
 
     @torch.no_grad()
     def forward_tiled(self, feat, rows, board_size, priors_out=None, values_out=None, slot=0):
         """feat: the engine's AZSP_FEAT_BF16_TILED feature tensor for `rows` leaf positions (or a tile-aligned slice of it).  Stem,
         tower, the 1x1 head convolutions and the fully connected layers run on the tiled layout in hand-written kernels.  `slot`
-        selects the scratch buffers (see _tiled_buffers)."""
-        import ctypes
-
-        dll, ck = self.binding.dll, self._ck
+        selects the scratch buffers (see _scratch)."""
+        dll = self.binding.dll
         f16 = self.pack_dtype == torch.float16  # azsp_*_f16: the same kernels on f16 elements (feat is then the engine's AZSP_FEAT_F16_TILED tensor)
         stem, head, fc = ((dll.azsp_stem_tiled_f16, dll.azsp_head_tiled_f16, dll.azsp_fc_heads_f16) if f16 else
                           (dll.azsp_stem_tiled, dll.azsp_head_tiled, dll.azsp_fc_heads))
-        st = ctypes.c_void_p(torch.cuda.current_stream(feat.device).cuda_stream) if feat.is_cuda else None  # (host twin: CPU tensors)
-        B, C = rows, self.filters
-        S = board_size + 2 * (self.stem_pad - 1)  # planes of the tower (network.py:101-105: the Gomoku stem pads by 3)
+        st = _stream(feat)
+        B, C, S = rows, self.filters, _planes(board_size, self.stem_pad)
         a, m, o = self._tiled_buffers(B, S, C, feat.device, slot)
-        ck(stem(feat.data_ptr(), self.stem_wp.data_ptr(), self.stem_b32.data_ptr(), a.data_ptr(), B, board_size, C, self.stem_pad, 1, st), "azsp_stem_tiled")
+        _ck(stem(feat.data_ptr(), self.stem_wp.data_ptr(), self.stem_b32.data_ptr(), a.data_ptr(), B, board_size, C, self.stem_pad, 1, st), "azsp_stem_tiled")
         a = self._blocks_tiled(a, m, o, B, S, C, st)
         k1, k2 = self.fc_wp.shape[1], self.fc_w1.shape[1]  # head-plane rows padded to the k-steps of azsp_fc_heads (zero padding)
         pol, val, pri_buf, v_buf = self._head_buffers(B, k1, k2, feat.device, slot)
-        ck(head(a.data_ptr(), self.head_w32.data_ptr(), self.head_b32.data_ptr(), pol.data_ptr(), val.data_ptr(), B, S, C, self.npol, self.nval, k1, k2, st),
-           "azsp_head_tiled")
-        nt = ((self.num_actions + 31) // 32, (self.fc_width + 31) // 32)
-        fused_fc = self.use_fused_fc and nt in ((3, 2), (3, 4), (6, 2), (6, 4), (12, 8)) and (not f16 or nt == (3, 4))
-        if not fused_fc:
+        _ck(head(a.data_ptr(), self.head_w32.data_ptr(), self.head_b32.data_ptr(), pol.data_ptr(), val.data_ptr(), B, S, C, self.npol, self.nval, k1, k2, st),
+            "azsp_head_tiled")
+        nt = _fc_tiles(self.num_actions, self.fc_width)
+        if not (self.use_fused_fc and nt in FC_TILES and (not f16 or nt == _fc_tiles(*F16_HEADS))):
             return self._fc_heads(pol[:B, : self.npol * S * S], val[:B, : self.nval * S * S], priors_out, values_out)
         pri = priors_out if priors_out is not None else pri_buf
         v = values_out if values_out is not None else v_buf
-        ck(fc(pol.data_ptr(), val.data_ptr(), self.fc_wp.data_ptr(), self.fc_bp.data_ptr(), k1 // 16, self.fc_w1.data_ptr(), self.fc_b1.data_ptr(),
-              k2 // 16, self.fc_w2.data_ptr(), ctypes.c_float(self.fc_b2), pri.data_ptr(), v.data_ptr(), B, self.num_actions, self.fc_width, st),
-           "azsp_fc_heads")
+        _ck(fc(pol.data_ptr(), val.data_ptr(), self.fc_wp.data_ptr(), self.fc_bp.data_ptr(), k1 // 16, self.fc_w1.data_ptr(), self.fc_b1.data_ptr(),
+               k2 // 16, self.fc_w2.data_ptr(), ctypes.c_float(self.fc_b2), pri.data_ptr(), v.data_ptr(), B, self.num_actions, self.fc_width, st),
+            "azsp_fc_heads")
         return pri, v
 
     @torch.no_grad()
@@ -676,15 +678,12 @@ class InferenceNet(nn.Module):
         device: azsp_tile_layout), otherwise `forward`.  Used where leaf rows arrive as NCHW planes: evaluation games
         (core/evaluate.py DeviceEvaluator), drop-in eval_func wrappers."""
         B, _, n, _ = x.shape
-        if not (x.is_cuda and self.supports_tiled_features(n, x.device)):
+        if self._path(n, x.device)[0] != "tiled":
             return self.forward(x, priors_out, values_out)
-        import ctypes
-
         xb = torch.zeros((B, 32, n, n), dtype=self.pack_dtype, device=x.device).contiguous(memory_format=torch.channels_last)
         xb[:, : x.shape[1]] = x.to(self.pack_dtype)
         feat = torch.zeros(self.binding.dll.azsp_tiled_bytes(B, n, 32) // 2, dtype=self.pack_dtype, device=x.device)
-        st = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        self._ck(self.binding.dll.azsp_tile_layout(xb.data_ptr(), feat.data_ptr(), B, n, 32, 1, st), "azsp_tile_layout")
+        _ck(self.binding.dll.azsp_tile_layout(xb.data_ptr(), feat.data_ptr(), B, n, 32, 1, _stream(x)), "azsp_tile_layout")
         pri, v = self.forward_tiled(feat, B, n, priors_out, values_out, slot=3)
         return (pri, v) if priors_out is not None else (pri.clone(), v.clone())  # the slot's output buffers are reused by the next call
 
@@ -703,34 +702,28 @@ class InferenceNet(nn.Module):
     def _tower_tiled(self, x):
         """The whole residual tower on the tiled activation layout (include/azsp.h: azsp_tile_layout /
         azsp_conv3x3_tiled): the weight-stationary MFMA kernel, activations converted once on entry and once on exit."""
-        import ctypes
-
-        dll, ck = self.binding.dll, self._ck
-        st = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        dll, st = self.binding.dll, _stream(x)
         B, C, S = x.shape[0], x.shape[1], x.shape[2]
         a, m, o = self._tiled_buffers(B, S, C, x.device)
-        ck(dll.azsp_tile_layout(x.data_ptr(), a.data_ptr(), B, S, C, 1, st), "azsp_tile_layout")
+        _ck(dll.azsp_tile_layout(x.data_ptr(), a.data_ptr(), B, S, C, 1, st), "azsp_tile_layout")
         a = self._blocks_tiled(a, m, o, B, S, C, st)
-        ck(dll.azsp_tile_layout(a.data_ptr(), x.data_ptr(), B, S, C, 0, st), "azsp_tile_layout")
+        _ck(dll.azsp_tile_layout(a.data_ptr(), x.data_ptr(), B, S, C, 0, st), "azsp_tile_layout")
         return x
 
     def _tower_split(self, x, slot=3):
         """The whole residual tower of an fp32 network on the split layout (azsp_split_layout / azsp_conv3x3_split): activations are
         converted once on entry and once on exit; x is channels-last fp32 [B,C,S,S] and is overwritten with the tower's output.
         (The evaluator of shapes whose stem or heads have no split kernel: a library stem and heads around the hand-written tower.)"""
-        import ctypes
-
-        dll, ck = self.binding.dll, self._ck
-        st = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        dll, st = self.binding.dll, _stream(x)
         rr = self._range_ptr(x.device)
         B, C, S = x.shape[0], x.shape[1], x.shape[2]
         (a, m, o), _, _, _ = self._split_buffers(B, S, C, x.device, slot)
         self._split = (a, m, o, B)
         if self.act_shift:
             x.mul_(2.0 ** -self.act_shift)  # exact; the tower biases b_sp carry the same factor
-        ck(dll.azsp_split_layout(x.data_ptr(), a.data_ptr(), B, S, C, 1, rr, st), "azsp_split_layout")
+        _ck(dll.azsp_split_layout(x.data_ptr(), a.data_ptr(), B, S, C, 1, rr, st), "azsp_split_layout")
         a = self._blocks_split(a, m, o, B, S, C, st, rr)
-        ck(dll.azsp_split_layout(a.data_ptr(), x.data_ptr(), B, S, C, 0, rr, st), "azsp_split_layout")
+        _ck(dll.azsp_split_layout(a.data_ptr(), x.data_ptr(), B, S, C, 0, rr, st), "azsp_split_layout")
         if self.act_shift:
             x.mul_(2.0 ** self.act_shift)
         return x
@@ -738,13 +731,16 @@ class InferenceNet(nn.Module):
     @torch.no_grad()
     def forward(self, x, priors_out=None, values_out=None):
         """x: [B,17,N,N] any dtype -> (priors fp32 [B,A], values fp32 [B])."""
-        if x.is_cuda and self.supports_split_features(x.shape[2], x.device):
+        path = self._path(x.shape[2], x.device)[0]
+        if path == "split":
             return self.forward_split(x.float().contiguous(), priors_out, values_out)
         x = x.to(self.dtype).contiguous(memory_format=self.mf)
         x = self._epilogue(F.conv2d(x, self.w[0], None, padding=self.stem_pad), self.b[0])
-        if self._tiled_tower_ok(x):
+        # the hand-written towers take square channels-last activations of their own element type
+        tower_ok = x.shape[2] == x.shape[3] and x.is_contiguous(memory_format=torch.channels_last)
+        if tower_ok and path in ("tiled", "tiled_tower") and x.dtype == torch.bfloat16:
             x = self._tower_tiled(x)
-        elif self._split_tower_ok(x):
+        elif tower_ok and path == "split_tower" and x.dtype == torch.float32:
             x = self._tower_split(x, slot=0 if priors_out is not None else 3)
         else:
             for i in range(self.n_blocks):

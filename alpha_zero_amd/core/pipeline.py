@@ -184,7 +184,7 @@ class SelfPlayActor:
         if e.features_tiled:
             self.infer.forward_tiled(e.features, e.rows, e.N, e.priors, e.values)
         elif e.features_split:
-            if self.infer.split_fallback_reason or self.infer.stem_fallback_reason:  # the fp32-class kernels (or their stem) were given up for this network
+            if self.infer.split_fallback_reason:  # the fp32-class kernels were given up for this network
                 self.infer._forward_after_split_fallback(e.features, e.priors, e.values, (e.rows, e.N))
                 return
             if not self.infer.supports_split_features(e.N, self.device):  # (someone switched the split kernels off on the live InferenceNet)

@@ -660,3 +660,75 @@ def test_widen_for_kernels_only_when_it_pays():
     w2, note2 = widen_for_kernels(go128_19, 19, torch.bfloat16)
     assert w2.conv_block[0].out_channels == 256 and "128 -> 256" in note2           # 4x: still worth it
     assert widen_for_kernels(go128_19, 19, torch.float32) == (go128_19, "")          # no fp32-class kernels at 19x19
+
+
+_TILED = "hand-written: tiled stem / tower / head / FC kernels (libazsp)"
+_SPLIT = ("fp32 class, hand-written: split-precision stem / tower ({}hi + lo f16 pairs, three MFMA products, fp32 accumulation) / "
+          "fp32 heads (libazsp)")
+_SPLIT_TOWER = ("fp32 class: hand-written split-precision tower (azsp_conv3x3_split{}: hi + lo f16 pairs, three MFMA products, fp32 "
+                "accumulation) behind a library fp32 stem and heads")
+_PATHS = {"tiled": _TILED, "tiled_f16": _TILED + ", f16 activations and weights",
+          "tiled_tower": "hand-written tower (azsp_conv3x3_tiled) behind a library stem and heads",
+          "split": _SPLIT.format("azsp_conv3x3_split: "),
+          "split_fused": _SPLIT.format("azsp_resblock_split: one launch per ResNetBlock, intermediate activation in LDS; "),
+          "tower": _SPLIT_TOWER.format(""), "tower_spg": _SPLIT_TOWER.format(", wave-per-tile kernel k_conv3x3_spg")}
+# (dtype, filters, board, gomoku) -> evaluator on "cuda" with every switch on, then with one of _SWITCHES off; every shape / switch not
+# listed here (and every shape on "cpu" or without a binding) is the library path.  A switched-off kernel family is reported as the
+# library, which is what the forward then runs.
+_SWITCHES = ("use_fused_block", "use_split_heads", "use_split_tower", "use_tiled_tower", "use_fused_conv")
+_T = ("tiled",) * 4 + ("library",) * 2
+_TS = ("tower_spg",) * 3 + ("library", "tower_spg", "library")
+_EXPECTED_PATHS = {
+    (torch.bfloat16, 64, 9, False): _T, (torch.bfloat16, 128, 9, False): _T, (torch.bfloat16, 64, 13, True): _T,
+    (torch.bfloat16, 256, 19, False): _T, (torch.float16, 128, 9, False): ("tiled_f16",) * 4 + ("library",) * 2,
+    (torch.float32, 64, 9, False): ("split_fused", "split", "tower", "library", "split_fused", "library"),
+    (torch.float32, 64, 13, True): ("split_fused", "split", "tower", "library", "split_fused", "library"),
+    (torch.float32, 128, 9, False): ("split", "split", "tower", "library", "split", "library"),
+    (torch.float32, 64, 13, False): _TS, (torch.float32, 64, 19, False): _TS, (torch.float32, 128, 13, False): _TS,
+    (torch.float32, 128, 13, True): _TS, (torch.float32, 128, 19, False): _TS, (torch.float32, 256, 9, False): _TS,
+    (torch.float32, 256, 13, False): _TS, (torch.float32, 256, 13, True): _TS, (torch.float32, 256, 19, False): _TS,
+}
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16, torch.float32])
+@pytest.mark.parametrize("filters", [40, 64, 128, 256])
+@pytest.mark.parametrize("board,gomoku", [(9, False), (13, False), (19, False), (13, True)])
+def test_evaluator_path_decision_host_twin(dtype, filters, board, gomoku):
+    """The evaluator each network shape runs on (evaluator_path) and the two supports_* answers, for every kernel switch and for a
+    network whose fp32-class kernels were given up: only the device type is inspected, so no GPU is needed."""
+    import engine_util as eu
+
+    torch.manual_seed(0)
+    net = AlphaZeroNet((17, board, board), board * board + (0 if gomoku else 1), 1, filters, 128, gomoku=gomoku)
+    library = f"library convolutions + azsp_bias_act epilogue (no hand-written kernel for {filters} filters on {board}x{board}, {dtype})"
+    want = dict(zip(("",) + _SWITCHES, _EXPECTED_PATHS.get((dtype, filters, board, gomoku), ("library",) * 6)))
+    inf = InferenceNet(net, dtype=dtype, binding=eu.hosttwin_binding())
+    for switch, path in want.items():
+        if switch:
+            setattr(inf, switch, False)
+        for device in ("cuda", "cpu"):
+            p = path if device == "cuda" else "library"
+            got = (inf.evaluator_path(board, device), inf.supports_tiled_features(board, device), inf.supports_split_features(board, device))
+            assert got == (_PATHS.get(p, library), p in ("tiled", "tiled_f16"), p.startswith("split")), (switch, device, got)
+        if switch:
+            setattr(inf, switch, True)
+    if dtype == torch.float32:
+        inf.split_fallback_reason = "the reason"
+        fb = "library fp32 convolutions + azsp_bias_act epilogue (fp32-class kernels given up for this network: the reason)"
+        for device in ("cuda", "cpu"):
+            assert (inf.evaluator_path(board, device), inf.supports_split_features(board, device)) == (fb, False)
+    inf = InferenceNet(net, dtype=dtype)  # no binding: the library path everywhere
+    assert (inf.evaluator_path(board, "cuda"), inf.supports_tiled_features(board, "cuda"), inf.supports_split_features(board, "cuda")) == (
+        library, False, False)
+
+
+@pytest.mark.parametrize("dtype,path", [(torch.bfloat16, "tiled_tower"), (torch.float16, "library"), (torch.float32, "tower")])
+def test_evaluator_path_behind_a_library_stem_host_twin(dtype, path):
+    """A stem with more input planes than the hand-written stem kernels take (32): the tower alone runs on them."""
+    import engine_util as eu
+
+    torch.manual_seed(0)
+    inf = InferenceNet(AlphaZeroNet((40, 9, 9), 82, 1, 128, 128), dtype=dtype, binding=eu.hosttwin_binding())
+    library = f"library convolutions + azsp_bias_act epilogue (no hand-written kernel for 128 filters on 9x9, {dtype})"
+    assert (inf.evaluator_path(9, "cuda"), inf.supports_tiled_features(9, "cuda"), inf.supports_split_features(9, "cuda")) == (
+        _PATHS.get(path, library), False, False)
