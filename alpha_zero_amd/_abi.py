@@ -24,7 +24,7 @@ class AzspConfig(C.Structure):
         "reuse_tree", "warm_up_steps", "has_resign", "check_resign_after_steps", "force_resign_disabled", "inject_random",
         "inject_moves", "stop_after_move", "max_plies", "stop_at_game_end", "feature_dtype", "log_moves", "log_capacity",
         "max_steps", "num_to_win", "training_steps", "rank", "device")] + [
-        ("c_puct_base", C.c_float), ("c_puct_init", C.c_float), ("disable_resign_ratio", C.c_float), ("reserved0", C.c_float),
+        ("c_puct_base", C.c_float), ("c_puct_init", C.c_float), ("disable_resign_ratio", C.c_float), ("num_stack", C.c_int32),
         ("dirichlet_eps", C.c_double), ("dirichlet_alpha", C.c_double), ("resign_threshold", C.c_double), ("komi", C.c_double),
         ("seed", C.c_uint64)]
 

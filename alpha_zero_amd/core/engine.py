@@ -34,6 +34,7 @@ class EngineConfig:
     komi: float = 7.5
     max_steps: int = 0
     num_to_win: int = 5
+    num_stack: int = 8               # history boards per observation (base.py:228-266): 2 * num_stack + 1 planes, 1..8
     resign_threshold: float = -1.0
     check_resign_after_steps: int = 40
     disable_resign_ratio: float = 0.1
@@ -55,6 +56,16 @@ class EngineConfig:
     device_index: int = 0
 
 
+MAX_NUM_STACK = 8  # the engine's history ring holds 8 boards (include/azsp.h AzspConfig.num_stack)
+
+
+def check_num_stack(num_stack):
+    """num_stack (history boards per observation) must be an integer in 1..MAX_NUM_STACK; raises ValueError naming the limit."""
+    if isinstance(num_stack, bool) or not isinstance(num_stack, (int, np.integer)) or not 1 <= int(num_stack) <= MAX_NUM_STACK:
+        raise ValueError(f"num_stack must be an integer in 1..{MAX_NUM_STACK} (the engine keeps {MAX_NUM_STACK} history boards), got {num_stack!r}")
+    return int(num_stack)
+
+
 def pbc_tables(c_puct_base, c_puct_init, n):
     """pb_c(N) as the reference evaluates it (mcts_v2.py:101): N is an np.float32 for interior nodes and
     re-used roots, a Python float for a freshly created root; sqrt(N) is a Python double that NumPy
@@ -71,6 +82,7 @@ class Engine:
     def __init__(self, binding: Binding, cfg: EngineConfig, device="cuda"):
         self.b, self.cfg, self.device = binding, cfg, torch.device(device)
         self.on_launch = None
+        check_num_stack(cfg.num_stack)
         c = AzspConfig()
         c.game = _abi.GAME_GO if cfg.game == "go" else _abi.GAME_GOMOKU
         c.board_size, c.num_games, c.num_parallel, c.num_simulations = cfg.board_size, cfg.num_games, cfg.num_parallel, cfg.num_simulations
@@ -85,7 +97,7 @@ class Engine:
         c.device = cfg.device_index
         c.c_puct_base, c.c_puct_init, c.disable_resign_ratio = cfg.c_puct_base, cfg.c_puct_init, cfg.disable_resign_ratio
         c.dirichlet_eps, c.dirichlet_alpha, c.resign_threshold, c.komi = cfg.dirichlet_eps, cfg.dirichlet_alpha, cfg.resign_threshold, cfg.komi
-        c.seed = cfg.seed
+        c.seed, c.num_stack = cfg.seed, cfg.num_stack
         self.h = C.c_void_p()
         self.b.check(self.b.dll.azsp_create(C.byref(c), C.byref(self.h)), None, "azsp_create")
         g = AzspGeometry()
@@ -93,6 +105,7 @@ class Engine:
         self.geo = g
         self.A, self.NP, self.N, self.G, self.P = g.num_actions, g.num_points, cfg.board_size, cfg.num_games, cfg.num_parallel
         self.rows = g.batch_rows
+        self.planes = g.planes  # 2 * num_stack + 1 observation planes per row
         t_np, t_py, sq = pbc_tables(cfg.c_puct_base, cfg.c_puct_init, g.table_len)
         self._ck(self.b.dll.azsp_set_tables(self.h, t_np.ctypes.data, t_py.ctypes.data, sq.ctypes.data, g.table_len), "azsp_set_tables")
         # evaluator-facing tensors (caller-visible; the engine reads / writes them in place)
@@ -104,7 +117,7 @@ class Engine:
             n = self.b.dll.azsp_tiled_bytes(self.rows, self.N, 32) // 2
             self.features = torch.zeros((n,), dtype=torch.float16 if cfg.feature_dtype == _abi.FEAT_F16_TILED else torch.bfloat16, device=self.device)
         else:
-            self.features = torch.zeros((self.rows, 17, self.N, self.N), dtype=_FEAT_TORCH[cfg.feature_dtype], device=self.device)
+            self.features = torch.zeros((self.rows, self.planes, self.N, self.N), dtype=_FEAT_TORCH[cfg.feature_dtype], device=self.device)
         self.valid = torch.zeros((self.rows,), dtype=torch.uint8, device=self.device)
         self.priors = torch.zeros((self.rows, self.A), dtype=torch.float32, device=self.device)
         self.values = torch.zeros((self.rows,), dtype=torch.float32, device=self.device)
@@ -151,7 +164,7 @@ class Engine:
 
     def env_step(self, actions=None, want_obs=False):
         """Standalone env kernels.  actions int[G] (None = export only; -2 no-op, -1 resign).
-        Returns dict(board int8[G,N,N], legal int8[G,A], scalars int32[G,12], obs int8[G,17,N,N] | None) on the host."""
+        Returns dict(board int8[G,N,N], legal int8[G,A], scalars int32[G,12], obs int8[G,2K+1,N,N] | None) on the host."""
         dev = self.device
         if actions is None:
             ap = None
@@ -161,15 +174,22 @@ class Engine:
         board = torch.empty((self.G, self.N, self.N), dtype=torch.int8, device=dev)
         legal = torch.empty((self.G, self.A), dtype=torch.int8, device=dev)
         scal = torch.empty((self.G, 12), dtype=torch.int32, device=dev)
-        obs = torch.empty((self.G, 17, self.N, self.N), dtype=torch.int8, device=dev) if want_obs else None
+        obs = torch.empty((self.G, self.planes, self.N, self.N), dtype=torch.int8, device=dev) if want_obs else None
         self._ck(self.b.dll.azsp_env_step(self.h, ap, board.data_ptr(), legal.data_ptr(), scal.data_ptr(),
                                           obs.data_ptr() if want_obs else None, self._stream()), "azsp_env_step")
         return dict(board=board.cpu().numpy(), legal=legal.cpu().numpy(), scalars=scal.cpu().numpy(),
                     obs=obs.cpu().numpy() if want_obs else None)
 
     def set_state(self, slot, board, hist, to_play, steps, ko=-1, last_was_pass=False, caps=(0, 0)):
+        """hist: the newest-first history boards, 1..8 of them (an env with num_stack K keeps K); a shorter history is padded with
+        empty boards to the engine's 8 rows, which an observation of K planes pairs never reads past row K - 1."""
         b = np.ascontiguousarray(board, dtype=np.int8).reshape(-1)
-        h = np.ascontiguousarray(hist, dtype=np.int8).reshape(8, -1)
+        h = np.asarray(hist, dtype=np.int8).reshape(-1, b.size)
+        if not 1 <= h.shape[0] <= 8:
+            raise ValueError(f"set_state takes 1..8 history boards, got {h.shape[0]}")
+        if h.shape[0] < 8:
+            h = np.concatenate([h, np.zeros((8 - h.shape[0], b.size), dtype=np.int8)])
+        h = np.ascontiguousarray(h)
         self._ck(self.b.dll.azsp_set_state(self.h, slot, b.ctypes.data, h.ctypes.data, int(to_play), int(steps), int(ko),
                                            int(bool(last_was_pass)), int(caps[0]), int(caps[1]), self._stream()), "azsp_set_state")
 
@@ -206,14 +226,14 @@ class Engine:
     def dropin_step(self, priors=None, values=None, feature_rows=None):
         """One iteration of uct_search's simulation loop in ONE host round trip (azsp_dropin_step): upload eval_func's `priors`
         float32[rows, A] / `values` float32[rows] for the previous leaves (None on the first call of a search), expand / backup, select
-        the next leaves, and return (status int32[G, 8], q float64[G, 2], valid bool[rows], obs [feature_rows, 17, N, N] of the engine's
-        feature dtype).  Feature dtypes with a plain [rows, 17, N, N] tensor only (AZSP_FEAT_I8 / F32)."""
+        the next leaves, and return (status int32[G, 8], q float64[G, 2], valid bool[rows], obs [feature_rows, 2K+1, N, N] of the engine's
+        feature dtype).  Feature dtypes with a plain [rows, 2K+1, N, N] tensor only (AZSP_FEAT_I8 / F32)."""
         assert not (self.features_tiled or self.features_split)
         nrow = self.rows if feature_rows is None else int(feature_rows)
         if getattr(self, "_dropin_bufs", None) is None:
             np_dt = {torch.int8: np.int8, torch.float32: np.float32}[self.features.dtype]
             self._dropin_bufs = (np.zeros((self.G, 8), dtype=np.int32), np.zeros((self.G, 2), dtype=np.float64), np.zeros(self.rows, dtype=np.uint8),
-                                 np.zeros((self.rows, 17, self.N, self.N), dtype=np_dt))
+                                 np.zeros((self.rows, self.planes, self.N, self.N), dtype=np_dt))
         st, q, valid, obs = self._dropin_bufs
         pp = vp = None
         if priors is not None:
@@ -243,7 +263,7 @@ class Engine:
 
     # -- samples ----------------------------------------------------------------------------------------
     def harvest(self, sample_capacity=None, max_games=None, with_moves=False):
-        """Returns (states int8[n,17,N,N], pi float32[n,A], z float32[n], games int32[k,16]) -- device tensors + host meta;
+        """Returns (states int8[n,2K+1,N,N], pi float32[n,A], z float32[n], games int32[k,16]) -- device tensors + host meta;
         with_moves=True appends moves int16[n] (the move played from every sample's position, -1 = resigned).
         The per-game extras of the same call (azsp_harvest_extra) are left in `self.last_extra` int32[k,4].
         ALIASING: the device tensors are views of buffers this engine re-uses -- the NEXT harvest() overwrites them in place.
@@ -251,7 +271,7 @@ class Engine:
         cap = sample_capacity or max(4 * self.G, 2 * self.geo.stage_capacity)
         mg = max_games or 2 * self.G
         if self._harvest_bufs is None or self._harvest_bufs[0].shape[0] < cap:
-            self._harvest_bufs = (torch.empty((cap, 17, self.N, self.N), dtype=torch.int8, device=self.device),
+            self._harvest_bufs = (torch.empty((cap, self.planes, self.N, self.N), dtype=torch.int8, device=self.device),
                                   torch.empty((cap, self.A), dtype=torch.float32, device=self.device),
                                   torch.empty((cap,), dtype=torch.float32, device=self.device),
                                   torch.empty((cap,), dtype=torch.int16, device=self.device))

@@ -99,7 +99,7 @@ def eval_against_prev_ckpt(env, black_player, white_player, black_elo, white_elo
 
 class DeviceEvaluator:
     """An evaluator for play_eval_games_parallel whose leaf rows never leave the device: wraps an InferenceNet (core/network.py).
-    `device_eval(x)` takes the engine's int8 observation rows [B,17,N,N] on the device and returns (priors f32[B,A], values f32[B])
+    `device_eval(x)` takes the engine's int8 observation rows [B,2K+1,N,N] on the device and returns (priors f32[B,A], values f32[B])
     on the device; calling the object with (state, batched) numpy arrays honours the reference's eval_func contract
     (pipeline.py:91-123), so the same object also serves the drop-in searches."""
 
@@ -111,6 +111,11 @@ class DeviceEvaluator:
         self.use_graph = use_graph
         self._calls = 0
         self._graphs = {}
+
+    @property
+    def in_channels(self):
+        """Observation planes the wrapped network takes (2 * num_stack + 1); the searches check it against the env."""
+        return getattr(self.inf, "in_channels", None)
 
     def _forward(self, x, priors_out=None, values_out=None):
         if hasattr(self.inf, "forward_planes"):
@@ -179,10 +184,10 @@ class DeviceEvaluator:
 
 
 def play_eval_games_parallel(game, board_size, players, num_simulations, num_parallel, c_puct_base, c_puct_init, komi=7.5, num_to_win=5,
-                             binding=None, device="cuda", max_rounds=1 << 20, openings=None):
+                             binding=None, device="cuda", max_rounds=1 << 20, openings=None, num_stack=8):
     """SURVEY 8f-2 "many in parallel": G evaluation games of pipeline.py:815-867 advance in lock-step on ONE engine.
 
-    players: one (black_eval, white_eval) pair per game; eval(states int8[B,17,N,N], True) -> (list of pi, list of v) with the
+    players: one (black_eval, white_eval) pair per game; eval(states int8[B,2K+1,N,N], True) -> (list of pi, list of v) with the
     reference's eval_func contract (pipeline.py:91-123).  Every game is what eval_against_prev_ckpt plays: no root noise, arg-max
     moves, a fresh tree for every move (`root_node=None`, pipeline.py:836), the searching player's own evaluator for all leaves of
     its search.  The whole game runs inside the engine (search, move, env step, termination, scoring).  Per round the leaf rows of all
@@ -190,7 +195,8 @@ def play_eval_games_parallel(game, board_size, players, num_simulations, num_par
     receive and return device tensors -- their rows are gathered / scattered by index on the device and never pass through the host
     (only the G side-to-move flags do).  openings: optional list of G move lists played (env.step) before the first search, e.g.
     random openings for a match between two evaluators.  Returns per game dict(moves, game_length, game_result, num_passes, winner)
-    -- the same games, move for move, as G sequential calls (tests/arena_checks.py); `moves` includes the opening moves."""
+    -- the same games, move for move, as G sequential calls (tests/arena_checks.py); `moves` includes the opening moves.
+    num_stack: history boards per observation (K, 1..8); an evaluator that knows its network's input planes (`in_channels`) must take 2K+1."""
     import torch
 
     from .. import _abi, _lib
@@ -199,9 +205,15 @@ def play_eval_games_parallel(game, board_size, players, num_simulations, num_par
 
     binding = binding or _lib.load(require_gpu=True)
     G = len(players)
+    for pair in players:
+        for ev in pair:
+            cin = getattr(ev, "in_channels", None)
+            if cin is not None and cin != 2 * num_stack + 1:
+                raise ValueError(f"an evaluator's network takes {cin} input planes, but num_stack = {num_stack} observations have {2 * num_stack + 1}")
     cfg = EngineConfig(game=game, board_size=board_size, num_games=G, num_parallel=num_parallel, num_simulations=num_simulations,
                        c_puct_base=c_puct_base, c_puct_init=c_puct_init, root_noise=False, deterministic=True, reuse_tree=False, warm_up_steps=-1,
-                       komi=komi, num_to_win=num_to_win, resign_threshold=-1.0, stop_at_game_end=True, feature_dtype=_abi.FEAT_I8)
+                       komi=komi, num_to_win=num_to_win, resign_threshold=-1.0, stop_at_game_end=True, feature_dtype=_abi.FEAT_I8,
+                       num_stack=num_stack)
     eng = Engine(binding, cfg, device=device)
     try:
         eng.reset_games()
@@ -238,7 +250,7 @@ def play_eval_games_parallel(game, board_size, players, num_simulations, num_par
             host_needed = not all(on_device[k] for k in np.unique(ev_of_game))
             if host_needed:
                 valid = valid_dev.cpu().numpy()
-                feats = eng.features.cpu().numpy().reshape(G, P, 17, board_size, board_size)
+                feats = eng.features.cpu().numpy().reshape(G, P, eng.planes, board_size, board_size)
                 pri = np.zeros((G, P, A), dtype=np.float32)
                 val = np.zeros((G, P), dtype=np.float32)
             for k, ev in enumerate(evs):

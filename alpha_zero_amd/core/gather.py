@@ -43,7 +43,7 @@ def unpack_samples(rows, state_shape, A):
 
 
 def gather_samples(states, pi, z, games, dst=0, group=None):
-    """states int8[n,17,N,N], pi f32[n,A], z f32[n] (device tensors of this rank), games int32[k,16] (numpy).
+    """states int8[n,C,N,N] (C = 2 * num_stack + 1), pi f32[n,A], z f32[n] (device tensors of this rank), games int32[k,16] (numpy).
     Returns on `dst` the concatenation over ranks (rank order) with game `start` offsets rebased and column 15
     (slot) made global as rank*2^20 + slot; on other ranks returns None.
 

@@ -53,14 +53,15 @@ class _Searcher:
         cfg = EngineConfig(game=game, board_size=env.board_size, num_games=1, num_parallel=P, num_simulations=sims, c_puct_base=base,
                            c_puct_init=init, root_noise=root_noise, komi=getattr(env, "komi", 7.5),
                            max_steps=getattr(env, "max_steps", 0) or 0, num_to_win=getattr(env, "num_to_win", 5),
-                           stop_after_move=True, feature_dtype=_abi.FEAT_I8, log_moves=False)
+                           num_stack=getattr(env, "num_stack", 8), stop_after_move=True, feature_dtype=_abi.FEAT_I8, log_moves=False)
         self.eng = Engine(binding, cfg, device=device)
         self.P = P
 
 
 def _get_searcher(env, sims, P, base, init, root_noise):
     key = ("go" if env.has_pass_move else "gomoku", env.board_size, sims, P, float(base), float(init), bool(root_noise),
-           getattr(env, "komi", None), getattr(env, "max_steps", None), getattr(env, "num_to_win", None), id(getattr(env, "_binding", None)))
+           getattr(env, "komi", None), getattr(env, "max_steps", None), getattr(env, "num_to_win", None), getattr(env, "num_stack", 8),
+           id(getattr(env, "_binding", None)))
     idle = _POOL.get(key)
     if idle:
         return idle.pop()
@@ -68,6 +69,7 @@ def _get_searcher(env, sims, P, base, init, root_noise):
 
 
 def _load_position(s, env):
+    # K = env.num_stack rows, newest first (a reference env's deque): Engine.set_state pads them to the engine's 8
     hist = np.stack([np.asarray(b, dtype=np.int8) for b in env.board_deltas])
     ko, caps = getattr(env, "ko", -1), getattr(env, "_caps", (0, 0))
     pos = getattr(env, "position", None)  # a reference GoEnv keeps these on its Position
@@ -142,6 +144,11 @@ def _search(env, eval_func, root_node, c_puct_base, c_puct_init, num_simulations
         raise ValueError(f"Expect `num_simulations` to a positive integer, got {num_simulations}")
     if env.is_game_over():
         raise RuntimeError("Game is over.")
+    planes = 2 * getattr(env, "num_stack", 8) + 1
+    cin = getattr(eval_func, "in_channels", None)  # known for evaluators that wrap a network (core/evaluate.py DeviceEvaluator)
+    if cin is not None and cin != planes:
+        raise ValueError(f"the evaluator's network takes {cin} input planes, but the env's observations (num_stack = "
+                         f"{getattr(env, 'num_stack', 8)}) have {planes}")
     if root_node is not None:
         if not isinstance(root_node, Node) or not root_node._alive:
             raise ValueError("`root_node` must be the handle returned by the previous search (or None)")

@@ -200,6 +200,7 @@ class InferenceNet(nn.Module):
         self.use_fused_fc = True
         self.mf = torch.channels_last if channels_last else torch.contiguous_format
         self.stem_pad = net.conv_block[0].padding[0]
+        self.in_channels = net.conv_block[0].in_channels  # 2 * num_stack + 1 observation planes (17 at the reference's default)
         self.filters = net.conv_block[0].out_channels
         self.n_blocks = len(net.res_blocks)
         # fp32-class path: every activation is carried as v * 2^-act_shift (an exact rescaling of a ReLU + skip tower, see set_act_shift)

@@ -48,6 +48,14 @@ from .engine import Engine, EngineConfig  # noqa: E402
 from .network import AlphaZeroNet, InferenceNet, widen_for_kernels  # noqa: E402
 from .replay import Transition  # noqa: E402
 
+def check_input_channels(network, num_stack):
+    """The engine's observations have 2 * num_stack + 1 planes (base.py:228-266); a network whose stem takes another count is refused
+    here instead of inside a kernel."""
+    cin = network.conv_block[0].in_channels
+    if cin != 2 * num_stack + 1:
+        raise ValueError(f"the network's stem takes {cin} input planes, but num_stack = {num_stack} observations have {2 * num_stack + 1}")
+
+
 _FEAT_OF = {torch.float32: _abi.FEAT_F32, torch.bfloat16: _abi.FEAT_BF16, torch.float16: _abi.FEAT_F16}
 
 
@@ -95,7 +103,7 @@ class SelfPlayActor:
                  c_puct_base=19652.0, c_puct_init=1.25, warm_up_steps=16, check_resign_after_steps=40, disable_resign_ratio=0.1,
                  resign_threshold=-1.0, komi=7.5, num_to_win=5, seed=1, rank=0, device="cuda", net_dtype=torch.float32,
                  use_graph=True, training_steps=0, binding=None, root_noise=True, deterministic=False, tiled_features=None, engine_kw=None,
-                 use_split_evaluator=True, auto_widen=None):
+                 use_split_evaluator=True, auto_widen=None, num_stack=8):
         """net_dtype: precision class of the leaf evaluator.  The default is the REFERENCE'S: fp32 (pipeline.py:91-123 evaluates in fp32,
         no autocast anywhere) -- on the hand-written split-precision kernels (hi + lo f16 pairs, three MFMA products, fp32 accumulation:
         include/azsp.h azsp_conv3x3_split) for 9x9 x {128, 64} and 13x13 Gomoku x 64 networks, on library fp32 convolutions (announced
@@ -106,8 +114,14 @@ class SelfPlayActor:
         kernels exist (comparison runs: bench.py's fp32_library_companion, tests/test_precision_parity.py).
         auto_widen: networks of a width without hand-written kernels run as a function-preserving widened copy (network.widen_for_kernels).
         None = on the GPU whenever the widened network actually reaches hand-written kernels (not for library comparison runs, not when
-        the caller disabled the kernels' feature layouts); True / False force it."""
+        the caller disabled the kernels' feature layouts); True / False force it.
+        num_stack: history boards per observation (the env's num_stack, 1..8): the engine writes 2 * num_stack + 1 planes, which must be
+        the network's input channels."""
         from .. import _lib
+        from .engine import check_num_stack
+
+        self.num_stack = check_num_stack(num_stack)
+        check_input_channels(network, self.num_stack)
 
         self.binding = binding or _lib.load(require_gpu=True)
         self.device = torch.device(device)
@@ -139,7 +153,7 @@ class SelfPlayActor:
             disable_resign_ratio=disable_resign_ratio, root_noise=root_noise, deterministic=deterministic,
             feature_dtype=((_abi.FEAT_F16_TILED if net_dtype == torch.float16 else _abi.FEAT_BF16_TILED) if self.tiled_features
                            else _abi.FEAT_F16_SPLIT if self.split_features else _FEAT_OF[net_dtype]),
-            training_steps=training_steps, seed=seed, rank=rank,
+            training_steps=training_steps, seed=seed, rank=rank, num_stack=self.num_stack,
             device_index=self.device.index or 0)
         for k, v in (engine_kw or {}).items():  # further EngineConfig fields (move logs, max_plies, ...: tests and diagnostics)
             if not hasattr(self.cfg, k):
@@ -162,6 +176,7 @@ class SelfPlayActor:
     # -- weights ---------------------------------------------------------------------------------------
     def set_network(self, network: AlphaZeroNet, training_steps=0):
         """Checkpoint hot-swap (pipeline.py:232-239): new weights take effect at the next round."""
+        check_input_channels(network, self.num_stack)
         if self.auto_widen:
             network, _ = widen_for_kernels(network, self.board_size, self.net_dtype)
         self.infer = InferenceNet(network, dtype=self.net_dtype, binding=self.binding if self.device.type == "cuda" else None).to(self.device)
@@ -423,7 +438,8 @@ def run_selfplay_actor_loop(seed, rank, network, device, data_queue, env, num_si
                           num_parallel=num_parallel, c_puct_base=c_puct_base, c_puct_init=c_puct_init, warm_up_steps=warm_up_steps,
                           check_resign_after_steps=check_resign_after_steps, disable_resign_ratio=disable_resign_ratio,
                           resign_threshold=thr, komi=getattr(env, "komi", 7.5), num_to_win=getattr(env, "num_to_win", 5),
-                          seed=seed, rank=rank, device=device, net_dtype=net_dtype, training_steps=training_steps, binding=binding)
+                          seed=seed, rank=rank, device=device, net_dtype=net_dtype, training_steps=training_steps, binding=binding,
+                          num_stack=getattr(env, "num_stack", 8))
     actor.drop_clamped_games = True  # the learner never sees a game that ran on a clamping evaluator (the reference's fp32 has no range)
     writer = None
     if logs_dir:  # per-actor statistics file with the reference's columns (pipeline.py:196, :268-271; logs/go/9x9/actor0.csv)

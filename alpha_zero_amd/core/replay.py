@@ -5,7 +5,7 @@ import numpy as np
 
 
 class Transition(NamedTuple):
-    state: Optional[np.ndarray]    # int8[17, N, N] observation before the move, mover's perspective
+    state: Optional[np.ndarray]    # int8[2K+1, N, N] observation before the move, mover's perspective (K = num_stack; 17 planes at 8)
     pi_prob: Optional[np.ndarray]  # search policy over all A actions
     value: Optional[float]         # z: +reward for the eventual last player's samples, -reward for the other's
 

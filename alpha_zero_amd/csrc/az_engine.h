@@ -46,6 +46,7 @@ struct AzCfg {
     int has_resign, check_resign_after, force_resign_disabled;  // force: -1 draw per game, 0/1 fixed
     int inject, inj_moves, stop_after_move, max_plies, stop_at_game_end;
     int feat_dtype, tab_len, log_moves, log_cap, stage_cap, training_steps;
+    int K;  // num_stack: history boards per observation (1..8), 2K + 1 planes
     float one_minus_eps_f32, disable_resign_ratio;
     double eps, alpha, resign_threshold;
     RuleCfg rc;
@@ -633,8 +634,22 @@ template <class Wv, int N, int GAME> struct Engine {
         });
         Wv::sync();
     }
+    // History depth K = c.K < 8 (num_stack): the observation is [X_t, Y_t, ..., X_t-K+1, Y_t-K+1, C] (base.py:228-259), 2K + 1 planes.
+    // gather_planes always assembles the 16 planes of K = 8; this rewrites planes 2K.. in LDS -- plane 2K becomes the colour plane (all
+    // ones when black is to move), the rest zero -- so that the emitters below read the K-deep observation from the same 16 plane rows.
+    // Kept out of the emitters: at K = 8 nothing here runs and the emitters' code is the one of the 17-plane engine.
+    AZ_HD void stack_planes(int me) {
+        if (c.K == 8) return;
+        const int KK = 2 * c.K;
+        const u64 colour = me == 0 ? ~0ull : 0ull;
+        Wv::lanes([&](int lane) {
+            for (int t = KK * W + lane; t < 16 * W; t += AZ_WAVE) sc.planes[t / W][t % W] = t / W == KK ? colour : 0ull;
+        });
+        Wv::sync();
+    }
+    // plain [2K+1][N][N] planes (after stack_planes): plane 16 -- the colour at K = 8 -- is never reached at K < 8
     template <class T> AZ_HD void emit_planes(T* out, T one, int me) {
-        const int total = 17 * NP;
+        const int total = (2 * c.K + 1) * NP;
         const bool black = me == 0;
         Wv::lanes([&](int lane) {
             for (int e = lane; e < total; e += AZ_WAVE) {
@@ -645,8 +660,10 @@ template <class Wv, int N, int GAME> struct Engine {
         });
     }
     // The evaluator's tiled input layout (include/azsp.h azsp_stem_tiled): [tile = T rows][4 chunks][T NP positions][8] bf16 (or f16) with
-    // T = max(1, 256 / NP) boards per tile (3 at 9x9), the 17 planes zero-padded to 32 channels.  Chunks 0..1 = the 16 stone planes, chunk 2 = colour plane + 7 zeros; chunk 3 and
-    // the padding are never written (the tensor is zero-initialised by its owner).
+    // T = max(1, 256 / NP) boards per tile (3 at 9x9), the 2K + 1 planes (K = num_stack) zero-padded to 32 channels.  At K = 8: chunks 0..1 =
+    // the 16 stone planes, chunk 2 = colour plane + 7 zeros; chunk 3 and the padding are never written (the tensor is zero-initialised by
+    // its owner).  At K < 8 the same stores write the planes stack_planes left in LDS (colour in channel 2K, zeros above it) and chunk 2
+    // gets zeros, so channels 2K + 1..31 are zero.
     // AZ_FEAT_F16_SPLIT = the input of the fp32-class evaluator's stem (include/azsp.h azsp_stem_split): the split layout
     // [row][plane: hi, lo][4 chunks][NP positions][8] f16 -- the same chunk strips with ONE board per tile and a second (lo) plane that is
     // never written: observation planes are 0 / 1, exactly representable in f16, so their lo halves are zero (the owner zero-initialises).
@@ -654,7 +671,7 @@ template <class Wv, int N, int GAME> struct Engine {
         const size_t r = (size_t)g * c.P + slot, tile = r / TBF;
         const int sub = (int)(r - tile * TBF);
         uint16_t* base = (uint16_t*)feat + tile * (size_t)(PLANES * 4 * TBF * NP * 8) + (size_t)sub * NP * 8;
-        const u32 black = me == 0 ? one : 0u;
+        const u32 black = (me == 0 && c.K == 8) ? one : 0u;  // channel 16: the colour plane at K = 8 only
         // One lane per POSITION (81 positions: lanes 0-63, then 0-16): the 16 plane words of its 64-position group are
         // wave-uniform LDS reads (broadcast), a stone is one bit-field extract, two planes make one dword (bf16 1.0 = 0x3F80) with two
         // multiply-adds, a chunk is one 16-byte store.  (The first version walked (chunk, position) pairs with 8 per-lane 64-bit
@@ -688,6 +705,7 @@ template <class Wv, int N, int GAME> struct Engine {
         });
     }
     AZ_HD void write_features(void* feat, int slot, int me) {
+        stack_planes(me);
         if (c.feat_dtype == AZ_FEAT_BF16_TILED || c.feat_dtype == AZ_FEAT_F16_TILED) {
             constexpr int TBF = (256 / NP) > 0 ? 256 / NP : 1;
             emit_tiled_t<TBF, 1>(feat, slot, me, c.feat_dtype == AZ_FEAT_F16_TILED ? 0x3C00u : 0x3F80u);  // 1.0 in f16 / bf16
@@ -697,7 +715,7 @@ template <class Wv, int N, int GAME> struct Engine {
             emit_tiled_t<1, 2>(feat, slot, me, 0x3C00u);
             return;
         }
-        const size_t row = ((size_t)g * c.P + slot) * (size_t)(17 * NP);
+        const size_t row = ((size_t)g * c.P + slot) * (size_t)((2 * c.K + 1) * NP);
         switch (c.feat_dtype) {
             case AZ_FEAT_I8: emit_planes<int8_t>((int8_t*)feat + row, (int8_t)1, me); break;
             case AZ_FEAT_F32: emit_planes<u32>((u32*)feat + row, 0x3F800000u, me); break;

@@ -255,7 +255,8 @@ struct OpEnvStep {
         }
         if (obs) {
             e.gather_planes(-1, -1, s.to_play);
-            int8_t* out = obs + (size_t)e.g * 17 * NP;
+            e.stack_planes(s.to_play);
+            int8_t* out = obs + (size_t)e.g * (2 * e.c.K + 1) * NP;
             e.template emit_planes<int8_t>(out, (int8_t)1, s.to_play);
         }
         E::Wave::sync();
@@ -327,12 +328,13 @@ struct OpHarvest {
                 const u64* pl = e.m.stg_planes + idx * 16 * W;
                 const float* spi = e.m.stg_pi + idx * A;
                 const int black = e.m.stg_meta[idx];
-                int8_t* so = states + (size_t)(start + k) * 17 * NP;
+                const int KK = 2 * e.c.K;  // stone planes of the observation; the colour plane follows them
+                int8_t* so = states + (size_t)(start + k) * (KK + 1) * NP;
                 float* po = pi + (size_t)(start + k) * A;
                 E::Wave::lanes([&](int lane) {
-                    for (int x = lane; x < 17 * NP; x += AZ_WAVE) {
+                    for (int x = lane; x < (KK + 1) * NP; x += AZ_WAVE) {
                         const int plane = x / NP, p = x - plane * NP;
-                        so[x] = plane < 16 ? (int8_t)((pl[plane * W + (p >> 6)] >> (p & 63)) & 1ull) : (int8_t)black;
+                        so[x] = plane < KK ? (int8_t)((pl[plane * W + (p >> 6)] >> (p & 63)) & 1ull) : (int8_t)black;
                     }
                     for (int x = lane; x < A; x += AZ_WAVE) po[x] = spi[x];
                 });
@@ -702,8 +704,8 @@ int azsp_create(const AzspConfig* p, void** out) {
     h->pub = *p;
     h->bytes = 0;
     if (az_geometry_of(p->game, p->board_size, &h->A, &h->AP, &h->W, &h->REC, &h->GREC) != 0 || p->num_games < 1 ||
-        p->num_parallel < 1 || p->num_parallel > AZ_MAXP || p->num_simulations < 1) {
-        delete h;
+        p->num_parallel < 1 || p->num_parallel > AZ_MAXP || p->num_simulations < 1 || p->num_stack < 0 || p->num_stack > 8) {
+        delete h;  // num_stack: at most the 8 boards of the history ring (GameRec::hist)
         return AZSP_EINVAL;
     }
     if (azb::set_device(p->device) != 0) {
@@ -738,6 +740,7 @@ int azsp_create(const AzspConfig* p, void** out) {
     c.max_plies = p->max_plies;
     c.stop_at_game_end = p->stop_at_game_end;
     c.feat_dtype = p->feature_dtype;
+    c.K = p->num_stack > 0 ? p->num_stack : 8;
     c.log_moves = p->log_moves;
     c.log_cap = (p->log_moves && p->log_capacity > 0) ? p->log_capacity : 1;
     c.tab_len = c.budget + 3 * c.P + 16;
@@ -821,7 +824,7 @@ int azsp_geometry(void* e, AzspGeometry* g) {
     AzHandle* h = (AzHandle*)e;
     g->num_actions = h->A;
     g->num_points = h->NP;
-    g->planes = 17;
+    g->planes = 2 * h->cfg.K + 1;
     g->batch_rows = h->cfg.G * h->cfg.P;
     g->max_nodes = h->cfg.max_nodes;
     g->budget = h->cfg.budget;
@@ -959,10 +962,10 @@ int azsp_dropin_step(void* e, const float* priors_host, const float* values_host
         (priors_host == nullptr) != (values_host == nullptr))
         return AZSP_EINVAL;
     const size_t G = (size_t)h->cfg.G, rows = G * (size_t)h->cfg.P, A = (size_t)h->A;
-    static const int elem_of[7] = {1, 4, 2, 2, 0, 0, 0};  // AZSP_FEAT_I8 / F32 / BF16 / F16: plain [rows][17][N][N] tensors only
+    static const int elem_of[7] = {1, 4, 2, 2, 0, 0, 0};  // AZSP_FEAT_I8 / F32 / BF16 / F16: plain [rows][2K+1][N][N] tensors only
     const int fd = h->pub.feature_dtype;
     if (fd < 0 || fd > 6 || elem_of[fd] == 0) return AZSP_EINVAL;
-    const size_t game_feat = (size_t)h->cfg.P * 17 * h->NP * elem_of[fd];
+    const size_t game_feat = (size_t)h->cfg.P * (2 * h->cfg.K + 1) * h->NP * elem_of[fd];
     if ((size_t)feat_bytes > G * game_feat) return AZSP_EINVAL;
     // page-locked staging, device-visible: [priors rows*A f32][values rows f32] | [status G*8 i32][q G*2 f64][fault G i32][valid rows u8][features]
     const size_t o_val = rows * A * 4, up = o_val + rows * 4, o_st = (up + 15) & ~(size_t)15, o_q = o_st + G * 32, o_err = o_q + G * 16,

@@ -17,7 +17,7 @@ class PlayerMove(namedtuple("PlayerMove", ["color", "move"])):
     """History record (base.py:19-22)."""
 
 
-def _engine_for(game, board_size, komi, max_steps, num_to_win, binding, device):
+def _engine_for(game, board_size, komi, max_steps, num_to_win, binding, device, num_stack=8):
     from ..core.engine import Engine, EngineConfig
 
     if binding is None:
@@ -25,7 +25,7 @@ def _engine_for(game, board_size, komi, max_steps, num_to_win, binding, device):
 
         binding, device = _lib.load(require_gpu=True), "cuda"
     cfg = EngineConfig(game=game, board_size=board_size, num_games=1, num_parallel=1, num_simulations=2, komi=komi,
-                       max_steps=max_steps, num_to_win=num_to_win, stop_after_move=True)
+                       max_steps=max_steps, num_to_win=num_to_win, num_stack=num_stack, stop_after_move=True)
     return Engine(binding, cfg, device=device), binding, device
 
 
@@ -39,8 +39,9 @@ class BoardGameEnv:
     def __init__(self, board_size=15, num_stack=8, black_player_id=1, white_player_id=2, has_pass_move=False,
                  has_resign_move=False, id="", *, komi=7.5, max_steps=0, num_to_win=99, _binding=None, _device=None):
         assert black_player_id != white_player_id != 0, "player ids can not be the same, and can not be zero"
-        if num_stack != 8:
-            raise ValueError("the engine stacks exactly 8 history boards (num_stack=8)")
+        from ..core.engine import check_num_stack
+
+        num_stack = check_num_stack(num_stack)  # 1..8: the engine's history ring holds 8 boards
         self.id, self.board_size, self.num_stack = id, board_size, num_stack
         self.black_player, self.white_player = black_player_id, white_player_id
         self.has_pass_move, self.has_resign_move = has_pass_move, has_resign_move
@@ -51,7 +52,7 @@ class BoardGameEnv:
         self.gtp_columns = "ABCDEFGHJKLMNOPQRSTUVWXYZ"
         self.gtp_rows = [str(i) for i in range(board_size, -1, -1)]
         self._komi, self._max_steps, self._num_to_win = komi, max_steps, num_to_win
-        self._eng, self._binding, self._device = _engine_for(self._game, board_size, komi, max_steps, num_to_win, _binding, _device)
+        self._eng, self._binding, self._device = _engine_for(self._game, board_size, komi, max_steps, num_to_win, _binding, _device, num_stack)
         self.history = []
         self.reset()
 
@@ -99,7 +100,7 @@ class BoardGameEnv:
         return self.observation(), reward, self._done, {}
 
     def observation(self):
-        """[X_t, Y_t, ..., X_t-7, Y_t-7, C] int8 planes from the player to move's perspective (base.py:228-259)."""
+        """[X_t, Y_t, ..., X_t-K+1, Y_t-K+1, C] int8 planes (K = num_stack) from the player to move's perspective (base.py:228-259)."""
         return self._obs.copy()
 
     # -- helpers with the reference's names -------------------------------------------------------------
@@ -194,7 +195,8 @@ class BoardGameEnv:
             new.__dict__[k] = v.copy() if isinstance(v, np.ndarray) else v
         new.history = list(self.history)
         new.board_deltas = deque([np.copy(b) for b in self.board_deltas], maxlen=self.num_stack)
-        new._eng, _, _ = _engine_for(self._game, self.board_size, self._komi, self._max_steps, self._num_to_win, self._binding, self._device)
+        new._eng, _, _ = _engine_for(self._game, self.board_size, self._komi, self._max_steps, self._num_to_win, self._binding, self._device,
+                                     self.num_stack)
         if not self._done:  # a finished game needs no device state: step() raises before touching the engine
             new._eng.set_state(0, self.board, self._hist_boards(), self.to_play, self.steps, self.ko, self._last_pass, self._caps)
         return new

@@ -64,7 +64,7 @@ extern "C" {
 #define AZSP_FEAT_F32 1
 #define AZSP_FEAT_BF16 2
 #define AZSP_FEAT_F16 3
-#define AZSP_FEAT_BF16_TILED 4 /* bf16 in the evaluator's tiled layout, 17 planes padded to 32 channels (azsp_stem_tiled) */
+#define AZSP_FEAT_BF16_TILED 4 /* bf16 in the evaluator's tiled layout, 2K+1 planes (K = num_stack) padded to 32 channels (azsp_stem_tiled) */
 #define AZSP_FEAT_F16_TILED 5  /* the same layout with f16 elements (azsp_stem_tiled_f16) */
 #define AZSP_FEAT_F16_SPLIT 6  /* the input of the fp32-class evaluator's stem (azsp_stem_split): split layout [row][plane: hi, lo][4 chunks]
                                   [N*N][8] f16 with 32 channels, azsp_split_bytes(rows, N, 32) bytes; the planes are 0 / 1 = exact f16 values,
@@ -113,7 +113,8 @@ typedef struct AzspConfig {
     float c_puct_base;         /* used by the caller to build the pb_c table (azsp_set_tables) */
     float c_puct_init;
     float disable_resign_ratio;
-    float reserved0;
+    int32_t num_stack;         /* K = history boards per observation, 1..8 (base.py:228-266): 2K+1 planes [X_t, Y_t, ..., X_t-K+1,
+                                  Y_t-K+1, C]; 0 = 8 (callers that predate the field pass 0); > 8 is AZSP_EINVAL */
     double dirichlet_eps;      /* 0.25 (mcts_v2.py:235) */
     double dirichlet_alpha;    /* 0.03 */
     double resign_threshold;   /* <= -1 disables resignation (pipeline.py:216) */
@@ -125,7 +126,7 @@ typedef struct AzspConfig {
 typedef struct AzspGeometry {
     int32_t num_actions;       /* A = N*N (+1 pass for Go) */
     int32_t num_points;        /* N*N */
-    int32_t planes;            /* 17 */
+    int32_t planes;            /* 2 * num_stack + 1 (17 at the default K = 8) */
     int32_t batch_rows;        /* G*P rows of features / priors / values */
     int32_t max_nodes;
     int32_t budget;
@@ -156,12 +157,13 @@ int azsp_reset_games(void* engine, void* stream);
 /* Standalone environment kernels.  actions_dev[G]: action, -1 = resign (Go), -2 = no-op (export only).
  * Outputs (each may be NULL): board int8[G][N*N] (reference colour ids), legal int8[G][A],
  * scalars int32[G][12] = {ko, caps_black, caps_white, steps, to_play, done, reward, winner, area_black,
- * area_white, illegal, last_was_pass}, obs int8[G][17][N][N]. */
+ * area_white, illegal, last_was_pass}, obs int8[G][2K+1][N][N] (K = num_stack). */
 int azsp_env_step(void* engine, const int32_t* actions_dev, int8_t* board_dev, int8_t* legal_dev, int32_t* scalars_dev,
                   int8_t* obs_dev, void* stream);
 
 /* Load an arbitrary position into slot `slot` and make it the (fresh, unevaluated) search root.
- * board_host int8[N*N] and hist_host int8[8][N*N] (newest first, hist[0] == board) use reference colour ids. */
+ * board_host int8[N*N] and hist_host int8[8][N*N] (newest first, hist[0] == board) use reference colour ids; with num_stack K < 8
+ * the rows K..7 are ignored (the observation never shows them). */
 int azsp_set_state(void* engine, int32_t slot, const int8_t* board_host, const int8_t* hist_host, int32_t to_play,
                    int32_t steps, int32_t ko, int32_t last_was_pass, int32_t caps_black, int32_t caps_white, void* stream);
 
@@ -199,7 +201,7 @@ int azsp_commit_move(void* engine, const int32_t* moves_host, void* stream);
  * previous call; both NULL on the first call of a search (nothing to back up yet).  The game's wave runs expand / backup (and the
  * end-of-search work when the budget is met), selects the next leaves into features_dev / valid_dev, and writes status_host int32[G][8],
  * q_host double[G][2] (as azsp_get_status; q_host may be NULL), valid_host uint8[rows] and the first features_bytes bytes of
- * features_dev (the observation planes eval_func receives; 0 = none; feature_dtype must be a plain [rows][17][N][N] tensor: I8 / F32 /
+ * features_dev (the observation planes eval_func receives; 0 = none; feature_dtype must be a plain [rows][2K+1][N][N] tensor: I8 / F32 /
  * BF16 / F16) -- through a page-locked staging buffer of the engine that the kernel reads and writes directly, so no copy command is
  * issued.  priors_dev / values_dev are the caller's evaluator tensors (unused by this entry beyond validation; azsp_expand_backup
  * reads them).  Host pointers may be pageable. */
@@ -207,7 +209,7 @@ int azsp_dropin_step(void* engine, const float* priors_host, const float* values
                      void* features_dev, uint8_t* valid_dev, int32_t* status_host, double* q_host, uint8_t* valid_host, void* features_host,
                      int64_t features_bytes, void* stream);
 
-/* Collect finished games.  states int8[cap][17][N][N], pi float[cap][A], z float[cap] receive the samples of
+/* Collect finished games.  states int8[cap][2K+1][N][N] (K = num_stack), pi float[cap][A], z float[cap] receive the samples of
  * whole games back to back; games_host int32[max_games][16] = {start, length, winner(ref id, 0 none), area_black,
  * area_white, num_passes, resigned, resign_disabled, marked_for_resign, could_won, marked_player(ref id, 0 none),
  * uid, training_steps, reward, last_player(ref id), slot}.  Synchronises the stream. */
@@ -381,9 +383,9 @@ int azsp_replay_gather(const int8_t* ring_states_dev, const float* ring_pi_dev, 
                        float* out_pi_dev, float* out_z_dev, void* stream);
 
 /* Stem of the evaluator (core/network.py:98-108 conv_block: conv3x3 17 -> C + BatchNorm + ReLU) on the tiled layout: the
- * input is the feature tensor azsp_select writes with feature_dtype = AZSP_FEAT_BF16_TILED (17 planes zero-padded to 32
- * channels: [tile][4][3*S*S][8] bf16, azsp_tiled_bytes(rows, S, 32) bytes); w_packed is [9 taps][C out][32 in] bf16 (input
- * channels 17..31 zero), the output is the tower's tiled layout with planes of board_size + 2 (pad - 1): pad = 1 for Go, pad = 3
+ * input is the feature tensor azsp_select writes with feature_dtype = AZSP_FEAT_BF16_TILED (2K+1 planes, 17 at num_stack K = 8,
+ * zero-padded to 32 channels: [tile][4][3*S*S][8] bf16, azsp_tiled_bytes(rows, S, 32) bytes); w_packed is [9 taps][C out][32 in] bf16
+ * (input channels 2K+1..31 zero), the output is the tower's tiled layout with planes of board_size + 2 (pad - 1): pad = 1 for Go, pad = 3
  * for Gomoku (core/network.py:101-105: 13x13 boards become 17x17 planes).  Same kernels as azsp_conv3x3_tiled with 4 input chunks;
  * on the device: (board 9, 128 filters, pad 1), (board 9, 64 filters, pad 1), (board 13, 64 filters, pad 3) and (board 19, 256 filters, pad 1). */
 int azsp_stem_tiled(const void* features_tiled_dev, const void* w_packed_dev, const float* bias_dev, void* y_tiled_dev, int64_t boards,

@@ -65,19 +65,20 @@ class _NullLogger:
         pass
 
 
-def main(name):
-    cfg = CONFIGS[name]
+def main(name, cfg=None, out_path=None):
+    """cfg / out_path: another config and file than CONFIGS[name] -> tests/golden/mcts_<name>.npz (tools/gen_golden_stack.py)."""
+    cfg = CONFIGS[name] if cfg is None else cfg
     ref_harness.install(cfg["n"])
     from alpha_zero.core import mcts_v2, pipeline
 
     if cfg["game"] == "go":
         from alpha_zero.envs.go import GoEnv
 
-        env = GoEnv()
+        env = GoEnv(num_stack=cfg.get("num_stack", 8))
     else:
         from alpha_zero.envs.gomoku import GomokuEnv
 
-        env = GomokuEnv(board_size=cfg["n"])
+        env = GomokuEnv(board_size=cfg["n"], num_stack=cfg.get("num_stack", 8))
     A = env.action_dim
     K = 16  # max uniforms recorded per move
     moves_log = []  # per searched move
@@ -242,7 +243,7 @@ def main(name):
             out[f"g{g}_zs"] = gm["zs"]
             out[f"g{g}_stats"] = np.array(json.dumps({k: (v if not isinstance(v, (np.floating, np.integer)) else v.item())
                                                      for k, v in gm["stats"].items()}))
-    np.savez_compressed(os.path.join(GOLD, f"mcts_{name}.npz"), **out)
+    np.savez_compressed(out_path or os.path.join(GOLD, f"mcts_{name}.npz"), **out)
     fin = [g["finished"] for g in games]
     print(f"{name}: {M} searched moves, games finished={fin}, "
           f"results={[g['stats'].get('game_result') for g in games]}, lens={[g['stats'].get('game_length') for g in games]}")
