@@ -1,6 +1,6 @@
 """bench.py -- self-play moves/sec of the batched engine (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1: one rank per GPU over RCCL.  Either the caller starts the ranks (`python -m torch.distributed.run --nproc-per-node N
 bench.py --gpus N ...`: WORLD_SIZE must then equal N) or, when WORLD_SIZE is not set, bench.py re-executes itself under
@@ -14,7 +14,7 @@ inherited visits count: mcts_v2.py:568), num_parallel P = 8, 10-block x 128-filt
 The evaluator runs at the REFERENCE'S precision class (fp32: pipeline.py:91-123, no autocast anywhere in the reference) on the
 hand-written split-precision kernels (az_conv_sp.h: every value a hi + lo f16 pair, a product = three f16 MFMAs into fp32
 accumulators; as close to fp64 as the library's fp32 convolution, tests/test_split_tower.py).  `--net-dtype bf16 / fp16` select the
-lower-precision evaluators; the default run reports the bf16 one as a labelled companion, never as `value`.
+lower-precision evaluators; a --full run reports the bf16 one as a labelled companion, never as `value`.
 One "step" = one engine round over all games: expand/backup of the previous G*P leaf batch, end-of-move
 work, selection of the next P leaves per game, observation planes, and the network forward on G*P rows.
 All inputs live in HBM; nothing crosses PCIe inside the timed region except the harvests of finished games.
@@ -26,6 +26,12 @@ move completions are spread evenly over rounds and a 20-round window measures th
 region always contains at least two harvests + gathers (every min(--harvest-every, --steps / 2) rounds).
 Prints ONE JSON line on rank 0.  --dump-outputs DIR also writes what the timed path handed its caller after the last timed step as
 DIR/<name>.npy (see step_outputs / dump_outputs); the inputs depend on the arguments only, so two builds can be compared output for output.
+
+A plain run does only what the headline needs: set-up, pre-roll, warm-up, the timed steps, the dump, the line.  Its line carries the
+figures of the timed steps themselves (`value`, `ms_per_step`, per-rank report, `engine_roofline` / `nn_roofline` from the steps' HIP
+events, the evaluator's range record).  --full also runs what takes runs of its own: the tower kernel replay behind `roofline`,
+the companion evaluators, the fresh-tree variant, the CPU baselines and c1_dropin; --no-companions / --no-fresh-tree /
+--no-cpu-baseline leave parts of it out.  Without --full those fields are null.
 """
 import argparse
 import json
@@ -99,6 +105,9 @@ def parse_args(argv=None):
     ap.add_argument("--preroll-rounds", type=int, default=300, help="minimum untimed rounds after the stagger (steady state, see module docstring)")
     ap.add_argument("--preroll-moves", type=int, default=2, help="every slot must have committed this many searched moves before timing")
     ap.add_argument("--harvest-every", type=int, default=50)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the measurements that take runs of their own: tower kernel replay and roofline, "
+                         "companion evaluators, fresh-tree variant, CPU baselines, c1_dropin (the --no-* options below leave parts out)")
     ap.add_argument("--cpu-seconds", type=float, default=60.0)
     ap.add_argument("--cpu-cores", type=int, default=0, help="0 = all usable host cores (cgroup quota aware)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -310,6 +319,14 @@ def per_rank_report(cnt, elapsed, world, dev):
             "harvest_gather_share_of_time": round(float(t[:, 4].max()), 5)}  # of each rank's own timed region, the largest
 
 
+def tower_path(actor, args, dev):
+    """(split, tiled): the actor's tower ran on the fp32-class split-precision kernels / on the bf16 or f16 tiled kernels."""
+    inf = actor.infer
+    split = args.net_dtype == "fp32" and getattr(inf, "_split", None) is not None and inf.supports_split_features(args.board, dev)
+    tiled = args.net_dtype != "fp32" and getattr(inf, "_tiled", None) is not None and actor.tiled_features
+    return split, tiled
+
+
 def tower_replay(actor, args, dev, reps=5):
     """Times the dominant kernel: the forward's own tower launch sequence, one HIP event after every launch (recorded on the stream the
     kernels are launched on), on the REAL activations of the last forward -- the tower input that forward's stem produced is kept in a
@@ -323,8 +340,7 @@ def tower_replay(actor, args, dev, reps=5):
     S_t = n + 2 * (inf.stem_pad - 1)  # tower planes (17x17 behind the Gomoku pad-3 stem)
     rows = actor.engine.rows
     st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    split = args.net_dtype == "fp32" and getattr(inf, "_split", None) is not None and inf.supports_split_features(n, dev)
-    tiled = args.net_dtype != "fp32" and getattr(inf, "_tiled", None) is not None and actor.tiled_features
+    split, tiled = tower_path(actor, args, dev)
     if not (split or tiled):
         return None
     fused = inf.use_fused_block and ((tiled and (args.filters, S_t) in ((64, 17), (64, 9)) and args.net_dtype == "bf16")  # one launch per ResNetBlock
@@ -758,10 +774,10 @@ def main(argv=None):
     if total_moves <= 0:
         raise SystemExit("bench.py: no move was committed inside the timed region -- the pre-roll did not reach the steady state")
 
-    # ---- dominant kernel (the tower convolution): average launch duration, HIP events on the launch stream -----------
-    conv = tower_replay(actor, args, dev) if rank == 0 else None
+    # ---- dominant kernel (the tower convolution): average launch duration, HIP events on the launch stream (--full) -----------
+    conv = tower_replay(actor, args, dev) if rank == 0 and args.full else None
     replay_range = None
-    if rank == 0 and erange is not None:  # (the replay runs the forward's own launches on its own data: expected 0 too); leaves the record clean
+    if rank == 0 and args.full and erange is not None:  # (the replay runs the forward's own launches on its own data: expected 0 too); leaves the record clean
         ev_r, mx_r = actor.infer.split_range_status(reset=True)
         replay_range = {"events": ev_r, "largest_abs": mx_r * 2.0 ** actor.infer.act_shift}
 
@@ -780,6 +796,7 @@ def main(argv=None):
             tb += ea[1].elapsed_time(ea[2]) / 20
         print(json.dumps({"split_round_ms": {"expand_backup_endmove": round(ta, 4), "select_features": round(tb, 4)}}), flush=True)
     if rank == 0:
+        split_eval = tower_path(actor, args, dev)[0]
         # ---- roofline of the dominant hand-written kernel: the fused round kernel (HBM bound) ----------
         e_bytes = {"bf16": 2, "fp16": 2, "fp32": 4}[args.net_dtype]
         W = (n * n + 63) // 64
@@ -813,7 +830,6 @@ def main(argv=None):
                                           "achieved_GBs": round(bk_bytes / (bk_ms * 1e-3) / 1e9, 2)}}
         flops_eval = net_flops_per_eval(n, A, args.blocks, args.filters, args.filters, game != "go")
         nn_tflops = flops_eval * args.games * args.parallel / (nn_ms * 1e-3) / 1e12
-        split_eval = conv is not None and conv["split"]
         # fp32-class evaluator: every multiply is SPLIT_PRODUCTS f16 MFMA products, so the bound on ALGORITHMIC flops is the f16 peak / 3
         peak = MFMA_PEAK_TFLOPS["fp16"] / SPLIT_PRODUCTS if split_eval else MFMA_PEAK_TFLOPS[args.net_dtype]
         nn_roof = {"kernel": "whole evaluator forward on G*P rows (stem + tower + heads)" + (", algorithmic (fp32-equivalent) flops; peak = f16 MFMA peak / 3 products" if split_eval else ""),
@@ -821,10 +837,10 @@ def main(argv=None):
                    "frac": round(nn_tflops / peak, 5), "avg_forward_ms": round(nn_ms, 3),
                    "share_of_step": round(nn_ms / (bk_ms + k_ms + nn_ms), 4),
                    "batch_fill": round((cnt["leaves"] + cnt["root_evals"]) / (steps * args.games * args.parallel), 4)}
-        roofline = tower_roofline(conv, args, bk_ms + k_ms + nn_ms) if conv is not None else engine_roof
-        # ---- companions (world == 1 only): the same engine and workload with another evaluator -- labelled, never `value` ----------
+        roofline = tower_roofline(conv, args, bk_ms + k_ms + nn_ms) if conv is not None else (engine_roof if args.full else None)
+        # ---- companions (--full, world == 1 only): the same engine and workload with another evaluator -- labelled, never `value` ----------
         lowp = fp32_lib = None
-        if world == 1 and not args.no_companions:
+        if args.full and world == 1 and not args.no_companions:
             def companion(dtype_name, split, steps, pre, label):
                 a = make_actor(dtype_name, split=split)
                 prer = preroll(a, args, world, dev, min_rounds=pre)
@@ -845,13 +861,13 @@ def main(argv=None):
                 # than the reference's, bounded against it in tests/test_precision_parity.py; full protocol (same pre-roll as the headline)
                 lowp = companion("bf16", True, args.steps, args.preroll_rounds, "full (the headline's pre-roll and window)")
                 # (b) the reference's precision on LIBRARY convolutions (+ azsp_bias_act): what the hand-written fp32-class kernels replace
-                if conv is not None and conv["split"]:
+                if split_eval:
                     fp32_lib = companion("fp32", False, min(20, args.steps), 30, "short protocol (30-round pre-roll, <= 20 steps: 180 ms per round)")
             else:
                 # a lower-precision run: the reference-precision evaluator as the companion
                 lowp = companion("fp32", True, min(40, args.steps), 60, "short protocol (60-round pre-roll, <= 40 steps)")
         fresh = None
-        if world == 1 and not args.no_fresh_tree:
+        if args.full and world == 1 and not args.no_fresh_tree:
             # SURVEY 8d's "fresh-tree" variant: sub-tree reuse off (mcts_v2.py:436-446 never runs), every move pays the full budget of
             # sims + P root visits instead of inheriting the chosen child's (mcts_v2.py:378 semantics discounted in `value`).  Without
             # inheritance every move takes the same number of rounds, so the slots stay in phase: the window is 5 whole move periods.
@@ -865,7 +881,7 @@ def main(argv=None):
             del af, evf
             torch.cuda.empty_cache()
         cpu, c1, c1d = None, None, None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             from oracle import baseline
 
             cores = args.cpu_cores or usable_host_cores()
@@ -909,7 +925,7 @@ def main(argv=None):
             "value": round(total_moves / elapsed_max, 2), "unit": "moves/s", "n_gpus": world, "rccl_ranks": rccl_ranks, "process_group": process_group,
             "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(elapsed_max / steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": DTYPE_LABEL[args.net_dtype] if (args.net_dtype != "fp32" or (conv is not None and conv["split"])) else (
+            "dtype": DTYPE_LABEL[args.net_dtype] if (args.net_dtype != "fp32" or split_eval) else (
                 "fp32-class tower (f16 hi+lo pairs, 3 MFMA products, fp32 accumulate) behind library fp32 stem and heads / f32-f64 tree"
                 if "split-precision tower" in actor.evaluator_path else "fp32 (library convolutions) / f32-f64 tree"),
             "data": "synthetic",

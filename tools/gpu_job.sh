@@ -20,11 +20,11 @@ for J in "$@"; do
     tests) timeout 2400 python -m pytest tests -m gpu -x -q > $O/gpu_tests.txt 2>&1; echo "tests rc=$?" | tee -a $O/status.txt; tail -5 $O/gpu_tests.txt ;;
     tests:*) timeout 1800 python -m pytest tests -m gpu -x -q -k "${J#tests:}" > $O/gpu_tests_k.txt 2>&1; echo "tests -k rc=$?" | tee -a $O/status.txt; tail -15 $O/gpu_tests_k.txt ;;
     smoke) timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; echo "smoke rc=$?" | tee -a $O/status.txt; tail -2 $O/smoke.txt ;;
-    bench) timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err; echo "bench rc=$?" | tee -a $O/status.txt; summ $O/bench_driver_cmd.json ;;
-    bench_c2) timeout 600 python bench.py --game gomoku --board 13 --blocks 6 --filters 64 --steps 100 --warmup 20 --no-companions --no-fresh-tree --no-cpu-baseline > $O/bench_gomoku13_c2.json 2> $O/bench_c2.err; echo "c2 rc=$?" | tee -a $O/status.txt; summ $O/bench_gomoku13_c2.json ;;
-    bench_c5) timeout 900 python bench.py --board 19 --games 1024 --sims 800 --blocks 20 --filters 256 --net-dtype bf16 --steps 40 --warmup 5 --no-companions --no-fresh-tree --no-cpu-baseline > $O/bench_go19_c5.json 2> $O/bench_c5.err; echo "c5 rc=$?" | tee -a $O/status.txt; summ $O/bench_go19_c5.json ;;
-    bench_12b64) timeout 600 python bench.py --blocks 12 --filters 64 --steps 100 --warmup 20 --no-companions --no-fresh-tree --no-cpu-baseline > $O/bench_go9_12b64.json 2> $O/bench_12b64.err; echo "12b64 rc=$?" | tee -a $O/status.txt; summ $O/bench_go9_12b64.json ;;
-    bench_c4) timeout 600 python bench.py --sims 400 --steps 60 --warmup 10 --no-companions --no-fresh-tree --no-cpu-baseline > $O/bench_go9_s400_c4_1gpu.json 2> $O/bench_c4.err; echo "c4 rc=$?" | tee -a $O/status.txt; summ $O/bench_go9_s400_c4_1gpu.json ;;
+    bench) timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err; echo "bench rc=$?" | tee -a $O/status.txt; summ $O/bench_driver_cmd.json ;;
+    bench_c2) timeout 600 python bench.py --game gomoku --board 13 --blocks 6 --filters 64 --steps 100 --warmup 20 --full --no-companions --no-fresh-tree --no-cpu-baseline > $O/bench_gomoku13_c2.json 2> $O/bench_c2.err; echo "c2 rc=$?" | tee -a $O/status.txt; summ $O/bench_gomoku13_c2.json ;;
+    bench_c5) timeout 900 python bench.py --board 19 --games 1024 --sims 800 --blocks 20 --filters 256 --net-dtype bf16 --steps 40 --warmup 5 --full --no-companions --no-fresh-tree --no-cpu-baseline > $O/bench_go19_c5.json 2> $O/bench_c5.err; echo "c5 rc=$?" | tee -a $O/status.txt; summ $O/bench_go19_c5.json ;;
+    bench_12b64) timeout 600 python bench.py --blocks 12 --filters 64 --steps 100 --warmup 20 --full --no-companions --no-fresh-tree --no-cpu-baseline > $O/bench_go9_12b64.json 2> $O/bench_12b64.err; echo "12b64 rc=$?" | tee -a $O/status.txt; summ $O/bench_go9_12b64.json ;;
+    bench_c4) timeout 600 python bench.py --sims 400 --steps 60 --warmup 10 --full --no-companions --no-fresh-tree --no-cpu-baseline > $O/bench_go9_s400_c4_1gpu.json 2> $O/bench_c4.err; echo "c4 rc=$?" | tee -a $O/status.txt; summ $O/bench_go9_s400_c4_1gpu.json ;;
     probe_power) (cd tools/probes && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -w -o mfma_power_probe mfma_power_probe.hip) && timeout 300 ./tools/probes/mfma_power_probe $O/mfma_power_probe.json > $O/mfma_power_probe.txt 2>&1; echo "probe rc=$?" | tee -a $O/status.txt; cat $O/mfma_power_probe.txt ;;
     pmc:*) PMC_FAMILIES="${J#pmc:}" bash tools/profile_r06.sh > $O/pmc_${J#pmc:}.log 2>&1; echo "pmc ${J#pmc:} rc=$?" | tee -a $O/status.txt; tail -3 $O/pmc_${J#pmc:}.log ;;
     rocprof_bench) (cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/rb && timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/rb -- python $GRAFT_REPO_ROOT/bench.py --gpus 1 --steps 20 --warmup 5 --no-companions --no-fresh-tree --no-cpu-baseline > $GRAFT_REPO_ROOT/$O/bench_under_rocprof.json 2> /tmp/rb.err; python $GRAFT_REPO_ROOT/tools/rocprof_summary.py $(find /tmp/rb -name "*.db" | head -1) > $GRAFT_REPO_ROOT/$O/kernel_stats_default.txt 2>&1); echo "rocprof rc=$?" | tee -a $O/status.txt; head -8 $O/kernel_stats_default.txt | cut -c1-200 ;;
@@ -45,7 +45,7 @@ for J in "$@"; do
           cp alpha_zero_amd/libazsp.so /tmp/libazsp_tree.so
           for R in 1 2; do for V in tree prev; do
             if [ $V = prev ]; then cp tools/probes/libazsp_prev.so alpha_zero_amd/libazsp.so; else cp /tmp/libazsp_tree.so alpha_zero_amd/libazsp.so; fi
-            timeout 600 python bench.py --gpus 1 --steps 40 --warmup 5 ${BENCH_AB_ARGS:-} --no-companions --no-fresh-tree --no-cpu-baseline > $O/bench_ab_${V}_$R.json 2> $O/bench_ab.err; echo "bench_ab $V $R rc=$?" | tee -a $O/status.txt; summ $O/bench_ab_${V}_$R.json
+            timeout 600 python bench.py --gpus 1 --steps 40 --warmup 5 ${BENCH_AB_ARGS:-} --full --no-companions --no-fresh-tree --no-cpu-baseline > $O/bench_ab_${V}_$R.json 2> $O/bench_ab.err; echo "bench_ab $V $R rc=$?" | tee -a $O/status.txt; summ $O/bench_ab_${V}_$R.json
           done; done
           cp /tmp/libazsp_tree.so alpha_zero_amd/libazsp.so ;;
     conv19_ab) timeout 600 python tools/conv19_ab.py > $O/conv19_ab.txt 2>&1; echo "conv19_ab rc=$?" | tee -a $O/status.txt; cat $O/conv19_ab.txt ;;

@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
-python $R/bench.py --steps 100 --warmup 60 2>&1 | tail -1 > $O/bench_default.json
+python $R/bench.py --steps 100 --warmup 60 --full 2>&1 | tail -1 > $O/bench_default.json
 timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/kt -- python $R/bench.py --steps 40 --warmup 60 --no-graph --no-cpu-baseline > /tmp/kt.log 2>&1
 tail -1 /tmp/kt.log > $O/bench_nograph_under_rocprof.json
 python $R/tools/rocprof_summary.py $(find /tmp/kt -name "*.db" | head -1) > $O/kernel_stats.txt

@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
-python $R/bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/r02_bench_driver_cmd.json
+python $R/bench.py --gpus 1 --steps 20 --warmup 5 --full 2>/dev/null | tail -1 > $O/r02_bench_driver_cmd.json
 timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/kg -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-fp32 > /tmp/kg.log 2>&1
 tail -1 /tmp/kg.log > $O/r02_bench_under_rocprof_graph.json
 python $R/tools/rocprof_summary.py $(find /tmp/kg -name "*.db" | head -1) > $O/r02_kernel_stats_default_graph.txt

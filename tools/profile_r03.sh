@@ -9,8 +9,8 @@ for rep in 1 2; do for v in 0 2 1; do
 done; done
 cat $O/r03l_conv19_ab.txt
 timeout 1500 python -m pytest tests -m gpu -q > $O/r03l_pytest.log 2>&1; echo "pytest rc=$?" | tee -a $O/r03l_pytest.log; tail -4 $O/r03l_pytest.log
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r03l_bench_driver_cmd.json 2> $O/r03l_bench_driver_cmd.err
-timeout 900 python bench.py --game gomoku --board 13 --blocks 6 --filters 64 --steps 100 --warmup 20 --cpu-seconds 20 > $O/r03l_bench_gomoku13_c2.json 2> $O/r03l_bench_gomoku13_c2.err
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/r03l_bench_driver_cmd.json 2> $O/r03l_bench_driver_cmd.err
+timeout 900 python bench.py --game gomoku --board 13 --blocks 6 --filters 64 --steps 100 --warmup 20 --full --cpu-seconds 20 > $O/r03l_bench_gomoku13_c2.json 2> $O/r03l_bench_gomoku13_c2.err
 python - <<'PY'
 import json,os
 O=os.environ.get("GRAFT_REPO_ROOT",".")+"/gpurun_out/"

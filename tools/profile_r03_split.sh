@@ -5,7 +5,7 @@ O=$GRAFT_REPO_ROOT/gpurun_out
 rm -f $O/split_conv_error.jsonl
 timeout 1800 python -m pytest tests -m gpu -q > $O/r03s_pytest.log 2>&1; echo "pytest rc=$?" | tee -a $O/r03s_pytest.log; tail -6 $O/r03s_pytest.log | cut -c1-300
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r03s_bench_driver_cmd.json 2> $O/r03s_bench_driver_cmd.err
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/r03s_bench_driver_cmd.json 2> $O/r03s_bench_driver_cmd.err
 python - <<'PY'
 import json,os
 O=os.environ.get("GRAFT_REPO_ROOT",".")+"/gpurun_out/"
