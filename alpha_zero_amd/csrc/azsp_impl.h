@@ -695,6 +695,14 @@ static int az_check_engine_fault(AzHandle* h, void* stream) {
     return AZSP_OK;
 }
 
+// The evaluator wrappers: a backend launcher returns 0, 1 (unsupported shape) or -1 (device error).
+static int az_rc(int rc) { return rc == 0 ? AZSP_OK : (rc > 0 ? AZSP_EINVAL : AZSP_EDEVICE); }
+// ... and most of them refuse the same way: `bad` arguments or a board count outside [0, 2^31) are EINVAL, no boards are nothing to do.
+template <class F> static int az_launch(bool bad, int64_t boards, F&& launch) {
+    if (bad || boards < 0 || boards > 0x7fffffff) return AZSP_EINVAL;
+    return boards == 0 ? AZSP_OK : az_rc(launch());
+}
+
 extern "C" {
 
 int azsp_create(const AzspConfig* p, void** out) {
@@ -1133,18 +1141,14 @@ int64_t azsp_tiled_bytes(int64_t boards, int32_t S, int32_t C) {
 }
 
 int azsp_tile_layout(const void* src, void* dst, int64_t boards, int32_t S, int32_t C, int32_t to_tiled, void* stream) {
-    if (!src || !dst || boards < 0 || boards > 0x7fffffff || S <= 0 || C <= 0 || C % 8) return AZSP_EINVAL;
-    if (boards == 0) return AZSP_OK;
-    const int rc = azb::launch_tile_layout(src, dst, (long long)boards, S, C, to_tiled, stream);
-    return rc == 0 ? AZSP_OK : (rc > 0 ? AZSP_EINVAL : AZSP_EDEVICE);
+    return az_launch(!src || !dst || S <= 0 || C <= 0 || C % 8, boards,
+                     [&] { return azb::launch_tile_layout(src, dst, (long long)boards, S, C, to_tiled, stream); });
 }
 
 static int az_conv3x3_tiled(const void* x, const void* w, const float* bias, const void* res, void* y, int64_t boards, int32_t S, int32_t C,
                             int32_t relu, void* stream, int f16) {
-    if (!x || !w || !bias || !y || boards < 0 || boards > 0x7fffffff) return AZSP_EINVAL;
-    if (boards == 0) return AZSP_OK;
-    const int rc = azb::launch_conv3x3_tiled(x, w, bias, res, y, (long long)boards, S, C, relu, stream, f16);
-    return rc == 0 ? AZSP_OK : (rc > 0 ? AZSP_EINVAL : AZSP_EDEVICE);
+    return az_launch(!x || !w || !bias || !y, boards,
+                     [&] { return azb::launch_conv3x3_tiled(x, w, bias, res, y, (long long)boards, S, C, relu, stream, f16); });
 }
 int azsp_conv3x3_tiled(const void* x, const void* w, const float* bias, const void* res, void* y, int64_t boards, int32_t S, int32_t C,
                        int32_t relu, void* stream) {
@@ -1161,52 +1165,39 @@ int64_t azsp_split_bytes(int64_t boards, int32_t S, int32_t C) {
 }
 
 int azsp_split_layout(const void* src, void* dst, int64_t boards, int32_t S, int32_t C, int32_t to_split, uint32_t* range_rec, void* stream) {
-    if (!src || !dst || boards < 0 || boards > 0x7fffffff || S <= 0 || C <= 0 || C % 8) return AZSP_EINVAL;
-    if (boards == 0) return AZSP_OK;
-    const int rc = azb::launch_split_layout(src, dst, (long long)boards, S, C, to_split, stream, range_rec);
-    return rc == 0 ? AZSP_OK : (rc > 0 ? AZSP_EINVAL : AZSP_EDEVICE);
+    return az_launch(!src || !dst || S <= 0 || C <= 0 || C % 8, boards,
+                     [&] { return azb::launch_split_layout(src, dst, (long long)boards, S, C, to_split, stream, range_rec); });
 }
 
 int azsp_conv3x3_split(const void* x, const void* w, const float* bias, const void* res, void* y, int64_t boards, int32_t S, int32_t C,
                        int32_t relu, uint32_t* range_rec, void* stream) {
-    if (!x || !w || !bias || !y || x == y || boards < 0 || boards > 0x7fffffff) return AZSP_EINVAL;
     // 17x17: 15 of a board's 304 column slots repeat a position of an EARLIER column tile, whose store has happened by the time the
     // repeat loads its residual -- in place (residual == y) the repeat would add the skip twice.  Refused, not silently wrong.
-    if (S == 17 && res == y) return AZSP_EINVAL;
-    if (boards == 0) return AZSP_OK;
-    const int rc = azb::launch_conv3x3_split(x, w, bias, res, y, (long long)boards, S, C, relu, stream, range_rec);
-    return rc == 0 ? AZSP_OK : (rc > 0 ? AZSP_EINVAL : AZSP_EDEVICE);
+    return az_launch(!x || !w || !bias || !y || x == y || (S == 17 && res == y), boards,
+                     [&] { return azb::launch_conv3x3_split(x, w, bias, res, y, (long long)boards, S, C, relu, stream, range_rec); });
 }
 
 int azsp_resblock_split(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y, int64_t boards, int32_t S, int32_t C,
                         uint32_t* range_rec, void* stream) {
-    if (!x || !w1 || !b1 || !w2 || !b2 || !y || x == y || boards < 0 || boards > 0x7fffffff) return AZSP_EINVAL;
-    if (boards == 0) return AZSP_OK;
-    const int rc = azb::launch_resblock_split(x, w1, b1, w2, b2, y, (long long)boards, S, C, stream, range_rec);
-    return rc == 0 ? AZSP_OK : (rc > 0 ? AZSP_EINVAL : AZSP_EDEVICE);
+    return az_launch(!x || !w1 || !b1 || !w2 || !b2 || !y || x == y, boards,
+                     [&] { return azb::launch_resblock_split(x, w1, b1, w2, b2, y, (long long)boards, S, C, stream, range_rec); });
 }
 
 int azsp_split_features(const float* planes, void* dst, int64_t boards, int32_t S, int32_t cin, uint32_t* range_rec, void* stream) {
-    if (!planes || !dst || boards < 0 || boards > 0x7fffffff || S <= 0 || cin < 1 || cin > 32) return AZSP_EINVAL;
-    if (boards == 0) return AZSP_OK;
-    const int rc = azb::launch_split_features(planes, dst, (long long)boards, S, cin, stream, range_rec);
-    return rc == 0 ? AZSP_OK : (rc > 0 ? AZSP_EINVAL : AZSP_EDEVICE);
+    return az_launch(!planes || !dst || S <= 0 || cin < 1 || cin > 32, boards,
+                     [&] { return azb::launch_split_features(planes, dst, (long long)boards, S, cin, stream, range_rec); });
 }
 
 int azsp_stem_split(const void* x, const void* w, const float* bias, void* y, int64_t boards, int32_t S, int32_t C, int32_t pad, int32_t relu,
                     uint32_t* range_rec, void* stream) {
-    if (!x || !w || !bias || !y || x == y || boards < 0 || boards > 0x7fffffff) return AZSP_EINVAL;
-    if (boards == 0) return AZSP_OK;
-    const int rc = azb::launch_stem_split(x, w, bias, y, (long long)boards, S, C, pad, relu, stream, 0, range_rec);
-    return rc == 0 ? AZSP_OK : (rc > 0 ? AZSP_EINVAL : AZSP_EDEVICE);
+    return az_launch(!x || !w || !bias || !y || x == y, boards,
+                     [&] { return azb::launch_stem_split(x, w, bias, y, (long long)boards, S, C, pad, relu, stream, 0, range_rec); });
 }
 
 int azsp_stem_split_exact(const void* x, const void* w, const float* bias, void* y, int64_t boards, int32_t S, int32_t C, int32_t pad, int32_t relu,
                           uint32_t* range_rec, void* stream) {
-    if (!x || !w || !bias || !y || x == y || boards < 0 || boards > 0x7fffffff) return AZSP_EINVAL;
-    if (boards == 0) return AZSP_OK;
-    const int rc = azb::launch_stem_split(x, w, bias, y, (long long)boards, S, C, pad, relu, stream, 1, range_rec);
-    return rc == 0 ? AZSP_OK : (rc > 0 ? AZSP_EINVAL : AZSP_EDEVICE);
+    return az_launch(!x || !w || !bias || !y || x == y, boards,
+                     [&] { return azb::launch_stem_split(x, w, bias, y, (long long)boards, S, C, pad, relu, stream, 1, range_rec); });
 }
 
 int azsp_split_range_read(const uint32_t* range_rec, uint32_t* events, float* max_abs, int32_t reset, void* stream) {
@@ -1226,22 +1217,17 @@ int64_t azsp_small_batch_waves(int64_t waves) { return (int64_t)azb::small_batch
 int azsp_head_split(const void* x, const float* head_w, const float* head_b, const float* pol_fc_wt, const float* pol_fc_b, const float* val_fc1_wt,
                     const float* val_fc1_b, const float* val_fc2_w, float val_fc2_b, float* priors, float* values, int64_t boards, int32_t S,
                     int32_t C, int32_t A, int32_t F, int32_t npol, void* stream) {
-    if (!x || !head_w || !head_b || !pol_fc_wt || !pol_fc_b || !val_fc1_wt || !val_fc1_b || !val_fc2_w || !priors || !values || boards < 0 ||
-        boards > 0x7fffffff || S <= 0 || C <= 0 || A <= 0 || F <= 0)
-        return AZSP_EINVAL;
-    if (boards == 0) return AZSP_OK;
     const azb::HeadSplitArgs a = {x, head_w, head_b, pol_fc_wt, pol_fc_b, val_fc1_wt, val_fc1_b, val_fc2_w, val_fc2_b, priors, values, (long long)boards,
                              S, C, A, F, npol};
-    const int rc = azb::launch_head_split(a, stream);
-    return rc == 0 ? AZSP_OK : (rc > 0 ? AZSP_EINVAL : AZSP_EDEVICE);
+    return az_launch(!x || !head_w || !head_b || !pol_fc_wt || !pol_fc_b || !val_fc1_wt || !val_fc1_b || !val_fc2_w || !priors || !values || S <= 0 ||
+                         C <= 0 || A <= 0 || F <= 0,
+                     boards, [&] { return azb::launch_head_split(a, stream); });
 }
 
 int azsp_resblock_tiled(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y, int64_t boards, int32_t S, int32_t C,
                         void* stream) {
-    if (!x || !w1 || !b1 || !w2 || !b2 || !y || boards < 0 || boards > 0x7fffffff) return AZSP_EINVAL;
-    if (boards == 0) return AZSP_OK;
-    const int rc = azb::launch_resblock_tiled(x, w1, b1, w2, b2, y, (long long)boards, S, C, stream);
-    return rc == 0 ? AZSP_OK : (rc > 0 ? AZSP_EINVAL : AZSP_EDEVICE);
+    return az_launch(!x || !w1 || !b1 || !w2 || !b2 || !y, boards,
+                     [&] { return azb::launch_resblock_tiled(x, w1, b1, w2, b2, y, (long long)boards, S, C, stream); });
 }
 
 int azsp_replay_gather(const int8_t* ring_states, const float* ring_pi, const float* ring_z, const int64_t* idx, int32_t batch, int32_t channels,
@@ -1257,10 +1243,8 @@ int azsp_replay_gather(const int8_t* ring_states, const float* ring_pi, const fl
 
 static int az_stem_tiled(const void* x, const void* w, const float* bias, void* y, int64_t boards, int32_t S, int32_t C, int32_t pad, int32_t relu,
                          void* stream, int f16) {
-    if (!x || !w || !bias || !y || boards < 0 || boards > 0x7fffffff || pad < 1) return AZSP_EINVAL;
-    if (boards == 0) return AZSP_OK;
-    const int rc = azb::launch_stem_tiled(x, w, bias, y, (long long)boards, S, C, pad, relu, stream, f16);
-    return rc == 0 ? AZSP_OK : (rc > 0 ? AZSP_EINVAL : AZSP_EDEVICE);
+    return az_launch(!x || !w || !bias || !y || pad < 1, boards,
+                     [&] { return azb::launch_stem_tiled(x, w, bias, y, (long long)boards, S, C, pad, relu, stream, f16); });
 }
 int azsp_stem_tiled(const void* x, const void* w, const float* bias, void* y, int64_t boards, int32_t S, int32_t C, int32_t pad, int32_t relu,
                     void* stream) {
@@ -1278,8 +1262,7 @@ static int az_head_tiled(const void* x, const float* w, const float* bias, void*
     if (val_stride == 0) val_stride = nval * S * S;
     if (pol_stride < npol * S * S || val_stride < nval * S * S) return AZSP_EINVAL;
     if (boards == 0) return AZSP_OK;
-    const int rc = azb::launch_head_tiled(x, w, bias, pol, val, (long long)boards, S, C, npol, nval, pol_stride, val_stride, stream, f16);
-    return rc == 0 ? AZSP_OK : (rc > 0 ? AZSP_EINVAL : AZSP_EDEVICE);
+    return az_rc(azb::launch_head_tiled(x, w, bias, pol, val, (long long)boards, S, C, npol, nval, pol_stride, val_stride, stream, f16));
 }
 int azsp_head_tiled(const void* x, const float* w, const float* bias, void* pol, void* val, int64_t boards, int32_t S, int32_t C, int32_t npol,
                     int32_t nval, int32_t pol_stride, int32_t val_stride, void* stream) {
@@ -1295,8 +1278,7 @@ static int az_fc_heads(const void* pol, const void* val, const void* wp, const f
     if (!pol || !val || !wp || !bp || !w1 || !b1 || !w2 || !priors || !values || boards < 0 || ks1 < 1 || ks2 < 1 || A < 1 || F < 1) return AZSP_EINVAL;
     if (boards == 0) return AZSP_OK;
     azb::FcHeadsArgs a = {pol, val, wp, w1, bp, b1, w2, b2, priors, values, (long long)boards, ks1, ks2, A, F, f16};
-    const int rc = azb::launch_fc_heads(a, stream);
-    return rc == 0 ? AZSP_OK : (rc > 0 ? AZSP_EINVAL : AZSP_EDEVICE);
+    return az_rc(azb::launch_fc_heads(a, stream));
 }
 int azsp_fc_heads(const void* pol, const void* val, const void* wp, const float* bp, int32_t ks1, const void* w1, const float* b1, int32_t ks2,
                   const float* w2, float b2, float* priors, float* values, int64_t boards, int32_t A, int32_t F, void* stream) {

@@ -1,6 +1,7 @@
 """A/B of the 19x19 x 256 tower convolution (BASELINE C5's dominant kernel) on the same box: the one-pass kernel (round 6,
-k_conv3x3_op19) against rounds 2-5's two-launch scheme (k_conv3x3_hb19, selected with AZSP_CONV19_TWO_LAUNCH=1 -- the library reads
-the switch once per process, so each variant runs in its own process).  Post-ReLU-like activations (half zeros), alternating plain /
+k_conv3x3_op19q) against rounds 2-5's two-launch scheme (k_conv3x3_hb19, selected with AZSP_CONV19_TWO_LAUNCH=1 -- the library reads
+the switch once per process, so each variant runs in its own process; a one-pass kernel is timed against an earlier build of itself by
+loading that build as a second library, see tools/split_prev_ab.py).  Post-ReLU-like activations (half zeros), alternating plain /
 residual layers like the forward.  usage: python tools/conv19_ab.py [boards]   (no argument: both variants, as sub-processes)"""
 import ctypes
 import os
@@ -59,9 +60,8 @@ if __name__ == "__main__":
         one(B)
     else:
         for rep in range(2):
-            variants = [("one pass (k_conv3x3_op19)" + (f", variant {v}" if v else ""), ({"AZSP_OP19_VARIANT": v} if v else {})) for v in os.environ.get("CONV19_AB_VARIANTS", "").split(",")]
-            for label, extra in variants + [("two launches (k_conv3x3_hb19)", {"AZSP_CONV19_TWO_LAUNCH": "1"})]:
+            for label, extra in (("one pass (k_conv3x3_op19q)", {}), ("two launches (k_conv3x3_hb19)", {"AZSP_CONV19_TWO_LAUNCH": "1"})):
                 print(f"{label}, {B} boards, run {rep}:", flush=True)
-                env = {k: v for k, v in os.environ.items() if k not in ("AZSP_CONV19_TWO_LAUNCH", "AZSP_OP19_VARIANT")}
+                env = {k: v for k, v in os.environ.items() if k != "AZSP_CONV19_TWO_LAUNCH"}
                 env.update(CONV19_AB_CHILD="1", **extra)
                 subprocess.run([sys.executable, os.path.abspath(__file__), str(B)], env=env, check=False)
