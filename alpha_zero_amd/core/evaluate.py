@@ -7,6 +7,7 @@
   * maybe_adjust_resign_threshold       core/pipeline.py:656-670
   * ResignController                    the learner's false-positive bookkeeping, core/pipeline.py:519-553
 Every search runs in the HIP engine through `uct_search` / `parallel_uct_search` (core/mcts_v2.py of this package)."""
+import itertools
 import math
 from typing import Iterable
 
@@ -105,71 +106,53 @@ class DeviceEvaluator:
 
     POLL_EVERY = 32  # leaf batches between two polls of the fp32-class evaluator's range record (a poll synchronises the stream)
     MAX_GRAPHS = 8   # captured forwards kept (one per engine buffer set and evaluator state)
+    _slot_ids = itertools.count()
 
     def __init__(self, inference_net, use_graph=True):
         self.inf = inference_net
         self.use_graph = use_graph
         self._calls = 0
-        self._graphs = {}
+        self._graphs = {}  # (buffers, InferenceNet.capture_state()) -> (hipGraph, the scratch slot of the network it replays into)
 
     @property
     def in_channels(self):
         """Observation planes the wrapped network takes (2 * num_stack + 1); the searches check it against the env."""
         return getattr(self.inf, "in_channels", None)
 
-    def _forward(self, x, priors_out=None, values_out=None):
-        if hasattr(self.inf, "forward_planes"):
-            return self.inf.forward_planes(x, priors_out, values_out)
-        return self.inf(x, priors_out, values_out) if priors_out is not None else self.inf(x)
-
     def _poll(self, x):
         self._calls += 1
-        if self._calls % self.POLL_EVERY == 0 and hasattr(self.inf, "poll_range"):
+        if self._calls % self.POLL_EVERY == 0:
             self.inf.poll_range(x)  # never silent, never left clamping: warn + rescale (InferenceNet.poll_range)
 
     def device_eval(self, x):
-        import torch
-
-        with torch.no_grad():
-            pri, v = self._forward(x)
+        pri, v = self.inf.forward_planes(x)  # (private copies of slot 3's output buffers)
         self._poll(x)
         return pri.float(), v.float()
-
-    def _state_key(self):
-        i = self.inf  # everything a captured forward bakes in besides the (in-place updated) weight tensors
-        return (id(i), getattr(i, "act_shift", 0), getattr(i, "act_calibrated", True), getattr(i, "split_fallback_reason", None),
-                getattr(i, "use_split_tower", None), getattr(i, "use_fused_block", None))
 
     def device_eval_into(self, x, priors_out, values_out):
         """The evaluator between an engine's own tensors: x = its feature rows, outputs written in place into its priors / values (fp32).
         On a HIP device the forward is replayed from a hipGraph captured per (buffers, evaluator state): a batch-1 forward of the drop-in
         searches is ~14 launches of a few microseconds each, i.e. launch-bound from Python (core/mcts_v2.py _simulate_on_device).  A change
-        of the evaluator's state (activation scale, fallback to the library, kernel switches) drops the capture."""
-        import torch
-
+        of the evaluator's state (InferenceNet.capture_state: activation scale, fallback to the library, kernel switches) leaves the
+        capture unused.  Every captured forward owns a scratch slot of the network: no other forward, of whatever batch size, can free
+        the buffers it replays into, and the slot is released with the graph."""
         if not (self.use_graph and x.is_cuda):
-            with torch.no_grad():
-                self._forward(x, priors_out, values_out)
+            self.inf.forward_planes(x, priors_out, values_out)
             self._poll(x)
             return
-        key = (x.data_ptr(), tuple(x.shape), x.dtype, priors_out.data_ptr(), values_out.data_ptr(), self._state_key())
-        g = self._graphs.get(key)
+        key = (x.data_ptr(), tuple(x.shape), x.dtype, priors_out.data_ptr(), values_out.data_ptr())
+        g, _ = self._graphs.get(key + (self.inf.capture_state(),), (None, None))
         if g is None:
-            with torch.no_grad():
-                side = torch.cuda.Stream(x.device)
-                side.wait_stream(torch.cuda.current_stream(x.device))
-                with torch.cuda.stream(side):
-                    for _ in range(2):  # eager first: calibration of the fp32-class activation scale, scratch buffers, library kernel choice
-                        self._forward(x, priors_out, values_out)
-                torch.cuda.current_stream(x.device).wait_stream(side)
-                torch.cuda.synchronize(x.device)
-                key = key[:-1] + (self._state_key(),)  # (the eager calls may have calibrated the scale or given the split kernels up)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._forward(x, priors_out, values_out)
-            if len(self._graphs) >= self.MAX_GRAPHS:
-                self._graphs.clear()
-            self._graphs[key] = g
+            from .network import capture_graph
+
+            slot = ("DeviceEvaluator", next(self._slot_ids))
+            # 2 eager calls first: calibration of the fp32-class activation scale, scratch buffers, library kernel choice
+            g = capture_graph(lambda: self.inf.forward_planes(x, priors_out, values_out, slot), x.device, 2)
+            if len(self._graphs) >= self.MAX_GRAPHS:  # full: start over
+                while self._graphs:
+                    self.inf.release_slot(self._graphs.popitem()[1][1])  # the graph goes, and in the same statement its slot
+            # (keyed by the state AFTER the eager calls: they may have calibrated the scale or given the split kernels up)
+            self._graphs[key + (self.inf.capture_state(),)] = (g, slot)
         g.replay()
         self._poll(x)
 

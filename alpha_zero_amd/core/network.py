@@ -132,6 +132,23 @@ def _ck(rc, what):
         raise RuntimeError(f"{what} failed with code {rc}")
 
 
+def capture_graph(fn, device, warmups):
+    """fn() as a replayable hipGraph.  `warmups` eager calls on a side stream come first -- whatever cannot be captured happens there
+    (calibration of the fp32-class activation scale, scratch allocation, the library's kernel choice) -- then the device is
+    synchronised and one more call is captured.  The one capture protocol of SelfPlayActor and DeviceEvaluator."""
+    side = torch.cuda.Stream(device)
+    side.wait_stream(torch.cuda.current_stream(device))
+    with torch.cuda.stream(side):
+        for _ in range(warmups):
+            fn()
+    torch.cuda.current_stream(device).wait_stream(side)
+    torch.cuda.synchronize(device)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        fn()
+    return g
+
+
 # widening multiplies the tower's FLOPs by (w / f)^2; the hand-written kernels are 4.5 - 5x the library's fp32 convolutions (measured: 40 -> 64 =
 # 2.56x the FLOPs is still 1.7x faster than the library at 40), so anything beyond 4x the FLOPs is left to the library path
 MAX_WIDEN_FLOPS_RATIO = 4.0
@@ -353,17 +370,25 @@ class InferenceNet(nn.Module):
 
     def _scratch(self, kind, slot, key, make):
         """Scratch memory of one `kind` ('split' | 'tiled' | 'head') per `slot`: callers whose forwards must not share scratch use
-        different slots (slot 0: the engine-facing forward, the one SelfPlayActor captures in a hipGraph -- its buffers must never be
-        freed by another caller of the same InferenceNet; slot 3: every other call -- evaluation games, drop-in eval_func wrappers,
-        tests; slots 1-2: the half-batch experiment of tools/overlap_actor.py).  A slot holds one `key` (size, device) at a time: a
-        call with another key frees the slot's entry before make() allocates the new one."""
+        different slots, and every forward NAMES its slot (none is inferred from its other arguments).  Slot 0: SelfPlayActor's
+        engine-facing forward, the one it captures in a hipGraph -- nobody else passes 0, so no other caller of the same InferenceNet
+        can free its buffers; slot 3, the default: every eager call -- evaluation games, drop-in eval_func wrappers, tests; slots
+        1-2: the half-batch experiment of tools/overlap_actor.py; any other hashable: one captured forward each of a DeviceEvaluator,
+        which returns it with release_slot when it drops the graph.  A slot holds one `key` (size, device) at a time: a call with
+        another key frees the slot's entry before make() allocates the new one -- so a slot a captured graph replays into must see
+        one key only."""
         if self._scratch_cache.get((kind, slot), (key,))[0] != key:
             del self._scratch_cache[(kind, slot)]
         if (kind, slot) not in self._scratch_cache:
             self._scratch_cache[(kind, slot)] = (key, make())
         return self._scratch_cache[(kind, slot)][1]
 
-    def _split_buffers(self, B, S, C, device, slot=0, board_size=None):
+    def release_slot(self, slot):
+        """Frees the scratch memory of `slot` (every kind); the owner of a captured forward calls this when it drops the graph."""
+        for k in [k for k in self._scratch_cache if k[1] == slot]:
+            del self._scratch_cache[k]
+
+    def _split_buffers(self, B, S, C, device, slot, board_size=None):
         """[three rotating tower buffers, feature buffer, priors, values] of the split-precision evaluator.  The stem's feature buffer is
         allocated only for callers that hand over fp32 planes (board_size given), sized with the BOARD (13 at Gomoku, not the 17 of the
         tower planes); the engine-facing forward passes the engine's own AZSP_FEAT_F16_SPLIT tensor and never allocates it."""
@@ -377,14 +402,12 @@ class InferenceNet(nn.Module):
         return ent
 
     @torch.no_grad()
-    def forward_split(self, planes, priors_out=None, values_out=None, slot=None, split_features=None, probe=None):
+    def forward_split(self, planes, priors_out=None, values_out=None, slot=3, split_features=None, probe=None):
         """planes: observation planes [B,17,N,N] fp32, contiguous NCHW (the engine's AZSP_FEAT_F32 features) -- or, with
         split_features = (rows, board_size), the engine's AZSP_FEAT_F16_SPLIT tensor itself (the stem's input layout: no conversion
         launch).  The whole evaluator at the reference's precision class (pipeline.py:91-123 evaluates in fp32) on hand-written kernels.
-        slot: scratch buffers to use (see _scratch); None = 0 when the outputs go to caller tensors (the engine's forward), 3 otherwise.
+        slot: scratch buffers to use (see _scratch).
         probe: optional callback(buffer, B) after the stem and after every tower convolution (calibrate_activation_scale)."""
-        if slot is None:
-            slot = 0 if priors_out is not None else 3
         if not self.act_calibrated and probe is None and planes.is_cuda and not torch.cuda.is_current_stream_capturing():
             self.calibrate_activation_scale(planes, split_features=split_features, slot=slot)
             if self.split_fallback_reason:  # the calibration gave the fp32-class kernels up for this network: library fp32 convolutions
@@ -439,30 +462,55 @@ class InferenceNet(nn.Module):
             _ck(self.binding.dll.azsp_split_range_read(rec, ctypes.byref(ev), ctypes.byref(mx), int(bool(reset)), stream), "azsp_split_range_read")
         return int(ev.value), float(mx.value)
 
+    def read_range(self):
+        """(events, max_abs) of this network's range record since the last read, and resets it -- (0, 0.0) at once, without touching the
+        device, unless the split-precision kernels are live: an fp32 network with a binding, use_split_tower, no fallback reason and
+        its record on the device.  Otherwise synchronises the stream (split_range_status)."""
+        live = (self.dtype == torch.float32 and self.binding is not None and self.use_split_tower and not self.split_fallback_reason
+                and self.range_rec.is_cuda)
+        return self.split_range_status(reset=True) if live else (0, 0.0)
+
+    def repair_range(self, ev, mx, planes=None, split_features=None, slot=3):
+        """The one answer to a range event (`ev` clamped lanes, the largest |v| = `mx` in the kernels' scaled units, as read_range
+        returns them): the evaluator is never left clamping.  Given the batch that was just evaluated -- NCHW planes, or with
+        split_features = (rows, board_size) the engine's AZSP_FEAT_F16_SPLIT tensor -- and the whole split evaluator running, the
+        activation scale is raised by at least 4x and the network re-calibrated on that batch (in `slot`), which may hand it to the
+        library's fp32 convolutions (split_fallback_reason).  Otherwise (the split tower behind a library stem / heads, or no batch:
+        no layer-by-layer calibration pass exists) the scale is raised by what the record shows -- a lower bound: clamped values
+        hide the true maximum -- + 16x, at most to MAX_ACT_SHIFT.  Warns once, with the old and the new scale.  Returns whether
+        anything was done (False: the scale was at its limit already); a forward captured before must then be captured again unless
+        capture_state() is what it was."""
+        old = self.act_shift
+        board = split_features[1] if split_features is not None else None if planes is None else planes.shape[2]
+        acted = planes is not None and self.supports_split_features(board, planes.device)
+        if acted:
+            self.set_act_shift(min(self.MAX_ACT_SHIFT, old + 2))
+            self.calibrate_activation_scale(planes if split_features is not None else planes.float().contiguous(), split_features=split_features, slot=slot)
+        else:
+            k = min(self.MAX_ACT_SHIFT, old + max(2, math.ceil(math.log2(max(mx, F16_MAX) / F16_MAX)) + 4))
+            acted = k > old
+            if acted:
+                self.set_act_shift(k)
+        what = (f"library fp32 convolutions from now on ({self.split_fallback_reason})" if self.split_fallback_reason
+                else f"activation scale raised 2^-{old} -> 2^-{self.act_shift}" if self.act_shift > old
+                else f"the activation scale is at its limit (2^-{old}): evaluate this network with use_split_tower = False")
+        warnings.warn(f"alpha_zero_amd: the fp32-class evaluator clamped {ev} activation lanes beyond f16's range (largest |v| = "
+                      f"{mx * 2.0 ** old:.6g}); the reference's fp32 network would have carried them -- {what}", RuntimeWarning, stacklevel=3)
+        return acted
+
     def poll_range(self, planes=None):
         """For callers that drive the InferenceNet themselves (evaluation games, drop-in eval_func wrappers: no SelfPlayActor polls for
-        them): reads and resets this network's range record; on an event it warns, raises the activation scale and -- given the batch
-        that was just evaluated -- re-calibrates on it.  Returns the number of events.  Synchronises the stream."""
-        if self.dtype != torch.float32 or not hasattr(self, "range_rec") or not self.range_rec.is_cuda or self.split_fallback_reason:
-            return 0
-        ev, mx = self.split_range_status(reset=True)
+        them): read_range, and on an event repair_range -- given the batch that was just evaluated, a re-calibration on it.  Returns
+        the number of events."""
+        ev, mx = self.read_range()
         if ev:
-            old = self.act_shift
-            if planes is not None and self.supports_split_features(planes.shape[2], planes.device):
-                self.set_act_shift(min(self.MAX_ACT_SHIFT, old + 2))
-                self.calibrate_activation_scale(planes.float().contiguous())
-            else:
-                # the split tower behind a library stem / heads (or no batch given): no layer-by-layer calibration pass -- raise the scale
-                # by what the record shows (a lower bound: clamped values hide the true maximum) + 16x, as SelfPlayActor does
-                k = min(self.MAX_ACT_SHIFT, old + max(2, math.ceil(math.log2(max(mx, F16_MAX) / F16_MAX)) + 4))
-                if k > old:
-                    self.set_act_shift(k)
-            what = (f"library fp32 convolutions from now on ({self.split_fallback_reason})" if self.split_fallback_reason
-                    else f"activation scale 2^-{old} -> 2^-{self.act_shift}" if self.act_shift > old
-                    else f"the activation scale is at its limit (2^-{old}): evaluate this network with use_split_tower = False")
-            warnings.warn(f"alpha_zero_amd: the fp32-class evaluator clamped {ev} activation lanes beyond f16's range (largest |v| = "
-                          f"{mx * 2.0 ** old:.6g}); {what}", RuntimeWarning, stacklevel=2)
+            self.repair_range(ev, mx, planes)
         return ev
+
+    def capture_state(self):
+        """Everything a captured forward of this network bakes in besides the (in-place updated) weight tensors: a hipGraph captured
+        under another capture_state() must not be replayed."""
+        return (id(self), self.act_shift, self.act_calibrated, self.split_fallback_reason, self.use_split_tower, self.use_fused_block)
 
     # -- range safety: exact power-of-two activation scale -------------------------------------------------------------------
     MAX_ACT_SHIFT = 9   # beyond 2^-9 the scaled stem weights lose fp32-class accuracy (their hi halves become f16 subnormals)
@@ -546,6 +594,22 @@ class InferenceNet(nn.Module):
             planes = planes[: B * 2 * 32 * n * n].view(B, 2, 4, n * n, 8)[:, 0].permute(0, 1, 3, 2).reshape(B, 32, n, n)[:, :cin].float()
         return self.forward(planes, priors_out, values_out)
 
+    @torch.no_grad()
+    def forward_rows(self, feat, layout, rows, board_size, priors_out=None, values_out=None, slot=3):
+        """The forward on `rows` leaf rows as an engine wrote them into `feat`, by the engine's feature `layout`: 'tiled' (AZSP_FEAT_BF16_TILED /
+        _F16_TILED -> forward_tiled), 'split' (AZSP_FEAT_F16_SPLIT -> forward_split; the library's fp32 convolutions once the
+        fp32-class kernels were given up for this network) or 'planes' (NCHW -> forward).  `slot`: see _scratch."""
+        if layout == "tiled":
+            return self.forward_tiled(feat, rows, board_size, priors_out, values_out, slot)
+        if layout == "planes":
+            return self.forward(feat, priors_out, values_out, slot)
+        if self.split_fallback_reason:
+            return self._forward_after_split_fallback(feat, priors_out, values_out, (rows, board_size))
+        if not self.supports_split_features(board_size, feat.device):  # (someone switched the split kernels off on the live InferenceNet)
+            raise RuntimeError("the engine writes the split-precision stem's input layout; build the actor with use_split_evaluator=False "
+                               "to evaluate an fp32 network on the library")
+        return self.forward_split(feat, priors_out, values_out, slot, split_features=(rows, board_size))
+
     def _blocks_split(self, a, m, o, B, S, C, st, rr=None, probe=None):
         """All residual blocks on split-layout buffers; returns the buffer holding the tower output."""
         dll = self.binding.dll
@@ -588,7 +652,7 @@ class InferenceNet(nn.Module):
             y.add_(res)
         return F.relu_(y)
 
-    def _tiled_buffers(self, B, S, C, device, slot=0):
+    def _tiled_buffers(self, B, S, C, device, slot):
         """Three rotating tower buffers (block input, middle, block output) of the tiled kernels."""
         n = self.binding.dll.azsp_tiled_bytes(B, S, C) // 2
         bufs = self._scratch("tiled", slot, (n, str(device)), lambda: [torch.zeros(n, dtype=self.pack_dtype, device=device) for _ in range(3)])
@@ -596,7 +660,7 @@ class InferenceNet(nn.Module):
             self._tiled = bufs  # (bench.py replays the tower on the activations of the last full-batch forward)
         return bufs
 
-    def _head_buffers(self, B, k1, k2, device, slot=0):
+    def _head_buffers(self, B, k1, k2, device, slot):
         return self._scratch("head", slot, (B, str(device)), lambda: (
             torch.zeros((B + 1, k1), dtype=self.pack_dtype, device=device), torch.zeros((B + 1, k2), dtype=self.pack_dtype, device=device),
             torch.empty((B, self.num_actions), dtype=torch.float32, device=device), torch.empty((B,), dtype=torch.float32, device=device)))
@@ -645,7 +709,7 @@ class InferenceNet(nn.Module):
         return self._path(board_size, device)[0] == "tiled"
 
     @torch.no_grad()
-    def forward_tiled(self, feat, rows, board_size, priors_out=None, values_out=None, slot=0):
+    def forward_tiled(self, feat, rows, board_size, priors_out=None, values_out=None, slot=3):
         """feat: the engine's AZSP_FEAT_BF16_TILED feature tensor for `rows` leaf positions (or a tile-aligned slice of it).  Stem,
         tower, the 1x1 head convolutions and the fully connected layers run on the tiled layout in hand-written kernels.  `slot`
         selects the scratch buffers (see _scratch)."""
@@ -673,19 +737,19 @@ class InferenceNet(nn.Module):
         return pri, v
 
     @torch.no_grad()
-    def forward_planes(self, x, priors_out=None, values_out=None):
+    def forward_planes(self, x, priors_out=None, values_out=None, slot=3):
         """x: observation planes [B,17,N,N] (any dtype, on the evaluator's device).  Runs the whole evaluator on the hand-written kernels
         when this network / board has them (the planes are padded to 32 channels and converted to the tiled feature layout on the
         device: azsp_tile_layout), otherwise `forward`.  Used where leaf rows arrive as NCHW planes: evaluation games
         (core/evaluate.py DeviceEvaluator), drop-in eval_func wrappers."""
         B, _, n, _ = x.shape
         if self._path(n, x.device)[0] != "tiled":
-            return self.forward(x, priors_out, values_out)
+            return self.forward(x, priors_out, values_out, slot)
         xb = torch.zeros((B, 32, n, n), dtype=self.pack_dtype, device=x.device).contiguous(memory_format=torch.channels_last)
         xb[:, : x.shape[1]] = x.to(self.pack_dtype)
         feat = torch.zeros(self.binding.dll.azsp_tiled_bytes(B, n, 32) // 2, dtype=self.pack_dtype, device=x.device)
         _ck(self.binding.dll.azsp_tile_layout(xb.data_ptr(), feat.data_ptr(), B, n, 32, 1, _stream(x)), "azsp_tile_layout")
-        pri, v = self.forward_tiled(feat, B, n, priors_out, values_out, slot=3)
+        pri, v = self.forward_tiled(feat, B, n, priors_out, values_out, slot)
         return (pri, v) if priors_out is not None else (pri.clone(), v.clone())  # the slot's output buffers are reused by the next call
 
     def _fc_heads(self, pol, val, priors_out, values_out):
@@ -700,12 +764,12 @@ class InferenceNet(nn.Module):
             return priors_out, values_out
         return pri, v
 
-    def _tower_tiled(self, x):
+    def _tower_tiled(self, x, slot=3):
         """The whole residual tower on the tiled activation layout (include/azsp.h: azsp_tile_layout /
         azsp_conv3x3_tiled): the weight-stationary MFMA kernel, activations converted once on entry and once on exit."""
         dll, st = self.binding.dll, _stream(x)
         B, C, S = x.shape[0], x.shape[1], x.shape[2]
-        a, m, o = self._tiled_buffers(B, S, C, x.device)
+        a, m, o = self._tiled_buffers(B, S, C, x.device, slot)
         _ck(dll.azsp_tile_layout(x.data_ptr(), a.data_ptr(), B, S, C, 1, st), "azsp_tile_layout")
         a = self._blocks_tiled(a, m, o, B, S, C, st)
         _ck(dll.azsp_tile_layout(a.data_ptr(), x.data_ptr(), B, S, C, 0, st), "azsp_tile_layout")
@@ -730,19 +794,19 @@ class InferenceNet(nn.Module):
         return x
 
     @torch.no_grad()
-    def forward(self, x, priors_out=None, values_out=None):
-        """x: [B,17,N,N] any dtype -> (priors fp32 [B,A], values fp32 [B])."""
+    def forward(self, x, priors_out=None, values_out=None, slot=3):
+        """x: [B,17,N,N] any dtype -> (priors fp32 [B,A], values fp32 [B]).  `slot`: scratch of the hand-written towers (see _scratch)."""
         path = self._path(x.shape[2], x.device)[0]
         if path == "split":
-            return self.forward_split(x.float().contiguous(), priors_out, values_out)
+            return self.forward_split(x.float().contiguous(), priors_out, values_out, slot)
         x = x.to(self.dtype).contiguous(memory_format=self.mf)
         x = self._epilogue(F.conv2d(x, self.w[0], None, padding=self.stem_pad), self.b[0])
         # the hand-written towers take square channels-last activations of their own element type
         tower_ok = x.shape[2] == x.shape[3] and x.is_contiguous(memory_format=torch.channels_last)
         if tower_ok and path in ("tiled", "tiled_tower") and x.dtype == torch.bfloat16:
-            x = self._tower_tiled(x)
+            x = self._tower_tiled(x, slot)
         elif tower_ok and path == "split_tower" and x.dtype == torch.float32:
-            x = self._tower_split(x, slot=0 if priors_out is not None else 3)
+            x = self._tower_split(x, slot)
         else:
             for i in range(self.n_blocks):
                 y = self._conv(x, 2 * i)

@@ -40,12 +40,13 @@ def game_stats_from_row(row, game: str, komi: float = 7.5, resign_threshold: flo
 # Batched self-play actor
 # =====================================================================================================
 import time  # noqa: E402
+import warnings  # noqa: E402
 
 import torch  # noqa: E402
 
 from .. import _abi  # noqa: E402
 from .engine import Engine, EngineConfig  # noqa: E402
-from .network import AlphaZeroNet, InferenceNet, widen_for_kernels  # noqa: E402
+from .network import AlphaZeroNet, InferenceNet, capture_graph, widen_for_kernels  # noqa: E402
 from .replay import Transition  # noqa: E402
 
 def check_input_channels(network, num_stack):
@@ -135,16 +136,12 @@ class SelfPlayActor:
         self.auto_widen = bool(auto_widen)
         self.board_size = board_size
         wnet, self._widen_note = widen_for_kernels(network, board_size, net_dtype) if self.auto_widen else (network, "")
-        probe = InferenceNet(wnet, dtype=net_dtype, binding=self.binding if self.device.type == "cuda" else None)
-        probe.use_split_tower = self.use_split_evaluator
-        self.tiled_features = probe.supports_tiled_features(board_size, self.device) if tiled_features is None else bool(tiled_features)
+        self.infer = self._inference_net(wnet)  # decides the engine's feature layout; moved to the device as the first evaluator below
+        self.tiled_features = self.infer.supports_tiled_features(board_size, self.device) if tiled_features is None else bool(tiled_features)
         # fp32-class evaluator: the engine writes the stem's input layout itself (AZSP_FEAT_F16_SPLIT; 0 / 1 planes are exact f16 values)
-        self.split_features = tiled_features is None and not self.tiled_features and probe.supports_split_features(board_size, self.device)
-        self.evaluator_path = (probe.evaluator_path(board_size, self.device) if self.tiled_features or tiled_features is None else
-                               "library stem (tiled features disabled by the caller)") + self._widen_note
+        self.split_features = tiled_features is None and not self.tiled_features and self.infer.supports_split_features(board_size, self.device)
+        self._library_stem = tiled_features is not None and not self.tiled_features  # (NCHW planes although the tiled kernels exist)
         if self.device.type == "cuda" and "hand-written" not in self.evaluator_path:
-            import warnings
-
             warnings.warn(f"alpha_zero_amd: evaluator falls back to {self.evaluator_path}", RuntimeWarning, stacklevel=2)
         self.cfg = EngineConfig(
             game=game, board_size=board_size, num_games=num_games, num_parallel=num_parallel, num_simulations=num_simulations,
@@ -171,22 +168,35 @@ class SelfPlayActor:
         self.clamp_window = ClampWindow(num_games)
         self.drop_clamped_games, self.clamped_games, self.last_harvest_clamped = False, 0, np.zeros(0, dtype=bool)
         self.drop_straddling_games = False
-        self.set_network(network, training_steps)
+        self._install(self.infer, training_steps)
 
     # -- weights ---------------------------------------------------------------------------------------
+    def _inference_net(self, network):
+        """The evaluator of `network`, still on the host (what it supports on self.device does not depend on where it lives)."""
+        inf = InferenceNet(network, dtype=self.net_dtype, binding=self.binding if self.device.type == "cuda" else None)
+        inf.use_split_tower = self.use_split_evaluator
+        return inf
+
+    def _install(self, infer, training_steps):
+        self.infer, self.training_steps, self._graph = infer.to(self.device), training_steps, None
+        self.engine.set_actor_state(self.resign_threshold, training_steps)  # games that start from now on carry this tag
+
     def set_network(self, network: AlphaZeroNet, training_steps=0):
         """Checkpoint hot-swap (pipeline.py:232-239): new weights take effect at the next round."""
         check_input_channels(network, self.num_stack)
         if self.auto_widen:
             network, _ = widen_for_kernels(network, self.board_size, self.net_dtype)
-        self.infer = InferenceNet(network, dtype=self.net_dtype, binding=self.binding if self.device.type == "cuda" else None).to(self.device)
-        self.infer.use_split_tower = self.use_split_evaluator
-        self.training_steps = training_steps
-        self.engine.set_actor_state(self.resign_threshold, training_steps)  # games that start from now on carry this tag
-        self._graph = None
-        if getattr(self, "rounds", 0) and "library stem (tiled features disabled" not in self.evaluator_path:
-            # a hot-swapped network starts uncalibrated at shift 0: drop the previous network's "activations carried x 2^-k" note
-            self.evaluator_path = self.infer.evaluator_path(self.board_size, self.device) + self._widen_note
+        self._install(self._inference_net(network), training_steps)
+
+    @property
+    def evaluator_path(self):
+        """Which kernels this actor's forward runs on, derived from the live InferenceNet: its evaluator_path (or the library stem the
+        caller asked for), the widen note, and the activation shift its calibration chose (a hot-swapped network starts without one)."""
+        inf = self.infer
+        base = "library stem (tiled features disabled by the caller)" if self._library_stem else inf.evaluator_path(self.board_size, self.device)
+        shift = (f"; activations carried x 2^-{inf.act_shift} (exact rescaling, calibrated max |v| = {inf.act_max_abs:.4g})"
+                 if self.split_features and inf.act_shift and not inf.split_fallback_reason else "")
+        return base + self._widen_note + shift
 
     def set_resign_threshold(self, resign_threshold):
         """var_resign_threshold as the reference actor reads it before EVERY game (pipeline.py:241-242): games that start after this
@@ -195,53 +205,23 @@ class SelfPlayActor:
         self.engine.set_actor_state(self.resign_threshold, self.training_steps)
 
     def _forward(self):
+        """The forward on the leaf rows the engine has just written, in scratch slot 0 (this actor's own: InferenceNet._scratch)."""
         e = self.engine
-        if e.features_tiled:
-            self.infer.forward_tiled(e.features, e.rows, e.N, e.priors, e.values)
-        elif e.features_split:
-            if self.infer.split_fallback_reason:  # the fp32-class kernels were given up for this network
-                self.infer._forward_after_split_fallback(e.features, e.priors, e.values, (e.rows, e.N))
-                return
-            if not self.infer.supports_split_features(e.N, self.device):  # (someone switched the split kernels off on the live InferenceNet)
-                raise RuntimeError("the engine writes the split-precision stem's input layout; build the actor with use_split_evaluator=False "
-                                   "to evaluate an fp32 network on the library")
-            self.infer.forward_split(e.features, e.priors, e.values, split_features=(e.rows, e.N))
-        else:
-            self.infer(e.features, e.priors, e.values)
+        self.infer.forward_rows(e.features, "tiled" if e.features_tiled else "split" if e.features_split else "planes", e.rows, e.N,
+                                e.priors, e.values, slot=0)
 
     def _calibrate(self):
         """fp32-class evaluator: one calibration pass on the leaf batch the engine has just written (InferenceNet.calibrate_activation_scale)
         fixes the power-of-two activation scale of this network BEFORE its first forward is used (and before a hipGraph is captured)."""
         e, inf = self.engine, self.infer
-        if not (e.features_split and not inf.act_calibrated and inf.supports_split_features(e.N, self.device)):
-            return
-        inf.calibrate_activation_scale(e.features, split_features=(e.rows, e.N), slot=0)
-        self._note_evaluator_path()
+        if e.features_split and inf.supports_split_features(e.N, self.device):
+            inf.calibrate_activation_scale(e.features, split_features=(e.rows, e.N), slot=0)
+            self._announce_fallback()
 
-    def _note_evaluator_path(self):
-        inf = self.infer
-        if inf.split_fallback_reason:
-            import warnings
-
-            self.evaluator_path = inf.evaluator_path(self.board_size, self.device) + self._widen_note
+    def _announce_fallback(self):
+        if self.infer.split_fallback_reason:  # the calibration gave the fp32-class kernels up for this network
             warnings.warn(f"alpha_zero_amd: evaluator falls back to {self.evaluator_path}", RuntimeWarning, stacklevel=3)
             self._graph = None
-        elif inf.act_shift and "activations carried" not in self.evaluator_path:
-            self.evaluator_path += f"; activations carried x 2^-{inf.act_shift} (exact rescaling, calibrated max |v| = {inf.act_max_abs:.4g})"
-
-    def _capture(self):
-        e = self.engine
-        s = torch.cuda.Stream(self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            for _ in range(3):  # let MIOpen pick its kernels before capture
-                self._forward()
-        torch.cuda.current_stream(self.device).wait_stream(s)
-        torch.cuda.synchronize(self.device)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self._forward()
-        self._graph = g
 
     # -- rounds ----------------------------------------------------------------------------------------
     def run_round(self, evs=None):
@@ -259,7 +239,7 @@ class SelfPlayActor:
             self._calibrate()
         if self.use_graph:
             if self._graph is None:
-                self._capture()
+                self._graph = capture_graph(self._forward, self.device, 3)  # (3 warm-ups: the library picks its kernels before the capture)
             self._graph.replay()
         else:
             self._forward()
@@ -297,45 +277,19 @@ class SelfPlayActor:
         the current leaf batch (a larger exact power-of-two activation scale), or, if the format cannot carry it, handed to the
         library's fp32 convolutions -- the actor never keeps playing on a clamping evaluator PAST THE POLL; what ran
         between the event and the poll is marked (ClampWindow: harvest() marks or drops those games)."""
-        inf = self.infer
-        if (self.device.type != "cuda" or self.net_dtype != torch.float32 or inf.binding is None or not inf.use_split_tower
-                or inf.split_fallback_reason or not hasattr(inf, "range_rec")):
-            return
-        ev, mx = inf.split_range_status(reset=True)
+        inf, e = self.infer, self.engine
+        ev, mx = inf.read_range()
         if not ev:
             return
-        import warnings
-
         self.range_events += ev
         self.range_max_abs = max(self.range_max_abs, mx * 2.0 ** inf.act_shift)
-        old_shift = inf.act_shift
-        e = self.engine
         # every game that ran a round since the last clean poll is suspect: the ones in progress now + the finished ones not handed out yet
         self.clamp_window.on_event(e.status()[0][:, 5])
-        if e.features_split and inf.supports_split_features(e.N, self.device):
-            inf.act_calibrated = False
-            inf.set_act_shift(min(inf.MAX_ACT_SHIFT, old_shift + 2))  # at least 4x more room, then whatever the calibration asks for
-            inf.calibrate_activation_scale(e.features, split_features=(e.rows, e.N), slot=0)
+        batch = dict(planes=e.features, split_features=(e.rows, e.N)) if e.features_split else {}  # (the re-calibration takes the stem's own layout)
+        if inf.repair_range(ev, mx, slot=0, **batch):
             self.range_rescales += 1
-            self._note_evaluator_path()
-            what = (f"falls back to the library's fp32 convolutions ({inf.split_fallback_reason})" if inf.split_fallback_reason
-                    else f"activation scale raised 2^-{old_shift} -> 2^-{inf.act_shift}")
-        else:
-            # the split tower behind a library stem / heads (shapes without split stem or head kernels): no layer-by-layer calibration
-            # pass exists for it -- raise the scale by what the record shows (a lower bound: clamped values hide the true maximum) + 16x
-            import math
-
-            k = min(inf.MAX_ACT_SHIFT, old_shift + max(2, math.ceil(math.log2(max(mx, 65504.0) / 65504.0)) + 4))
-            if k > old_shift:
-                inf.set_act_shift(k)
-                self._graph = None  # (this path multiplies by 2^-k with a host constant: a captured graph holds the old one)
-                self.range_rescales += 1
-                what = f"activation scale raised 2^-{old_shift} -> 2^-{inf.act_shift}"
-            else:
-                what = "the scale is at its limit: evaluate this network with use_split_tower = False"
-        warnings.warn(f"alpha_zero_amd: the fp32-class evaluator clamped {ev} activation lanes beyond f16's range (largest |v| = "
-                      f"{mx * 2.0 ** old_shift:.6g}); the reference's fp32 network would have carried them -- {what}",
-                      RuntimeWarning, stacklevel=3)
+        self._graph = None  # re-captured after any repair: never a replay across a change of InferenceNet.capture_state()
+        self._announce_fallback()
 
     def harvest(self, with_moves=False):
         """Finished games as the reference actor emits them: [(game_seq: list[Transition], stats: dict)]

@@ -732,3 +732,40 @@ def test_evaluator_path_behind_a_library_stem_host_twin(dtype, path):
     library = f"library convolutions + azsp_bias_act epilogue (no hand-written kernel for 128 filters on 9x9, {dtype})"
     assert (inf.evaluator_path(9, "cuda"), inf.supports_tiled_features(9, "cuda"), inf.supports_split_features(9, "cuda")) == (
         _PATHS.get(path, library), False, False)
+
+
+def test_scratch_slots_are_named_by_the_caller_and_released_one_by_one_host_twin():
+    """InferenceNet._scratch: a forward uses the slot its caller names -- never one inferred from its other arguments -- so two forwards
+    with caller-supplied outputs and different row counts (a P = 1 and a P = 8 search on one evaluator) keep their buffers when they
+    run under different slots: the same memory afterwards, the same bits from the first forward again.  release_slot removes exactly
+    that slot's entries.  (In ONE slot the second row count frees the first entry: that is what a captured forward must never meet.)"""
+    import engine_util as eu
+
+    torch.manual_seed(9)
+    inf = InferenceNet(AlphaZeroNet((17, 9, 9), 82, 2, 64, 64).eval(), dtype=torch.float32, binding=eu.hosttwin_binding())
+    g = torch.Generator().manual_seed(10)
+    x1, x8 = ((torch.rand(b, 17, 9, 9, generator=g) > 0.6).float() for b in (1, 8))
+    out = lambda b: (torch.empty(b, 82), torch.empty(b))  # noqa: E731
+    ptrs = lambda slot: [t.data_ptr() for t in inf._scratch_cache[("split", slot)][1][0]]  # noqa: E731
+
+    p1, v1 = out(1)
+    inf.forward_split(x1, p1, v1, slot="one")
+    first = ptrs("one")
+    p8, v8 = out(8)
+    inf.forward_split(x8, p8, v8, slot="eight")
+    assert set(inf._scratch_cache) == {("split", "one"), ("split", "eight")} and ptrs("one") == first
+    eight = ptrs("eight")
+    p1b, v1b = out(1)
+    inf.forward_split(x1, p1b, v1b, slot="one")
+    assert torch.equal(p1b, p1) and torch.equal(v1b, v1) and ptrs("one") == first and ptrs("eight") == eight
+    p8b, v8b = out(8)
+    inf.forward_split(x8, p8b, v8b, slot="eight")
+    assert torch.equal(p8b, p8) and torch.equal(v8b, v8)
+    # outputs to caller tensors do not select a slot: without one it is 3, the eager callers' -- never 0, the actor's
+    inf.forward_split(x8, p8b, v8b)
+    inf.forward_split(x1)
+    assert ("split", 3) in inf._scratch_cache and ("split", 0) not in inf._scratch_cache and inf._scratch_cache[("split", 3)][0][0] == 1
+    inf.release_slot("one")
+    assert set(inf._scratch_cache) == {("split", "eight"), ("split", 3)} and ptrs("eight") == eight
+    inf.release_slot("eight"), inf.release_slot("never used")
+    assert set(inf._scratch_cache) == {("split", 3)}

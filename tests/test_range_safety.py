@@ -381,8 +381,44 @@ def test_loud_stem_weights_fall_back_to_the_library_on_one_fallback_reason_on_th
     assert inf.split_fallback_reason and shift == 0 and inf.act_shift == 0 and worst > 65504.0, (shift, worst)  # (a lower bound: saturated passes hide the true maximum)
     assert float(inf.stem_wsp.abs().max()) == 0.0 and "library fp32" in inf.evaluator_path(9, "cpu")
     inf.set_act_shift(0)  # idempotent, still no ValueError
-    p, v = inf._forward_after_split_fallback(x, None, None, None)
+    p, v = inf.forward_rows(x, "planes", 2, 9)
+    ps, vs = inf.forward_rows(eu.split_features(x), "split", 2, 9)  # the engine's own layout is unpacked for the library: the same forward
+    assert torch.equal(ps, p) and torch.equal(vs, v)
     with torch.no_grad():
         lg, vr = net(x)
     assert (p - torch.softmax(lg, -1)).abs().max().item() <= 1e-4 and (v - vr.squeeze(1)).abs().max().item() <= 1e-4
     assert bnd.dll.azsp_split_range_status(None, None, 1, None) == 0
+
+
+def test_range_repair_policy_on_a_made_up_event_on_the_host_twin():
+    """InferenceNet.repair_range, the one answer of actors and evaluators to a range event, driven with made-up events (reading the
+    record and acting on it are separate, so the record need not be on a device).  Without a batch there is no calibration pass: the
+    scale rises by ceil(log2(largest |v| / 65504)) + 4 bits, at most to MAX_ACT_SHIFT, where the network is reported as beyond the
+    kernels.  Every event gives ONE warning with the word "clamped", the count, the largest |v| in the network's units and the old
+    and the new scale."""
+    import engine_util as eu
+
+    torch.manual_seed(5)
+    inf = InferenceNet(AlphaZeroNet((17, 9, 9), 82, 2, 64, 64).eval(), dtype=torch.float32, binding=eu.hosttwin_binding())
+    assert inf.read_range() == (0, 0.0) and inf.poll_range() == 0  # the record is not on a device: a clean poll, nothing touched
+
+    def repair(ev, mx):
+        with warnings.catch_warnings(record=True) as w:
+            warnings.simplefilter("always")
+            acted = inf.repair_range(ev, mx)
+        assert len(w) == 1 and w[0].category is RuntimeWarning
+        return acted, str(w[0].message)
+
+    state = inf.capture_state()
+    acted, msg = repair(7, 1.0e6)  # ceil(log2(1e6 / 65504)) = 4, + 4 bits of headroom
+    assert acted and inf.act_shift == 8 and inf.capture_state() != state
+    assert "clamped 7 activation lanes" in msg and "largest |v| = 1e+06" in msg and "2^-0 -> 2^-8" in msg, msg
+    assert torch.equal(inf.b_sp[0], inf.b32[0] * 2.0 ** -8)  # (the shift is applied, not only noted)
+    inf.set_act_shift(3)
+    acted, msg = repair(2, 5 * 65504.0)  # 3 + 4 bits asked for, MAX_ACT_SHIFT caps them at 6; |v| is reported in the network's units
+    assert acted and inf.act_shift == inf.MAX_ACT_SHIFT == 9
+    assert "clamped 2 activation lanes" in msg and "largest |v| = 2.62016e+06" in msg and "2^-3 -> 2^-9" in msg, msg
+    state = inf.capture_state()
+    acted, msg = repair(1, 1.0e5)
+    assert not acted and inf.act_shift == 9 and inf.capture_state() == state
+    assert "clamped 1 activation lanes" in msg and "scale is at its limit (2^-9)" in msg and "use_split_tower = False" in msg, msg

@@ -76,7 +76,9 @@ def test_gpu_dropin_search_with_the_device_resident_product_evaluator_reproduces
     """uct_search / parallel_uct_search handed a DeviceEvaluator (core/evaluate.py) around the fp32-class hand-written evaluator with the
     reference's shipped checkpoint: the leaves stay on the device, the forward is replayed from a hipGraph between the engine's own
     tensors, the host polls the status a few times per move.  Statement: the same as for the host callback -- EVERY move of the
-    reference's recorded games identical (pi to 1e-6, same sampled move, |Q - ref| <= 1e-6), P = 1 with sub-tree reuse and P = 8."""
+    reference's recorded games identical (pi to 1e-6, same sampled move, |Q - ref| <= 1e-6), P = 1 with sub-tree reuse and P = 8.
+    The P = 1 game is played once more after the P = 8 one with the same evaluator: a captured P = 1 forward that is replayed then must
+    still own its scratch (every captured forward has a scratch slot of the network to itself: ADVICE r6 #1), so that leg is exact too."""
     from alpha_zero_amd import _lib
     from alpha_zero_amd.core.evaluate import DeviceEvaluator
     from alpha_zero_amd.core.network import InferenceNet, widen_network
@@ -84,12 +86,16 @@ def test_gpu_dropin_search_with_the_device_resident_product_evaluator_reproduces
     infsp = InferenceNet(widen_network(rc.load_shipped(), 64), dtype=torch.float32, binding=_lib.load()).cuda()
     for use_graph in (True, False):
         ev = DeviceEvaluator(infsp, use_graph=use_graph)
-        for name in ("gomoku13_ckpt200000_p1_s100", "gomoku13_ckpt200000_p8_s200"):
-            infsp._split = None
+        for leg, name in enumerate(("gomoku13_ckpt200000_p1_s100", "gomoku13_ckpt200000_p8_s200", "gomoku13_ckpt200000_p1_s100")):
+            infsp._split, captured = None, len(ev._graphs)
             recs, total = rc.run_golden("gpu", name, ev, teacher_forced=False)
-            assert infsp._split is not None, "the split-precision kernels did not run"
+            # (the third leg with graphs is all replays of the first leg's captures: no Python forward runs, nothing is captured anew)
+            replays_only = use_graph and leg == 2 and len(ev._graphs) == captured
+            assert infsp._split is not None or replays_only, "the split-precision kernels did not run"
             f = rc.summarize(recs, total)
-            assert f["moves_compared"] == f["moves_in_golden"] >= 40 and f["exact_moves"] == f["moves_compared"], (use_graph, name, f)
-            assert f["max_dpi"] <= 1e-6 and f["max_dq"] <= 1e-6 and f["max_dcq"] <= 1e-6, (use_graph, name, f)
+            assert f["moves_compared"] == f["moves_in_golden"] >= 40 and f["exact_moves"] == f["moves_compared"], (use_graph, leg, name, f)
+            assert f["max_dpi"] <= 1e-6 and f["max_dq"] <= 1e-6 and f["max_dcq"] <= 1e-6, (use_graph, leg, name, f)
+            for _, slot in ev._graphs.values():  # every cached graph replays into scratch the network still holds
+                assert ("split", slot) in infsp._scratch_cache, (use_graph, leg, name, slot)
         assert (len(ev._graphs) >= 1) == use_graph  # (one captured forward per engine buffer set)
     assert infsp.split_range_status(reset=True)[0] == 0
