@@ -7,6 +7,23 @@ GAME_GO, GAME_GOMOKU = 0, 1
 FEAT_I8, FEAT_F32, FEAT_BF16, FEAT_F16, FEAT_BF16_TILED, FEAT_F16_TILED, FEAT_F16_SPLIT = 0, 1, 2, 3, 4, 5, 6
 ST_NEED_ROOT, ST_SEARCH, ST_MOVE_DONE, ST_IDLE, ST_WAIT_BUF = 0, 1, 2, 3, 4
 
+# Columns of the engine's fixed-width rows: the enums of include/azsp.h without the AZSP_ prefix (tests/test_engine_host.py pins them).
+# status int32[G][STC_COUNT] + q float64[G][STQ_COUNT]: azsp_get_status / azsp_dropin_step
+(STC_STATUS, STC_PLY, STC_ROOT_N, STC_N_LEAVES, STC_LAST_MOVE, STC_GAMES_DONE, STC_ROOT_EVAL_PENDING, STC_NOISE_PENDING,
+ STC_COUNT) = range(9)
+STQ_ROOT_Q, STQ_CHILD_Q, STQ_COUNT = range(3)
+# scalars int32[G][ENV_COUNT]: azsp_env_step
+(ENV_KO, ENV_CAPS_BLACK, ENV_CAPS_WHITE, ENV_STEPS, ENV_TO_PLAY, ENV_DONE, ENV_REWARD, ENV_WINNER, ENV_AREA_BLACK, ENV_AREA_WHITE,
+ ENV_ILLEGAL, ENV_LAST_PASS, ENV_COUNT) = range(13)
+# games int32[k][GR_COUNT] + extras int32[k][GX_COUNT]: azsp_harvest / azsp_harvest_extra
+(GR_START, GR_LENGTH, GR_WINNER, GR_AREA_BLACK, GR_AREA_WHITE, GR_PASSES, GR_RESIGNED, GR_RESIGN_DISABLED, GR_MARKED, GR_COULD_WON,
+ GR_MARKED_PLAYER, GR_UID, GR_TRAINING_STEPS, GR_REWARD, GR_LAST_PLAYER, GR_SLOT, GR_COUNT) = range(17)
+GR_SLOT_RANK_SHIFT = 20  # rows merged across ranks: slot | rank << GR_SLOT_RANK_SHIFT (core/gather.py)
+GR_SLOT_MASK = (1 << GR_SLOT_RANK_SHIFT) - 1
+GX_TS_END, GX_THRESHOLD_LO, GX_THRESHOLD_HI, GX_STRADDLED, GX_COUNT = range(5)
+# q float64[SQ_COUNT]: azsp_get_search
+SQ_ROOT_Q, SQ_CHILD_Q, SQ_ROOT_N, SQ_MOVE, SQ_COUNT = range(5)
+
 SYMBOLS = [
     "azsp_create", "azsp_destroy", "azsp_last_error", "azsp_geometry", "azsp_set_tables", "azsp_set_injection",
     "azsp_reset_games", "azsp_env_step", "azsp_set_state", "azsp_begin_move", "azsp_select", "azsp_expand_backup",

@@ -164,7 +164,7 @@ class Engine:
 
     def env_step(self, actions=None, want_obs=False):
         """Standalone env kernels.  actions int[G] (None = export only; -2 no-op, -1 resign).
-        Returns dict(board int8[G,N,N], legal int8[G,A], scalars int32[G,12], obs int8[G,2K+1,N,N] | None) on the host."""
+        Returns dict(board int8[G,N,N], legal int8[G,A], scalars int32[G,ENV_COUNT], obs int8[G,2K+1,N,N] | None) on the host."""
         dev = self.device
         if actions is None:
             ap = None
@@ -173,7 +173,7 @@ class Engine:
             ap = self._actions.data_ptr()
         board = torch.empty((self.G, self.N, self.N), dtype=torch.int8, device=dev)
         legal = torch.empty((self.G, self.A), dtype=torch.int8, device=dev)
-        scal = torch.empty((self.G, 12), dtype=torch.int32, device=dev)
+        scal = torch.empty((self.G, _abi.ENV_COUNT), dtype=torch.int32, device=dev)
         obs = torch.empty((self.G, self.planes, self.N, self.N), dtype=torch.int8, device=dev) if want_obs else None
         self._ck(self.b.dll.azsp_env_step(self.h, ap, board.data_ptr(), legal.data_ptr(), scal.data_ptr(),
                                           obs.data_ptr() if want_obs else None, self._stream()), "azsp_env_step")
@@ -218,21 +218,21 @@ class Engine:
                                        self.valid.data_ptr(), self._stream()), "azsp_round")
 
     def status(self):
-        st = np.zeros((self.G, 8), dtype=np.int32)
-        q = np.zeros((self.G, 2), dtype=np.float64)
+        st = np.zeros((self.G, _abi.STC_COUNT), dtype=np.int32)
+        q = np.zeros((self.G, _abi.STQ_COUNT), dtype=np.float64)
         self._ck(self.b.dll.azsp_get_status(self.h, st.ctypes.data, q.ctypes.data, self._stream()), "azsp_get_status")
         return st, q
 
     def dropin_step(self, priors=None, values=None, feature_rows=None):
         """One iteration of uct_search's simulation loop in ONE host round trip (azsp_dropin_step): upload eval_func's `priors`
         float32[rows, A] / `values` float32[rows] for the previous leaves (None on the first call of a search), expand / backup, select
-        the next leaves, and return (status int32[G, 8], q float64[G, 2], valid bool[rows], obs [feature_rows, 2K+1, N, N] of the engine's
+        the next leaves, and return (status int32[G, STC_COUNT], q float64[G, STQ_COUNT], valid bool[rows], obs [feature_rows, 2K+1, N, N] of the engine's
         feature dtype).  Feature dtypes with a plain [rows, 2K+1, N, N] tensor only (AZSP_FEAT_I8 / F32)."""
         assert not (self.features_tiled or self.features_split)
         nrow = self.rows if feature_rows is None else int(feature_rows)
         if getattr(self, "_dropin_bufs", None) is None:
             np_dt = {torch.int8: np.int8, torch.float32: np.float32}[self.features.dtype]
-            self._dropin_bufs = (np.zeros((self.G, 8), dtype=np.int32), np.zeros((self.G, 2), dtype=np.float64), np.zeros(self.rows, dtype=np.uint8),
+            self._dropin_bufs = (np.zeros((self.G, _abi.STC_COUNT), dtype=np.int32), np.zeros((self.G, _abi.STQ_COUNT), dtype=np.float64), np.zeros(self.rows, dtype=np.uint8),
                                  np.zeros((self.rows, self.planes, self.N, self.N), dtype=np_dt))
         st, q, valid, obs = self._dropin_bufs
         pp = vp = None
@@ -248,7 +248,7 @@ class Engine:
     def get_search(self, slot, ply=0):
         pi = np.zeros(self.A, dtype=np.float64)
         cn = np.zeros(self.A, dtype=np.float32)
-        q = np.zeros(4, dtype=np.float64)
+        q = np.zeros(_abi.SQ_COUNT, dtype=np.float64)
         self._ck(self.b.dll.azsp_get_search(self.h, slot, ply, pi.ctypes.data, cn.ctypes.data, q.ctypes.data, self._stream()), "azsp_get_search")
         return pi, cn, q
 
@@ -263,9 +263,9 @@ class Engine:
 
     # -- samples ----------------------------------------------------------------------------------------
     def harvest(self, sample_capacity=None, max_games=None, with_moves=False):
-        """Returns (states int8[n,2K+1,N,N], pi float32[n,A], z float32[n], games int32[k,16]) -- device tensors + host meta;
+        """Returns (states int8[n,2K+1,N,N], pi float32[n,A], z float32[n], games int32[k,GR_COUNT]) -- device tensors + host meta;
         with_moves=True appends moves int16[n] (the move played from every sample's position, -1 = resigned).
-        The per-game extras of the same call (azsp_harvest_extra) are left in `self.last_extra` int32[k,4].
+        The per-game extras of the same call (azsp_harvest_extra) are left in `self.last_extra` int32[k,GX_COUNT].
         ALIASING: the device tensors are views of buffers this engine re-uses -- the NEXT harvest() overwrites them in place.
         Consume (or .clone()) them before harvesting again; SelfPlayActor.harvest_tensors(clone=True) does the latter."""
         cap = sample_capacity or max(4 * self.G, 2 * self.geo.stage_capacity)
@@ -277,8 +277,8 @@ class Engine:
                                   torch.empty((cap,), dtype=torch.int16, device=self.device))
         st, pi, z, mvbuf = self._harvest_bufs
         self._ck(self.b.dll.azsp_harvest_moves(self.h, mvbuf.data_ptr() if with_moves else None), "azsp_harvest_moves")
-        games = np.zeros((mg, 16), dtype=np.int32)
-        extra = np.zeros((mg, 4), dtype=np.int32)
+        games = np.zeros((mg, _abi.GR_COUNT), dtype=np.int32)
+        extra = np.zeros((mg, _abi.GX_COUNT), dtype=np.int32)
         self._ck(self.b.dll.azsp_harvest_extra(self.h, extra.ctypes.data), "azsp_harvest_extra")
         ns, ng = C.c_int32(0), C.c_int32(0)
         self._ck(self.b.dll.azsp_harvest(self.h, st.data_ptr(), pi.data_ptr(), z.data_ptr(), st.shape[0], games.ctypes.data, mg,

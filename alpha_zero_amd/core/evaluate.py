@@ -206,9 +206,9 @@ def play_eval_games_parallel(game, board_size, players, num_simulations, num_par
             for t in range(max(len(o) for o in openings)):
                 acts = np.array([o[t] if t < len(o) else -2 for o in openings], dtype=np.int32)
                 out = eng.env_step(acts)
-                # the env kernel skips an illegal or post-terminal action and flags it (scalars[10]); an opening that was not
+                # the env kernel skips an illegal or post-terminal action and flags it (ENV_ILLEGAL); an opening that was not
                 # played as given would shift the colour / evaluator pairing by one ply and report moves that never happened
-                bad = np.nonzero((acts != -2) & (out["scalars"][:, 10] != 0))[0]
+                bad = np.nonzero((acts != -2) & (out["scalars"][:, _abi.ENV_ILLEGAL] != 0))[0]
                 if len(bad):
                     raise ValueError(f"opening move {t} of game {int(bad[0])} (action {int(acts[bad[0]])}) was rejected by the rules")
         # distinct evaluator objects and, per game and colour, which one searches
@@ -225,9 +225,9 @@ def play_eval_games_parallel(game, board_size, players, num_simulations, num_par
             eng.expand_backup()
             eng.select()
             st, _ = eng.status()
-            if np.all(st[:, 0] == _abi.ST_IDLE):
+            if np.all(st[:, _abi.STC_STATUS] == _abi.ST_IDLE):
                 break
-            side = (st[:, 1] & 1).astype(np.int64)                      # ply even: black is searching
+            side = (st[:, _abi.STC_PLY] & 1).astype(np.int64)                      # ply even: black is searching
             ev_of_game = who[np.arange(G), side]
             valid_dev = eng.valid.view(G, P).bool()
             host_needed = not all(on_device[k] for k in np.unique(ev_of_game))
@@ -267,11 +267,11 @@ def play_eval_games_parallel(game, board_size, players, num_simulations, num_par
         games, moves = got[3], got[4].cpu().numpy()
         out = [None] * G
         for row in games:
-            g, s0, ln = int(row[15]), int(row[0]), int(row[1])
+            g, s0, ln = int(row[_abi.GR_SLOT]), int(row[_abi.GR_START]), int(row[_abi.GR_LENGTH])
             stats = game_stats_from_row(row, game, komi)
             opening = [int(m) for m in openings[g]] if openings is not None else []
             out[g] = dict(moves=opening + [int(m) for m in moves[s0:s0 + ln]], game_length=len(opening) + stats["game_length"], game_result=stats["game_result"],
-                          num_passes=stats.get("num_passes"), winner=int(row[2]))
+                          num_passes=stats.get("num_passes"), winner=int(row[_abi.GR_WINNER]))
         if not all(o is not None for o in out):
             raise RuntimeError("evaluation games did not all reach the harvest")
         return out

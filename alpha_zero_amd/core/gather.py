@@ -4,12 +4,17 @@ during search, so this is the only exchange on the data path: per harvest, one a
 `gather` of a packed byte buffer to `dst` (RCCL over xGMI when the backend is "nccl": every sender uses
 its own direct link into the root).  Works unchanged on gloo/CPU tensors (tests).
 
-Wire format per rank and harvest: [maxn rows][row_bytes] + [maxk][64] bytes, a row =
+Wire format per rank and harvest: [maxn rows][row_bytes] + [maxk][GAME_ROW_BYTES] bytes, a row =
 ceil(17 N^2 / 8) bytes of bit-packed 0/1 observation planes | A float32 of pi | 1 float32 of z  (173 + 328 + 4 = 505 B per
-sample at 9x9 instead of 1709 B unpacked), the tail = the 16-int game records.  Padded to the largest rank of this harvest."""
+sample at 9x9 instead of 1709 B unpacked), the tail = the game rows (int32[GR_COUNT]).  Padded to the largest rank of this harvest."""
 import numpy as np
 import torch
 import torch.distributed as dist
+
+from .. import _abi
+
+GAME_ROW_BYTES = 4 * _abi.GR_COUNT  # one int32 game row on the wire
+
 
 def _bit_weights(dev):
     return torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.uint8, device=dev)
@@ -43,9 +48,9 @@ def unpack_samples(rows, state_shape, A):
 
 
 def gather_samples(states, pi, z, games, dst=0, group=None):
-    """states int8[n,C,N,N] (C = 2 * num_stack + 1), pi f32[n,A], z f32[n] (device tensors of this rank), games int32[k,16] (numpy).
-    Returns on `dst` the concatenation over ranks (rank order) with game `start` offsets rebased and column 15
-    (slot) made global as rank*2^20 + slot; on other ranks returns None.
+    """states int8[n,C,N,N] (C = 2 * num_stack + 1), pi f32[n,A], z f32[n] (device tensors of this rank), games int32[k,GR_COUNT] (numpy).
+    Returns on `dst` the concatenation over ranks (rank order) with game `start` offsets rebased and column GR_SLOT
+    made global as slot | rank << GR_SLOT_RANK_SHIFT; on other ranks returns None.
 
     Collectives only (every rank takes part in every call, no point-to-point pairing to get wrong): one all_gather of the
     (samples, games) counts, then ONE `gather` of the packed byte buffer to `dst`, padded to the largest count of this harvest.
@@ -57,7 +62,7 @@ def gather_samples(states, pi, z, games, dst=0, group=None):
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     dev = states.device
     state_shape, A = tuple(states.shape[1:]), pi.shape[1]
-    g_t = torch.as_tensor(np.ascontiguousarray(games, dtype=np.int32)).reshape(-1, 16).to(dev)
+    g_t = torch.as_tensor(np.ascontiguousarray(games, dtype=np.int32)).reshape(-1, _abi.GR_COUNT).to(dev)
     counts = torch.tensor([states.shape[0], g_t.shape[0]], dtype=torch.int64, device=dev)
     all_counts = [torch.zeros_like(counts) for _ in range(world)]
     dist.all_gather(all_counts, counts, group=group)
@@ -67,7 +72,7 @@ def gather_samples(states, pi, z, games, dst=0, group=None):
         return (states[:0], pi[:0], z[:0], np.zeros((0, 16), dtype=np.int32)) if rank == dst else None
     rows = pack_samples(states, pi, z)
     rb = rows.shape[1]
-    buf = torch.zeros((maxn * rb + maxk * 64,), dtype=torch.uint8, device=dev)
+    buf = torch.zeros((maxn * rb + maxk * GAME_ROW_BYTES,), dtype=torch.uint8, device=dev)
     if rows.numel():
         buf[: rows.numel()] = rows.reshape(-1)
     if g_t.numel():  # (a rank with no finished game in this harvest: an empty [0, 16] tensor has no byte view -- found by the 8-rank gloo test)
@@ -84,9 +89,9 @@ def gather_samples(states, pi, z, games, dst=0, group=None):
             s_r, p_r, z_r = unpack_samples(out[r][: n * rb].reshape(n, rb), state_shape, A)
             parts_s.append(s_r), parts_p.append(p_r), parts_z.append(z_r)
         if k:
-            grows = out[r][maxn * rb: maxn * rb + k * 64].clone().view(torch.int32).reshape(k, 16).cpu().numpy().copy()
-            grows[:, 0] += base
-            grows[:, 15] += r << 20
+            grows = out[r][maxn * rb: maxn * rb + k * GAME_ROW_BYTES].clone().view(torch.int32).reshape(k, _abi.GR_COUNT).cpu().numpy().copy()
+            grows[:, _abi.GR_START] += base
+            grows[:, _abi.GR_SLOT] += r << _abi.GR_SLOT_RANK_SHIFT
             parts_g.append(grows)
         base += n
     if not parts_s:

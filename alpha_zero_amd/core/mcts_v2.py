@@ -88,10 +88,10 @@ def _simulate_with_callback(eng, eval_func, P, num_parallel, A):
     val = np.zeros(eng.rows, dtype=np.float32)
     st, q, valid, obs = eng.dropin_step(None, None, P)
     for _ in range(1 << 20):
-        if st[0, 0] == _abi.ST_MOVE_DONE:
+        if st[0, _abi.STC_STATUS] == _abi.ST_MOVE_DONE:
             return
         if valid.any():
-            if st[0, 6] or num_parallel == 1:  # root evaluation / uct_search leaves: unbatched call (mcts_v2.py:365, :414, :555)
+            if st[0, _abi.STC_ROOT_EVAL_PENDING] or num_parallel == 1:  # root evaluation / uct_search leaves: unbatched call (mcts_v2.py:365, :414, :555)
                 p, v = eval_func(obs[0], False)
                 pri[0], val[0] = np.asarray(p, dtype=np.float32), v
             else:
@@ -130,9 +130,9 @@ def _simulate_on_device(eng, evaluator, num_simulations, num_parallel):
     eng.round()  # nothing to back up yet: selects the first leaf (or asks for the root's evaluation)
     for _ in range(1 << 20):
         st, _ = eng.status()
-        if st[0, 0] == _abi.ST_MOVE_DONE:
+        if st[0, _abi.STC_STATUS] == _abi.ST_MOVE_DONE:
             return
-        left = max(num_simulations - int(st[0, 2]), 1)
+        left = max(num_simulations - int(st[0, _abi.STC_ROOT_N]), 1)
         iterate(max(1, (left // 2) // per_iter))
     raise RuntimeError("the search did not finish")
 
@@ -182,13 +182,13 @@ def _search(env, eval_func, root_node, c_puct_base, c_puct_init, num_simulations
     eng.commit_move([int(move)])
     st, q = eng.status()
     next_root = None
-    if st[0, 0] == _abi.ST_SEARCH:
+    if st[0, _abi.STC_STATUS] == _abi.ST_SEARCH:
         out = eng.env_step(None)  # export the new root position for the hand-over check of the next call
-        next_root = Node(s, out["board"][0].copy(), int(out["scalars"][0][4]), int(out["scalars"][0][3]))
+        next_root = Node(s, out["board"][0].copy(), int(out["scalars"][0][_abi.ENV_TO_PLAY]), int(out["scalars"][0][_abi.ENV_STEPS]))
     else:
         _release(s)
     assert root_legal[move] == 1
-    return (move, search_pi, float(q[0, 0]), float(q[0, 1]), next_root)
+    return (move, search_pi, float(q[0, _abi.STQ_ROOT_Q]), float(q[0, _abi.STQ_CHILD_Q]), next_root)
 
 
 def uct_search(env, eval_func, root_node, c_puct_base, c_puct_init, num_simulations=800, root_noise=False, warm_up=False,

@@ -1,20 +1,22 @@
 """Self-play actor on the batched engine (reference: alpha_zero/core/pipeline.py:83-382).
 
 `game_stats_from_row` rebuilds the per-game `stats` dict of play_and_record_one_game
-(pipeline.py:367-380) from the 16-int game record the engine emits at harvest time.
+(pipeline.py:367-380) from the game row (include/azsp.h AZSP_GR_*, mirrored as _abi.GR_*) the engine emits at harvest time.
 """
 from typing import Any, Dict
 
 import numpy as np
 
+from .. import _abi
+
 
 def _result_string(row, game, komi):
     """go.py:194-200 + go_engine.py:527-534 / gomoku.py:138-147"""
-    winner = int(row[2])
+    winner = int(row[_abi.GR_WINNER])
     if game == "go":
-        if int(row[6]):  # resigned
+        if int(row[_abi.GR_RESIGNED]):
             return "B+R" if winner == 1 else "W+R"
-        score = float(int(row[3])) - (float(int(row[4])) + komi)
+        score = float(int(row[_abi.GR_AREA_BLACK])) - (float(int(row[_abi.GR_AREA_WHITE])) + komi)
         if score > 0:
             return "B+" + "%.1f" % score
         if score < 0:
@@ -24,13 +26,14 @@ def _result_string(row, game, komi):
 
 
 def game_stats_from_row(row, game: str, komi: float = 7.5, resign_threshold: float = -1.0) -> Dict[str, Any]:
-    stats: Dict[str, Any] = {"game_length": int(row[1]), "game_result": _result_string(row, game, komi)}
+    """`row`: one game row int32[GR_COUNT] of Engine.harvest() (azsp_harvest's games_host)."""
+    stats: Dict[str, Any] = {"game_length": int(row[_abi.GR_LENGTH]), "game_result": _result_string(row, game, komi)}
     if game == "go":  # has_pass_move / has_resign_move (pipeline.py:372-380)
-        stats["num_passes"] = int(row[5])
-        stats["is_resign_disabled"] = bool(row[7])
-        stats["is_marked_for_resign"] = bool(row[8])
-        stats["is_could_won"] = bool(row[9])
-        mp = int(row[10])
+        stats["num_passes"] = int(row[_abi.GR_PASSES])
+        stats["is_resign_disabled"] = bool(row[_abi.GR_RESIGN_DISABLED])
+        stats["is_marked_for_resign"] = bool(row[_abi.GR_MARKED])
+        stats["is_could_won"] = bool(row[_abi.GR_COULD_WON])
+        mp = int(row[_abi.GR_MARKED_PLAYER])
         stats["marked_resign_player"] = "B" if mp == 1 else "W" if mp == -1 else None
         stats["resign_threshold"] = resign_threshold
     return stats
@@ -44,7 +47,6 @@ import warnings  # noqa: E402
 
 import torch  # noqa: E402
 
-from .. import _abi  # noqa: E402
 from .engine import Engine, EngineConfig  # noqa: E402
 from .network import AlphaZeroNet, InferenceNet, capture_graph, widen_for_kernels  # noqa: E402
 from .replay import Transition  # noqa: E402
@@ -258,7 +260,7 @@ class SelfPlayActor:
         e.g. an asynchronous learner or a replay insert on another stream)."""
         st, pi, z, games = self.engine.harvest()
         self._check_evaluator_range()
-        self.last_harvest_clamped = self.clamp_window.mask(games[:, 11]) if len(games) else np.zeros(0, dtype=bool)
+        self.last_harvest_clamped = self.clamp_window.mask(games[:, _abi.GR_UID]) if len(games) else np.zeros(0, dtype=bool)
         self.clamped_games += int(self.last_harvest_clamped.sum())
         return (st.clone(), pi.clone(), z.clone(), games) if clone else (st, pi, z, games)
 
@@ -284,7 +286,7 @@ class SelfPlayActor:
         self.range_events += ev
         self.range_max_abs = max(self.range_max_abs, mx * 2.0 ** inf.act_shift)
         # every game that ran a round since the last clean poll is suspect: the ones in progress now + the finished ones not handed out yet
-        self.clamp_window.on_event(e.status()[0][:, 5])
+        self.clamp_window.on_event(e.status()[0][:, _abi.STC_GAMES_DONE])
         batch = dict(planes=e.features, split_features=(e.rows, e.N)) if e.features_split else {}  # (the re-calibration takes the stem's own layout)
         if inf.repair_range(ev, mx, slot=0, **batch):
             self.range_rescales += 1
@@ -306,16 +308,16 @@ class SelfPlayActor:
         states, pi, z = states.cpu().numpy(), pi.cpu().numpy(), z.cpu().numpy()
         moves = got[4].cpu().numpy() if with_moves else None
         out = []
-        self.last_harvest_clamped = self.clamp_window.mask(games[:, 11])
+        self.last_harvest_clamped = self.clamp_window.mask(games[:, _abi.GR_UID])
         for row, ex, clamped in zip(games, extra, self.last_harvest_clamped):
-            s0, ln = int(row[0]), int(row[1])
+            s0, ln = int(row[_abi.GR_START]), int(row[_abi.GR_LENGTH])
             if clamped:
                 # the game ran a round between a clamp event of the fp32-class evaluator and its repair: some of its searches may have
                 # used a clamped activation where the reference's fp32 forward (pipeline.py:102-109) carries the value on
                 self.clamped_games += 1
                 if self.drop_clamped_games:
                     continue
-            if int(ex[3]):
+            if int(ex[_abi.GX_STRADDLED]):
                 # The game was in progress across a weight hot-swap -- impossible in the reference, whose actor only reloads between
                 # games (pipeline.py:232-239).  It keeps the tag of the weights that STARTED it (pipeline.py:237 -> :271) and is
                 # counted; drop_straddling_games=True discards it instead.
@@ -325,9 +327,9 @@ class SelfPlayActor:
             pis = pi[s0:s0 + ln].astype(np.float64) if self.game == "go" else pi[s0:s0 + ln]
             seq = [Transition(state=states[s0 + i].copy(), pi_prob=pis[i].copy(), value=float(z[s0 + i])) for i in range(ln)]
             # the threshold this very game was played with (pipeline.py:241-242, :379), exact double
-            thr = float(np.array([ex[1], ex[2]], dtype=np.int32).view(np.float64)[0])
+            thr = float(np.array([ex[_abi.GX_THRESHOLD_LO], ex[_abi.GX_THRESHOLD_HI]], dtype=np.int32).view(np.float64)[0])
             stats = game_stats_from_row(row, self.game, self.komi, thr)
-            stats["training_steps"] = int(row[12])  # weights in use when the game started (pipeline.py:237, :271, :492)
+            stats["training_steps"] = int(row[_abi.GR_TRAINING_STEPS])  # weights in use when the game started (pipeline.py:237, :271, :492)
             if clamped:
                 stats["evaluator_clamped"] = True  # (only ever present on such a game: the reference's stats keys stay as they are)
             out.append((seq, stats, [int(m) for m in moves[s0:s0 + ln] if m >= 0]) if with_moves else (seq, stats))

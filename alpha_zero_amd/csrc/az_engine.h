@@ -1290,11 +1290,11 @@ template <class Wv, int N, int GAME> struct Engine {
             gr.out_root_q = rq;
             gr.out_child_q = cq;
             if (c.log_moves && gr.ply < c.log_cap) {
-                double* lq = m.log_q + ((size_t)g * c.log_cap + gr.ply) * 4;
-                lq[0] = rq;
-                lq[1] = cq;
-                lq[2] = (double)gr.root_N;
-                lq[3] = (double)mv;
+                double* lq = m.log_q + ((size_t)g * c.log_cap + gr.ply) * AZSP_SQ_COUNT;
+                lq[AZSP_SQ_ROOT_Q] = rq;
+                lq[AZSP_SQ_CHILD_Q] = cq;
+                lq[AZSP_SQ_ROOT_N] = (double)gr.root_N;
+                lq[AZSP_SQ_MOVE] = (double)mv;
             }
         }
         cnt[AZC_MOVES]++;

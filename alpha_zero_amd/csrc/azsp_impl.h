@@ -13,6 +13,10 @@
 #include "az_conv.h"
 #include "az_engine.h"
 
+// The fixed-width rows of the ABI (include/azsp.h): today's widths, pinned so that the drop-in staging offsets cannot drift.
+static_assert(AZSP_STC_COUNT == 8 && AZSP_STQ_COUNT == 2 && AZSP_ENV_COUNT == 12, "status / env rows are part of the ABI");
+static_assert(AZSP_GR_COUNT == 16 && AZSP_GX_COUNT == 4 && AZSP_SQ_COUNT == 4, "game / search rows are part of the ABI");
+
 #define AZ_FOR_EACH_VARIANT(X) \
     X(5, AZ_GO) X(9, AZ_GO) X(13, AZ_GO) X(19, AZ_GO) X(7, AZ_GOMOKU) X(9, AZ_GOMOKU) X(13, AZ_GOMOKU) X(15, AZ_GOMOKU)
 
@@ -85,17 +89,17 @@ struct OpStatus {
     double* q;
     template <class E> AZ_HD void operator()(E& e) const {
         if (E::Wave::first()) {
-            int* s = status + (size_t)e.g * 8;
-            s[0] = e.gr.status;
-            s[1] = e.gr.ply;
-            s[2] = e.gr.root_N;
-            s[3] = e.gr.n_leaves;
-            s[4] = e.gr.out_move;
-            s[5] = e.gr.games_done;
-            s[6] = e.gr.root_eval_pending;
-            s[7] = e.gr.noise_pending;
-            q[(size_t)e.g * 2] = e.gr.out_root_q;
-            q[(size_t)e.g * 2 + 1] = e.gr.out_child_q;
+            int* s = status + (size_t)e.g * AZSP_STC_COUNT;
+            s[AZSP_STC_STATUS] = e.gr.status;
+            s[AZSP_STC_PLY] = e.gr.ply;
+            s[AZSP_STC_ROOT_N] = e.gr.root_N;
+            s[AZSP_STC_N_LEAVES] = e.gr.n_leaves;
+            s[AZSP_STC_LAST_MOVE] = e.gr.out_move;
+            s[AZSP_STC_GAMES_DONE] = e.gr.games_done;
+            s[AZSP_STC_ROOT_EVAL_PENDING] = e.gr.root_eval_pending;
+            s[AZSP_STC_NOISE_PENDING] = e.gr.noise_pending;
+            q[(size_t)e.g * AZSP_STQ_COUNT + AZSP_STQ_ROOT_Q] = e.gr.out_root_q;
+            q[(size_t)e.g * AZSP_STQ_COUNT + AZSP_STQ_CHILD_Q] = e.gr.out_child_q;
         }
     }
 };
@@ -110,8 +114,8 @@ struct OpDropinStep {
     const float* values;
     void* feat;
     unsigned char* valid;
-    int* status;               // host-visible: [G][8]
-    double* q;                 // host-visible: [G][2]
+    int* status;               // host-visible: [G][AZSP_STC_COUNT]
+    double* q;                 // host-visible: [G][AZSP_STQ_COUNT]
     int* fault;                // host-visible: [G], the engine fault flags as this game's wave sees them when it is done
     unsigned char* valid_out;  // host-visible: [G * P]
     unsigned char* feat_out;   // host-visible: the first feat_bytes bytes of `feat`
@@ -150,7 +154,8 @@ struct OpRngProbe {
     int plies, tries;
     template <class E> AZ_HD void operator()(E& e) const { e.probe_rng(noise, unif, plies, tries); }
 };
-// packed position uploaded by azsp_set_state: u64 stones[2][W], u64 hist[8][2][W], int scalars[8]
+// packed position uploaded by azsp_set_state: u64 stones[2][W], u64 hist[8][2][W], int scalars[8] (PK_*)
+enum { PK_TO_PLAY, PK_STEPS, PK_KO, PK_LAST_PASS, PK_CAPS_BLACK, PK_CAPS_WHITE };
 struct OpSetState {
     int slot;
     const u64* packed;
@@ -163,12 +168,12 @@ struct OpSetState {
         typename E::S s;
         for (int q = 0; q < 2; ++q)
             for (int w = 0; w < W; ++w) s.stones[q][w] = packed[q * W + w];
-        s.to_play = (uint8_t)sc[0];
-        s.steps = (int16_t)sc[1];
-        s.ko = (int16_t)sc[2];
-        s.flags = sc[3] ? AZF_LASTPASS : 0;
-        s.caps[0] = (uint16_t)sc[4];
-        s.caps[1] = (uint16_t)sc[5];
+        s.to_play = (uint8_t)sc[PK_TO_PLAY];
+        s.steps = (int16_t)sc[PK_STEPS];
+        s.ko = (int16_t)sc[PK_KO];
+        s.flags = sc[PK_LAST_PASS] ? AZF_LASTPASS : 0;
+        s.caps[0] = (uint16_t)sc[PK_CAPS_BLACK];
+        s.caps[1] = (uint16_t)sc[PK_CAPS_WHITE];
         s.winner = -1;
         s.reward = 0;
         s.area[0] = s.area[1] = 0;
@@ -238,19 +243,19 @@ struct OpEnvStep {
             int ab = 0, aw = 0;
             if (go) R::go_area(R::ld(s.stones[0]), R::ld(s.stones[1]), ab, aw);
             if (E::Wave::first()) {
-                int* o = scalars + (size_t)e.g * 12;
-                o[0] = s.ko;
-                o[1] = s.caps[0];
-                o[2] = s.caps[1];
-                o[3] = s.steps;
-                o[4] = s.to_play == 0 ? b_id : w_id;
-                o[5] = (s.flags & AZF_TERMINAL) ? 1 : 0;
-                o[6] = s.reward;
-                o[7] = s.winner < 0 ? 0 : (s.winner == 0 ? b_id : w_id);
-                o[8] = ab;
-                o[9] = aw;
-                o[10] = illegal;
-                o[11] = (s.flags & AZF_LASTPASS) ? 1 : 0;
+                int* o = scalars + (size_t)e.g * AZSP_ENV_COUNT;
+                o[AZSP_ENV_KO] = s.ko;
+                o[AZSP_ENV_CAPS_BLACK] = s.caps[0];
+                o[AZSP_ENV_CAPS_WHITE] = s.caps[1];
+                o[AZSP_ENV_STEPS] = s.steps;
+                o[AZSP_ENV_TO_PLAY] = s.to_play == 0 ? b_id : w_id;
+                o[AZSP_ENV_DONE] = (s.flags & AZF_TERMINAL) ? 1 : 0;
+                o[AZSP_ENV_REWARD] = s.reward;
+                o[AZSP_ENV_WINNER] = s.winner < 0 ? 0 : (s.winner == 0 ? b_id : w_id);
+                o[AZSP_ENV_AREA_BLACK] = ab;
+                o[AZSP_ENV_AREA_WHITE] = aw;
+                o[AZSP_ENV_ILLEGAL] = illegal;
+                o[AZSP_ENV_LAST_PASS] = (s.flags & AZF_LASTPASS) ? 1 : 0;
             }
         }
         if (obs) {
@@ -305,7 +310,7 @@ struct OpHarvest {
     int max_games;
     const int* ofs;   // [G][2][2] = (first output row, game index) of a staging buffer, -1 = not this time
     int16_t* moves;   // optional: the move played from every sample's position (azsp_harvest_moves)
-    int* extra;       // [max_games][4] = {training_steps at game end, resign threshold double bits lo, hi, straddled a weight swap}
+    int* extra;       // [max_games][AZSP_GX_COUNT]
     template <class E> AZ_HD void operator()(E& e) const {
         const int NP = E::NP, A = E::A, W = E::W;
         const bool go = E::GAME_ID == AZ_GO;
@@ -346,28 +351,28 @@ struct OpHarvest {
                 }
             }
             if (E::Wave::first()) {
-                int* o = games + (size_t)gi * 16;
-                o[0] = start;
-                o[1] = len;
-                o[2] = sh[SH_WINNER] < 0 ? 0 : (sh[SH_WINNER] == 0 ? b_id : w_id);
-                o[3] = sh[SH_AREA_B];
-                o[4] = sh[SH_AREA_W];
-                o[5] = sh[SH_PASSES];
-                o[6] = sh[SH_RESIGNED];
-                o[7] = sh[SH_RESIGN_DISABLED];
-                o[8] = sh[SH_MARKED];
-                o[9] = sh[SH_COULD_WON];
-                o[10] = sh[SH_MARKED_PLAYER] < 0 ? 0 : (sh[SH_MARKED_PLAYER] == 0 ? b_id : w_id);
-                o[11] = sh[SH_UID];
-                o[12] = sh[SH_TRAINING_STEPS];
-                int* x = extra + (size_t)gi * 4;
-                x[0] = sh[SH_TS_END];
-                x[1] = sh[SH_THR_LO];
-                x[2] = sh[SH_THR_HI];
-                x[3] = sh[SH_TS_END] != sh[SH_TRAINING_STEPS] ? 1 : 0;
-                o[13] = reward;
-                o[14] = last_player == 0 ? b_id : w_id;
-                o[15] = e.g;
+                int* o = games + (size_t)gi * AZSP_GR_COUNT;
+                o[AZSP_GR_START] = start;
+                o[AZSP_GR_LENGTH] = len;
+                o[AZSP_GR_WINNER] = sh[SH_WINNER] < 0 ? 0 : (sh[SH_WINNER] == 0 ? b_id : w_id);
+                o[AZSP_GR_AREA_BLACK] = sh[SH_AREA_B];
+                o[AZSP_GR_AREA_WHITE] = sh[SH_AREA_W];
+                o[AZSP_GR_PASSES] = sh[SH_PASSES];
+                o[AZSP_GR_RESIGNED] = sh[SH_RESIGNED];
+                o[AZSP_GR_RESIGN_DISABLED] = sh[SH_RESIGN_DISABLED];
+                o[AZSP_GR_MARKED] = sh[SH_MARKED];
+                o[AZSP_GR_COULD_WON] = sh[SH_COULD_WON];
+                o[AZSP_GR_MARKED_PLAYER] = sh[SH_MARKED_PLAYER] < 0 ? 0 : (sh[SH_MARKED_PLAYER] == 0 ? b_id : w_id);
+                o[AZSP_GR_UID] = sh[SH_UID];
+                o[AZSP_GR_TRAINING_STEPS] = sh[SH_TRAINING_STEPS];
+                int* x = extra + (size_t)gi * AZSP_GX_COUNT;
+                x[AZSP_GX_TS_END] = sh[SH_TS_END];
+                x[AZSP_GX_THRESHOLD_LO] = sh[SH_THR_LO];
+                x[AZSP_GX_THRESHOLD_HI] = sh[SH_THR_HI];
+                x[AZSP_GX_STRADDLED] = sh[SH_TS_END] != sh[SH_TRAINING_STEPS] ? 1 : 0;
+                o[AZSP_GR_REWARD] = reward;
+                o[AZSP_GR_LAST_PLAYER] = last_player == 0 ? b_id : w_id;
+                o[AZSP_GR_SLOT] = e.g;
                 sh[SH_STATE] = AZB_FREE;
             }
             E::Wave::sync();
@@ -679,20 +684,22 @@ static int az_geometry_of(int game, int n, int* A, int* AP, int* W, int* REC, in
     }
 }
 
+// the engine's sticky fault flags as a result code (and the message behind azsp_last_error)
+static int az_engine_fault_rc(AzHandle* h, int flags) {
+    if (!flags) return AZSP_OK;
+    char buf[160];
+    snprintf(buf, sizeof buf, "engine fault flags 0x%x (1=node pool exhausted, 2=tree deeper than %d, 4=move sampling, 8=staging full)", flags,
+             AZ_PATH_CAP);
+    h->err = buf;
+    return AZSP_EENGINE;
+}
 static int az_check_engine_fault(AzHandle* h, void* stream) {
     int e = 0;
     if (azb::d2h(&e, h->mem.err, sizeof(int), stream) != 0) {
         h->err = std::string("copy failed: ") + azb::backend_error();
         return AZSP_EDEVICE;
     }
-    if (e) {
-        char buf[160];
-        snprintf(buf, sizeof buf, "engine fault flags 0x%x (1=node pool exhausted, 2=tree deeper than %d, 4=move sampling, 8=staging full)", e,
-                 AZ_PATH_CAP);
-        h->err = buf;
-        return AZSP_EENGINE;
-    }
-    return AZSP_OK;
+    return az_engine_fault_rc(h, e);
 }
 
 // The evaluator wrappers: a backend launcher returns 0, 1 (unsupported shape) or -1 (device error).
@@ -785,19 +792,19 @@ int azsp_create(const AzspConfig* p, void** out) {
     m.stg_hdr = az_new<int>(h, G * 2 * SH_COUNT);
     m.log_pi = az_new<double>(h, G * c.log_cap * h->A);
     m.log_childN = az_new<float>(h, G * c.log_cap * h->A);
-    m.log_q = az_new<double>(h, G * c.log_cap * 4);
+    m.log_q = az_new<double>(h, G * c.log_cap * AZSP_SQ_COUNT);
     m.counters = az_new<u64>(h, G * AZC_COUNT);
     m.err = az_new<int>(h, 4);
-    h->d_status = az_new<int>(h, G * 8);
-    h->d_q = az_new<double>(h, G * 2);
+    h->d_status = az_new<int>(h, G * AZSP_STC_COUNT);
+    h->d_q = az_new<double>(h, G * AZSP_STQ_COUNT);
     h->d_moves = az_new<int>(h, G);
     h->d_packed = az_new<u64>(h, 18 * h->W + 8);
     h->d_hcounts = az_new<int>(h, 4);
     h->d_hlen = az_new<int>(h, 2 * G);
     h->d_hofs = az_new<int>(h, 4 * G);
     h->d_games_cap = (int)(2 * G);
-    h->d_games = az_new<int>(h, (size_t)h->d_games_cap * 16);
-    h->d_gextra = az_new<int>(h, (size_t)h->d_games_cap * 4);
+    h->d_games = az_new<int>(h, (size_t)h->d_games_cap * AZSP_GR_COUNT);
+    h->d_gextra = az_new<int>(h, (size_t)h->d_games_cap * AZSP_GX_COUNT);
     if (!m.nodes || !m.games || !m.rootP || !m.free_stack || !m.leaf_path || !m.stg_planes || !m.stg_pi || !m.log_pi ||
         !h->d_games || !h->d_gextra || !m.err || !h->d_hlen || !h->d_hofs) {
         for (void* q : h->allocs) azb::release(q);
@@ -893,12 +900,12 @@ int azsp_set_state(void* e, int32_t slot, const int8_t* board, const int8_t* his
             else if (v == w_id) pk[2 * W + (k * 2 + 1) * W + (p >> 6)] |= 1ull << (p & 63);
         }
     int* sc = (int*)(pk.data() + 18 * W);
-    sc[0] = to_play == 1 ? 0 : 1;
-    sc[1] = steps;
-    sc[2] = ko;
-    sc[3] = last_was_pass;
-    sc[4] = caps_b;
-    sc[5] = caps_w;
+    sc[PK_TO_PLAY] = to_play == 1 ? 0 : 1;
+    sc[PK_STEPS] = steps;
+    sc[PK_KO] = ko;
+    sc[PK_LAST_PASS] = last_was_pass;
+    sc[PK_CAPS_BLACK] = caps_b;
+    sc[PK_CAPS_WHITE] = caps_w;
     if (azb::h2d(h->d_packed, pk.data(), pk.size() * sizeof(u64), stream)) return AZSP_EDEVICE;
     OpSetState op = {slot, h->d_packed};
     return az_run(h, op, stream);
@@ -958,8 +965,8 @@ int azsp_get_status(void* e, int32_t* status, double* q, void* stream) {
     OpStatus op = {h->d_status, h->d_q};
     int rc = az_run(h, op, stream);
     if (rc) return rc;
-    if (status && azb::d2h(status, h->d_status, sizeof(int) * 8 * (size_t)h->cfg.G, stream)) return AZSP_EDEVICE;
-    if (q && azb::d2h(q, h->d_q, sizeof(double) * 2 * (size_t)h->cfg.G, stream)) return AZSP_EDEVICE;
+    if (status && azb::d2h(status, h->d_status, sizeof(int) * AZSP_STC_COUNT * (size_t)h->cfg.G, stream)) return AZSP_EDEVICE;
+    if (q && azb::d2h(q, h->d_q, sizeof(double) * AZSP_STQ_COUNT * (size_t)h->cfg.G, stream)) return AZSP_EDEVICE;
     return az_check_engine_fault(h, stream);
 }
 
@@ -975,8 +982,9 @@ int azsp_dropin_step(void* e, const float* priors_host, const float* values_host
     if (fd < 0 || fd > 6 || elem_of[fd] == 0) return AZSP_EINVAL;
     const size_t game_feat = (size_t)h->cfg.P * (2 * h->cfg.K + 1) * h->NP * elem_of[fd];
     if ((size_t)feat_bytes > G * game_feat) return AZSP_EINVAL;
-    // page-locked staging, device-visible: [priors rows*A f32][values rows f32] | [status G*8 i32][q G*2 f64][fault G i32][valid rows u8][features]
-    const size_t o_val = rows * A * 4, up = o_val + rows * 4, o_st = (up + 15) & ~(size_t)15, o_q = o_st + G * 32, o_err = o_q + G * 16,
+    // page-locked staging, device-visible: [priors rows*A f32][values rows f32] | [status G*STC_COUNT i32][q G*STQ_COUNT f64][fault G i32][valid rows u8][features]
+    const size_t st_bytes = AZSP_STC_COUNT * sizeof(int32_t), q_bytes = AZSP_STQ_COUNT * sizeof(double);
+    const size_t o_val = rows * A * 4, up = o_val + rows * 4, o_st = (up + 15) & ~(size_t)15, o_q = o_st + G * st_bytes, o_err = o_q + G * q_bytes,
                  o_valid = (o_err + G * 4 + 15) & ~(size_t)15, o_feat = o_valid + ((rows + 15) & ~(size_t)15), total = o_feat + (size_t)feat_bytes;
     if (h->pin_bytes < total) {
         if (h->pin) {
@@ -1001,19 +1009,13 @@ int azsp_dropin_step(void* e, const float* priors_host, const float* values_host
         h->err = std::string("synchronisation failed: ") + azb::backend_error();
         return AZSP_EDEVICE;
     }
-    memcpy(status_host, pin + o_st, G * 32);
-    if (q_host) memcpy(q_host, pin + o_q, G * 16);
+    memcpy(status_host, pin + o_st, G * st_bytes);
+    if (q_host) memcpy(q_host, pin + o_q, G * q_bytes);
     memcpy(valid_host, pin + o_valid, rows);
     if (feat_bytes > 0) memcpy(feat_host, pin + o_feat, (size_t)feat_bytes);
     int ef = 0;
     for (size_t g = 0; g < G; ++g) ef |= ((const int*)(pin + o_err))[g];
-    if (ef) {
-        char buf[160];
-        snprintf(buf, sizeof buf, "engine fault flags 0x%x (1=node pool exhausted, 2=tree deeper than %d, 4=move sampling, 8=staging full)", ef, AZ_PATH_CAP);
-        h->err = buf;
-        return AZSP_EENGINE;
-    }
-    return AZSP_OK;
+    return az_engine_fault_rc(h, ef);
 }
 
 int azsp_rng_probe(void* e, int32_t plies, int32_t tries, double* noise_host, double* unif_host, void* stream) {
@@ -1042,7 +1044,7 @@ int azsp_get_search(void* e, int32_t slot, int32_t ply, double* pi, float* cn, d
     const size_t o = (size_t)slot * h->cfg.log_cap + ply;
     if (pi && azb::d2h(pi, h->mem.log_pi + o * h->A, sizeof(double) * h->A, stream)) return AZSP_EDEVICE;
     if (cn && azb::d2h(cn, h->mem.log_childN + o * h->A, sizeof(float) * h->A, stream)) return AZSP_EDEVICE;
-    if (q && azb::d2h(q, h->mem.log_q + o * 4, sizeof(double) * 4, stream)) return AZSP_EDEVICE;
+    if (q && azb::d2h(q, h->mem.log_q + o * AZSP_SQ_COUNT, sizeof(double) * AZSP_SQ_COUNT, stream)) return AZSP_EDEVICE;
     return AZSP_OK;
 }
 
@@ -1076,8 +1078,8 @@ int azsp_harvest(void* e, int8_t* states, float* pi, float* z, int32_t cap, int3
     if (azb::d2h(cnt, h->d_hcounts, sizeof cnt, stream)) return AZSP_EDEVICE;
     *n_samples = cnt[0];
     *n_games = cnt[1];
-    if (cnt[1] > 0 && azb::d2h(games, h->d_games, sizeof(int) * 16 * (size_t)cnt[1], stream)) return AZSP_EDEVICE;
-    if (cnt[1] > 0 && h->harvest_extra && azb::d2h(h->harvest_extra, h->d_gextra, sizeof(int) * 4 * (size_t)cnt[1], stream)) return AZSP_EDEVICE;
+    if (cnt[1] > 0 && azb::d2h(games, h->d_games, sizeof(int) * AZSP_GR_COUNT * (size_t)cnt[1], stream)) return AZSP_EDEVICE;
+    if (cnt[1] > 0 && h->harvest_extra && azb::d2h(h->harvest_extra, h->d_gextra, sizeof(int) * AZSP_GX_COUNT * (size_t)cnt[1], stream)) return AZSP_EDEVICE;
     return az_check_engine_fault(h, stream);
 }
 

@@ -10,6 +10,7 @@ from copy import copy
 
 import numpy as np
 
+from .. import _abi
 from .coords import CoordsConvertor
 
 
@@ -60,16 +61,16 @@ class BoardGameEnv:
     def _pull(self, out):
         sc = out["scalars"][0]
         self.board = out["board"][0].copy()
-        done = bool(sc[5])
+        done = bool(sc[_abi.ENV_DONE])
         # dtype follows the reference: Go masks come from np.concatenate(..., [1]) -> int64 (go_engine.py:441);
         # Gomoku / base masks and the all-zero terminal mask are int8 (base.py:72, go.py:142)
         self.legal_actions = out["legal"][0].astype(np.int64 if (self._game == "go" and not done) else np.int8)
-        self.to_play = int(sc[4])
-        self.steps = int(sc[3])
-        self.winner = int(sc[7]) or None
-        self._done, self._reward = done, float(sc[6])
-        self.ko, self._caps, self._last_pass = int(sc[0]), (int(sc[1]), int(sc[2])), bool(sc[11])
-        self._areas = (int(sc[8]), int(sc[9]))
+        self.to_play = int(sc[_abi.ENV_TO_PLAY])
+        self.steps = int(sc[_abi.ENV_STEPS])
+        self.winner = int(sc[_abi.ENV_WINNER]) or None
+        self._done, self._reward = done, float(sc[_abi.ENV_REWARD])
+        self.ko, self._caps, self._last_pass = int(sc[_abi.ENV_KO]), (int(sc[_abi.ENV_CAPS_BLACK]), int(sc[_abi.ENV_CAPS_WHITE])), bool(sc[_abi.ENV_LAST_PASS])
+        self._areas = (int(sc[_abi.ENV_AREA_BLACK]), int(sc[_abi.ENV_AREA_WHITE]))
         self._obs = out["obs"][0].copy()
 
     def reset(self, **kwargs):
@@ -90,7 +91,7 @@ class BoardGameEnv:
             raise ValueError(f"Illegal action {action}.")
         mover = self.to_play
         out = self._eng.env_step([int(action)], want_obs=True)
-        if out["scalars"][0][10]:
+        if out["scalars"][0][_abi.ENV_ILLEGAL]:
             raise ValueError(f"Illegal action {action}.")
         self._pull(out)
         self.last_move, self.last_player = copy(int(action)), mover

@@ -156,8 +156,22 @@ int azsp_reset_games(void* engine, void* stream);
 
 /* Standalone environment kernels.  actions_dev[G]: action, -1 = resign (Go), -2 = no-op (export only).
  * Outputs (each may be NULL): board int8[G][N*N] (reference colour ids), legal int8[G][A],
- * scalars int32[G][12] = {ko, caps_black, caps_white, steps, to_play, done, reward, winner, area_black,
- * area_white, illegal, last_was_pass}, obs int8[G][2K+1][N][N] (K = num_stack). */
+ * scalars int32[G][AZSP_ENV_COUNT] (columns below), obs int8[G][2K+1][N][N] (K = num_stack). */
+enum {
+    AZSP_ENV_KO,          /* the ko point, -1 = none */
+    AZSP_ENV_CAPS_BLACK,
+    AZSP_ENV_CAPS_WHITE,
+    AZSP_ENV_STEPS,
+    AZSP_ENV_TO_PLAY,     /* ref id */
+    AZSP_ENV_DONE,
+    AZSP_ENV_REWARD,
+    AZSP_ENV_WINNER,      /* ref id, 0 none */
+    AZSP_ENV_AREA_BLACK,  /* Go only, else 0 */
+    AZSP_ENV_AREA_WHITE,
+    AZSP_ENV_ILLEGAL,     /* 0 = the action was applied; 1 game over, 2 invalid action, 3 illegal action */
+    AZSP_ENV_LAST_PASS,
+    AZSP_ENV_COUNT
+};
 int azsp_env_step(void* engine, const int32_t* actions_dev, int8_t* board_dev, int8_t* legal_dev, int32_t* scalars_dev,
                   int8_t* obs_dev, void* stream);
 
@@ -184,12 +198,25 @@ int azsp_expand_backup_range(void* engine, const float* priors_dev, const float*
 int azsp_round(void* engine, const float* priors_dev, const float* values_dev, void* features_dev, uint8_t* valid_dev,
                void* stream);
 
-/* status_host int32[G][8] = {status, ply, root_N, n_leaves, last_move, games_done, root_eval_pending, noise_pending};
- * q_host double[G][2] = {root_Q, best_child_Q} of the last finished search.  Synchronises the stream. */
+/* status_host int32[G][AZSP_STC_COUNT] and q_host double[G][AZSP_STQ_COUNT] (columns below; the Q pair is that of the last
+ * finished search).  Synchronises the stream. */
+enum {
+    AZSP_STC_STATUS,  /* AZSP_ST_* */
+    AZSP_STC_PLY,
+    AZSP_STC_ROOT_N,
+    AZSP_STC_N_LEAVES,
+    AZSP_STC_LAST_MOVE,
+    AZSP_STC_GAMES_DONE,
+    AZSP_STC_ROOT_EVAL_PENDING,
+    AZSP_STC_NOISE_PENDING,
+    AZSP_STC_COUNT
+};
+enum { AZSP_STQ_ROOT_Q, AZSP_STQ_CHILD_Q /* of the chosen move, 0 without a child node */, AZSP_STQ_COUNT };
 int azsp_get_status(void* engine, int32_t* status_host, double* q_host, void* stream);
 
 /* Search outputs of `slot` at log index `ply` (log_moves or drop-in mode): pi double[A], child_N float[A],
- * q double[4] = {root_Q, best_child_Q, root_N, move}.  Synchronises the stream. */
+ * q double[AZSP_SQ_COUNT] (columns below).  Synchronises the stream. */
+enum { AZSP_SQ_ROOT_Q, AZSP_SQ_CHILD_Q /* of the chosen move, 0 without a child node */, AZSP_SQ_ROOT_N, AZSP_SQ_MOVE, AZSP_SQ_COUNT };
 int azsp_get_search(void* engine, int32_t slot, int32_t ply, double* pi_host, float* child_n_host, double* q_host, void* stream);
 
 /* Drop-in mode: the caller's chosen moves (int32[G], host); re-roots each tree on the chosen child. */
@@ -199,8 +226,8 @@ int azsp_commit_move(void* engine, const int32_t* moves_host, void* stream);
  * caller's eval_func in ONE kernel launch and ONE stream synchronisation (the separate entries above cost four launches and eight
  * synchronisations).  priors_host float[rows][A] / values_host float[rows] (rows = G * P) = eval_func's outputs for the leaves of the
  * previous call; both NULL on the first call of a search (nothing to back up yet).  The game's wave runs expand / backup (and the
- * end-of-search work when the budget is met), selects the next leaves into features_dev / valid_dev, and writes status_host int32[G][8],
- * q_host double[G][2] (as azsp_get_status; q_host may be NULL), valid_host uint8[rows] and the first features_bytes bytes of
+ * end-of-search work when the budget is met), selects the next leaves into features_dev / valid_dev, and writes status_host
+ * int32[G][AZSP_STC_COUNT], q_host double[G][AZSP_STQ_COUNT] (as azsp_get_status; q_host may be NULL), valid_host uint8[rows] and the first features_bytes bytes of
  * features_dev (the observation planes eval_func receives; 0 = none; feature_dtype must be a plain [rows][2K+1][N][N] tensor: I8 / F32 /
  * BF16 / F16) -- through a page-locked staging buffer of the engine that the kernel reads and writes directly, so no copy command is
  * issued.  priors_dev / values_dev are the caller's evaluator tensors (unused by this entry beyond validation; azsp_expand_backup
@@ -210,9 +237,28 @@ int azsp_dropin_step(void* engine, const float* priors_host, const float* values
                      int64_t features_bytes, void* stream);
 
 /* Collect finished games.  states int8[cap][2K+1][N][N] (K = num_stack), pi float[cap][A], z float[cap] receive the samples of
- * whole games back to back; games_host int32[max_games][16] = {start, length, winner(ref id, 0 none), area_black,
- * area_white, num_passes, resigned, resign_disabled, marked_for_resign, could_won, marked_player(ref id, 0 none),
- * uid, training_steps, reward, last_player(ref id), slot}.  Synchronises the stream. */
+ * whole games back to back; games_host int32[max_games][AZSP_GR_COUNT] (columns below).  Synchronises the stream. */
+enum {
+    AZSP_GR_START,            /* first sample row of the game */
+    AZSP_GR_LENGTH,           /* number of samples */
+    AZSP_GR_WINNER,           /* ref id, 0 none */
+    AZSP_GR_AREA_BLACK,
+    AZSP_GR_AREA_WHITE,
+    AZSP_GR_PASSES,
+    AZSP_GR_RESIGNED,
+    AZSP_GR_RESIGN_DISABLED,
+    AZSP_GR_MARKED,           /* marked for resign */
+    AZSP_GR_COULD_WON,
+    AZSP_GR_MARKED_PLAYER,    /* ref id, 0 none */
+    AZSP_GR_UID,
+    AZSP_GR_TRAINING_STEPS,   /* tag of the weights that STARTED the game */
+    AZSP_GR_REWARD,
+    AZSP_GR_LAST_PLAYER,      /* ref id */
+    AZSP_GR_SLOT,             /* game slot; a caller that merges the rows of several engines tags it with its rank (below) */
+    AZSP_GR_COUNT
+};
+#define AZSP_GR_SLOT_RANK_SHIFT 20 /* merged rows: slot | rank << AZSP_GR_SLOT_RANK_SHIFT (alpha_zero_amd/core/gather.py) */
+#define AZSP_GR_SLOT_MASK ((1 << AZSP_GR_SLOT_RANK_SHIFT) - 1)
 int azsp_harvest(void* engine, int8_t* states_dev, float* pi_dev, float* z_dev, int32_t sample_capacity,
                  int32_t* games_host, int32_t max_games, int32_t* n_samples_out, int32_t* n_games_out, void* stream);
 
@@ -229,10 +275,16 @@ int azsp_rng_probe(void* engine, int32_t plies, int32_t tries, double* noise_hos
  * NULL (the default) disables it.  The buffer must stay valid for every later azsp_harvest call. */
 int azsp_harvest_moves(void* engine, int16_t* moves_dev);
 
-/* Third optional output of azsp_harvest: extra_host int32[max_games][4] (host memory, row i belongs to games_host row i) =
- * {training_steps of the weights in use when the game ENDED, the game's own resign threshold as the low / high word of its
- * double, 1 if the game straddled a weight hot-swap (end tag != start tag)}.  games_host column 12 is the tag of the weights that
- * STARTED the game, which is what the reference actor writes (core/pipeline.py:237 -> :271).  NULL (default) disables it. */
+/* Third optional output of azsp_harvest: extra_host int32[max_games][AZSP_GX_COUNT] (host memory, row i belongs to games_host
+ * row i; columns below).  games_host column AZSP_GR_TRAINING_STEPS is the tag of the weights that STARTED the game, which is what the
+ * reference actor writes (core/pipeline.py:237 -> :271).  NULL (default) disables it. */
+enum {
+    AZSP_GX_TS_END,        /* training_steps of the weights in use when the game ENDED */
+    AZSP_GX_THRESHOLD_LO,  /* the game's own resign threshold: low / high word of its double */
+    AZSP_GX_THRESHOLD_HI,
+    AZSP_GX_STRADDLED,     /* 1 if the game straddled a weight hot-swap (end tag != start tag) */
+    AZSP_GX_COUNT
+};
 int azsp_harvest_extra(void* engine, int32_t* extra_host);
 
 /* Per-game actor state: the reference actor re-reads the shared resign threshold (core/pipeline.py:241-242) and the weights'

@@ -193,7 +193,7 @@ def check_dropin_step_equals_the_separate_entries(kind, G=3, P=4, n=5, sims=24, 
         obs_b = eb.features.cpu().numpy()
         assert np.array_equal(st_a, st_b) and np.array_equal(q_a, q_b), (it, st_a, st_b)
         assert np.array_equal(valid_a, valid_b) and np.array_equal(obs_a, obs_b), it
-        if (st_a[:, 0] == _abi.ST_MOVE_DONE).all():
+        if (st_a[:, _abi.STC_STATUS] == _abi.ST_MOVE_DONE).all():
             break
         pri = rng.random((rows, A)).astype(np.float32)
         pri /= pri.sum(axis=1, keepdims=True)

@@ -11,6 +11,7 @@ import pytest
 
 import dropin_checks as dc
 import engine_util as eu
+from alpha_zero_amd import _abi
 
 
 def check_go19_known_sequences(kind, golden_dir):
@@ -60,10 +61,10 @@ def check_go9_score_boards(kind, golden_dir):
     out = eng.env_step(np.full(len(boards), 81, dtype=np.int32))    # white passes: game over, scored
     sc = out["scalars"]
     for i, (eb, ew) in enumerate(areas):
-        assert sc[i, 5] == 1 and (sc[i, 8], sc[i, 9]) == (eb, ew), (i, sc[i], eb, ew)
+        assert sc[i, _abi.ENV_DONE] == 1 and (sc[i, _abi.ENV_AREA_BLACK], sc[i, _abi.ENV_AREA_WHITE]) == (eb, ew), (i, sc[i], eb, ew)
         diff = float(eb) - (float(ew) + 7.5)
         winner = 1 if diff > 0 else -1
-        assert sc[i, 7] == winner
+        assert sc[i, _abi.ENV_WINNER] == winner
         # reward is from the last mover's (white's) point of view (go.py:141-150)
-        assert sc[i, 6] == (1 if winner == -1 else -1)
+        assert sc[i, _abi.ENV_REWARD] == (1 if winner == -1 else -1)
     eng.close()

@@ -15,6 +15,7 @@ sys.path.insert(0, HERE)
 rank, world, outdir = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3]
 dist.init_process_group("gloo", rank=rank, world_size=world)
 import engine_util as eu  # noqa: E402
+from alpha_zero_amd import _abi  # noqa: E402
 from alpha_zero_amd.core.gather import gather_samples  # noqa: E402
 from alpha_zero_amd.core.network import AlphaZeroNet  # noqa: E402
 from alpha_zero_amd.core.pipeline import SelfPlayActor  # noqa: E402
@@ -28,7 +29,7 @@ for it in range(400):
     a.run_rounds(20)
     if world > 2 and (rank + it) % 3 == 0:  # this rank sits the exchange out: zero samples, zero games
         st, pi, z, games = (torch.empty((0, 17, 5, 5), dtype=torch.int8), torch.empty((0, 26), dtype=torch.float32), torch.empty((0,), dtype=torch.float32),
-                            np.zeros((0, 16), dtype=np.int32))
+                            np.zeros((0, _abi.GR_COUNT), dtype=np.int32))
     else:
         st, pi, z, games = a.harvest_tensors()
     np.savez(os.path.join(outdir, f"local{rank}_{it}.npz"), states=st.numpy(), pi=pi.numpy(), z=z.numpy(), games=games)
@@ -39,10 +40,10 @@ for it in range(400):
             acc = [[], [], [], [], 0]
         if len(res[3]):
             g = res[3].copy()
-            g[:, 0] += acc[4]
+            g[:, _abi.GR_START] += acc[4]
             acc[0].append(res[0].numpy().copy()), acc[1].append(res[1].numpy().copy()), acc[2].append(res[2].numpy().copy()), acc[3].append(g)
             acc[4] += res[0].shape[0]
-        ranks_seen = set(int(x) >> 20 for gg in acc[3] for x in gg[:, 15])
+        ranks_seen = set(int(x) >> _abi.GR_SLOT_RANK_SHIFT for gg in acc[3] for x in gg[:, _abi.GR_SLOT])
         flag[0] = 1 if ranks_seen == set(range(world)) and it >= 5 else 0
     dist.broadcast(flag, 0)
     if flag.item():
@@ -53,7 +54,7 @@ for j in range(it + 1):
     d = np.load(os.path.join(outdir, f"local{rank}_{j}.npz"))
     g = d["games"].copy()
     if len(g):
-        g[:, 0] += base
+        g[:, _abi.GR_START] += base
     base += d["z"].shape[0]
     parts[0].append(d["states"]), parts[1].append(d["pi"]), parts[2].append(d["z"]), parts[3].append(g)
 np.savez(os.path.join(outdir, f"local{rank}.npz"), states=np.concatenate(parts[0]), pi=np.concatenate(parts[1]), z=np.concatenate(parts[2]),

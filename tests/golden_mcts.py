@@ -1,5 +1,6 @@
 """Helpers shared by the oracle / host-twin / GPU search-parity tests: load an MCTS golden file
-(produced by the reference, tools/gen_golden_mcts.py) and expose its per-move records."""
+(produced by the reference, tools/gen_golden_mcts.py; the stack_mcts_* family at num_stack < 8 by tools/gen_golden_stack.py) and expose
+its per-move records."""
 import glob
 import json
 import os
@@ -16,10 +17,10 @@ def names(real_network=False):
 
 
 class MctsGolden:
-    def __init__(self, name):
-        self.g = np.load(os.path.join(GOLDEN, f"mcts_{name}.npz"))
+    def __init__(self, name, prefix="mcts_"):
+        self.g = np.load(os.path.join(GOLDEN, f"{prefix}{name}.npz"))
         self.cfg = json.loads(str(self.g["config"]))
-        self.A = self.cfg["num_actions"]
+        self.A, self.K = self.cfg["num_actions"], self.cfg.get("num_stack", 8)
 
     def moves_of_game(self, gi):
         return np.flatnonzero(self.g["game"] == gi)
@@ -28,6 +29,6 @@ class MctsGolden:
         return bool(int(self.g[f"g{gi}_finished"]))
 
     def samples(self, gi):
-        n = self.cfg["n"]
-        st = np.unpackbits(self.g[f"g{gi}_states"], axis=1)[:, : 17 * n * n].reshape(-1, 17, n, n).astype(np.int8)
+        n, C = self.cfg["n"], 2 * self.K + 1
+        st = np.unpackbits(self.g[f"g{gi}_states"], axis=1)[:, : C * n * n].reshape(-1, C, n, n).astype(np.int8)
         return st, self.g[f"g{gi}_pis"], self.g[f"g{gi}_zs"], json.loads(str(self.g[f"g{gi}_stats"]))

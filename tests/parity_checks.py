@@ -4,6 +4,7 @@ import json
 import numpy as np
 
 import engine_util as eu
+from alpha_zero_amd import _abi
 import golden_mcts
 from alpha_zero_amd.core.pipeline import game_stats_from_row
 from synth_eval import eval_batch
@@ -15,11 +16,10 @@ def check_go_file(kind, path, n, chunk=2048):
     lists = [mv[off[i]:off[i + 1]].astype(np.int32) for i in range(len(off) - 1)]
     bad = []
     for c0 in range(0, len(lists), chunk):
-        res = eu.replay_env_batch(kind, "go", n, lists[c0:c0 + chunk])
-        for j, (k, ds, do, fin) in enumerate(res):
+        for j, (k, ds, do, fin) in enumerate(zip(*eu.replay_env_batch(kind, "go", n, lists[c0:c0 + chunk]))):
             i = c0 + j
             ok = (k == len(lists[i]) and ds == g["state_digest"][i].tobytes() and do == g["obs_digest"][i].tobytes()
-                  and (fin[8], fin[9]) == tuple(g["areas"][i]))
+                  and (fin[_abi.ENV_AREA_BLACK], fin[_abi.ENV_AREA_WHITE]) == tuple(g["areas"][i]))
             if not ok:
                 bad.append(i)
     return bad, len(lists)
@@ -34,23 +34,22 @@ def check_gomoku_file(kind, path):
     bad = []
     for (size, ntw), ids in groups.items():
         lists = [mv[off[i]:off[i + 1]].astype(np.int32) for i in ids]
-        res = eu.replay_env_batch(kind, "gomoku", size, lists, num_to_win=ntw)
-        for i, (k, ds, do, fin) in zip(ids, res):
+        for i, k, ds, do, fin in zip(ids, *eu.replay_env_batch(kind, "gomoku", size, lists, num_to_win=ntw)):
             ok = (k == off[i + 1] - off[i] and ds == g["state_digest"][i].tobytes() and do == g["obs_digest"][i].tobytes()
-                  and fin[7] == g["meta"][i][2] and fin[6] == g["meta"][i][3])
+                  and fin[_abi.ENV_WINNER] == g["meta"][i][2] and fin[_abi.ENV_REWARD] == g["meta"][i][3])
             if not ok:
                 bad.append(i)
     return bad, len(off) - 1
 
 
-def check_mcts_golden(kind, name, feature_dtype=None):
-    """Batched actor with the recorded randomness injected vs the reference's outputs.
-    Bit-exact: visit counts, chosen moves, root_Q, best_child_Q, evaluation counts, (Go) pi as float64,
-    sample states / z / stats.  Gomoku pi (float32 in the reference, platform-dependent np.power) <= 1e-6."""
-    G = golden_mcts.MctsGolden(name)
+def check_mcts_golden(kind, name, feature_dtype=_abi.FEAT_I8, prefix="mcts_"):
+    """Batched actor with the recorded randomness injected vs the reference's outputs (prefix="stack_mcts_": the goldens at num_stack
+    K < 8).  Bit-exact: visit counts, chosen moves, root_Q, best_child_Q, evaluation counts, (Go) pi as float64, the (state, pi, z)
+    samples of finished games with 2K+1 planes and their stats.  Gomoku pi (float32 in the reference, platform-dependent np.power)
+    <= 1e-6.  Returns (engine counters, number of finished games)."""
+    G = golden_mcts.MctsGolden(name, prefix)
     g, cfg = G.g, G.cfg
-    kw = {} if feature_dtype is None else {"feature_dtype": feature_dtype}
-    logs, (states, pis, zs, games), n_evals, counters = eu.run_golden_selfplay(kind, G, eval_batch, **kw)
+    logs, (states, pis, zs, games), n_evals, counters = eu.run_golden_selfplay(kind, G, eval_batch, feature_dtype)
     for gi in range(cfg["games"]):
         ix = G.moves_of_game(gi)
         for k, i in enumerate(ix):
@@ -64,21 +63,24 @@ def check_mcts_golden(kind, name, feature_dtype=None):
             else:
                 assert np.abs(L["pi"] - g["pi"][i]).max() <= 1e-6, where
             assert n_evals[gi, k] == g["n_evals"][i], where
-    by_slot = {int(row[15]): row for row in games}
+    assert states.shape[1] == 2 * G.K + 1
+    by_slot = {int(row[_abi.GR_SLOT]): row for row in games}
+    finished = 0
     for gi in range(cfg["games"]):
         if not G.finished(gi):
             assert gi not in by_slot
             continue
+        finished += 1
         st, gp, gz, gstats = G.samples(gi)
         row = by_slot[gi]
-        s0, ln = int(row[0]), int(row[1])
-        assert ln == len(st)
-        assert np.array_equal(states[s0:s0 + ln], st)
-        assert np.array_equal(zs[s0:s0 + ln], gz.astype(np.float32))
+        est, epi, ez = eu.samples_of(row, states, pis, zs)
+        assert len(est) == len(st)
+        assert np.array_equal(est, st)
+        assert np.array_equal(ez, gz.astype(np.float32))
         if cfg["game"] == "go":
-            assert np.array_equal(pis[s0:s0 + ln], gp.astype(np.float32))
+            assert np.array_equal(epi, gp.astype(np.float32))
         else:
-            assert np.abs(pis[s0:s0 + ln] - gp).max() <= 1e-6
+            assert np.abs(epi - gp).max() <= 1e-6
         stats = game_stats_from_row(row, game=cfg["game"], komi=7.5, resign_threshold=cfg.get("resign_threshold", -1.0))
         assert json.loads(json.dumps(stats)) == gstats, (stats, gstats)
-    return counters
+    return counters, finished

@@ -13,6 +13,7 @@ sys.path.insert(0, HERE)
 rank, world, outdir = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3]
 dist.init_process_group("gloo", rank=rank, world_size=world)
 import engine_util as eu  # noqa: E402
+from alpha_zero_amd import _abi  # noqa: E402
 from alpha_zero_amd.core.gather import gather_samples  # noqa: E402
 from alpha_zero_amd.core.network import AlphaZeroNet  # noqa: E402
 from alpha_zero_amd.core.pipeline import SelfPlayActor  # noqa: E402
@@ -28,7 +29,7 @@ for it in range(400):
     assert st.shape[1:] == (9, 5, 5)
     g = games.copy()
     if len(g):
-        g[:, 0] += local[4]
+        g[:, _abi.GR_START] += local[4]
     local[0].append(st.numpy().copy()), local[1].append(pi.numpy().copy()), local[2].append(z.numpy().copy()), local[3].append(g)
     local[4] += st.shape[0]
     res = gather_samples(st.clone(), pi.clone(), z.clone(), games, dst=0)
@@ -36,10 +37,10 @@ for it in range(400):
     if rank == 0:
         if len(res[3]):
             g = res[3].copy()
-            g[:, 0] += acc[4]
+            g[:, _abi.GR_START] += acc[4]
             acc[0].append(res[0].numpy().copy()), acc[1].append(res[1].numpy().copy()), acc[2].append(res[2].numpy().copy()), acc[3].append(g)
             acc[4] += res[0].shape[0]
-        ranks_seen = set(int(x) >> 20 for gg in acc[3] for x in gg[:, 15])
+        ranks_seen = set(int(x) >> _abi.GR_SLOT_RANK_SHIFT for gg in acc[3] for x in gg[:, _abi.GR_SLOT])
         flag[0] = 1 if ranks_seen == set(range(world)) and it >= 3 else 0
     dist.broadcast(flag, 0)
     if flag.item():

@@ -8,6 +8,7 @@ import numpy as np
 import torch
 
 import engine_util as eu
+from alpha_zero_amd import _abi
 from alpha_zero_amd.core.network import AlphaZeroNet
 from alpha_zero_amd.core.pipeline import SelfPlayActor
 
@@ -71,6 +72,11 @@ def test_actor_gomoku_and_weight_swap():
         assert stats["game_result"] in ("B+1.0", "W+1.0", "DRAW")
 
 
+def _assert_games_tile_the_samples(games):
+    order = games[np.argsort(games[:, _abi.GR_START])]
+    assert order[0, _abi.GR_START] == 0 and np.all(order[1:, _abi.GR_START] == np.cumsum(order[:-1, _abi.GR_LENGTH]))
+
+
 def test_sample_gather_two_ranks_gloo(tmp_path):
     """N > 1 data path: finished-game tensors of every rank arrive on rank 0 in rank order (gloo, world_size 2)."""
     script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "gather_worker.py")
@@ -79,24 +85,18 @@ def test_sample_gather_two_ranks_gloo(tmp_path):
     assert all(p.wait(timeout=300) == 0 for p in procs)
     out = np.load(os.path.join(str(tmp_path), "rank0.npz"))
     games = out["games"]
-    assert len(games) >= 2 and out["states"].shape[0] == out["z"].shape[0] == out["pi"].shape[0] == games[:, 1].sum()
+    assert len(games) >= 2 and out["states"].shape[0] == out["z"].shape[0] == out["pi"].shape[0] == games[:, _abi.GR_LENGTH].sum()
     # starts are rebased: games tile the sample range without overlap
-    order = np.argsort(games[:, 0])
-    assert games[order[0], 0] == 0 and np.all(games[order][1:, 0] == np.cumsum(games[order][:-1, 1]))
-    assert set(np.unique(games[:, 15] >> 20)) == {0, 1}
+    _assert_games_tile_the_samples(games)
+    assert set(np.unique(games[:, _abi.GR_SLOT] >> _abi.GR_SLOT_RANK_SHIFT)) == {0, 1}
     # each rank's samples are byte-identical to what that rank harvested locally
     for r in range(2):
-        loc = np.load(os.path.join(str(tmp_path), f"local{r}.npz"))
-        mine = games[(games[:, 15] >> 20) == r]
-        assert len(mine) == len(loc["games"])
-        for row, lrow in zip(mine[np.argsort(mine[:, 0])], loc["games"][np.argsort(loc["games"][:, 0])]):
-            assert np.array_equal(out["states"][row[0]:row[0] + row[1]], loc["states"][lrow[0]:lrow[0] + lrow[1]])
-            assert np.array_equal(out["z"][row[0]:row[0] + row[1]], loc["z"][lrow[0]:lrow[0] + lrow[1]])
+        eu.assert_rank_samples_gathered(out, r, np.load(os.path.join(str(tmp_path), f"local{r}.npz")))
 
 
 def test_sample_gather_eight_ranks_gloo(tmp_path):
     """The 8-GPU data path on 8 gloo ranks (the only de-risking of the driver's 8-GPU run available without the node):
-    uneven sample counts per rank, ranks that contribute zero samples to a gather (padded exchange), the `rank << 20` slot tag for all
+    uneven sample counts per rank, ranks that contribute zero samples to a gather (padded exchange), the `rank << GR_SLOT_RANK_SHIFT` slot tag for all
     eight ranks, rebased starts -- and every rank's samples byte-identical on rank 0 to what that rank harvested locally."""
     W = 8
     script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "gather_worker.py")
@@ -105,21 +105,14 @@ def test_sample_gather_eight_ranks_gloo(tmp_path):
     assert all(p.wait(timeout=900) == 0 for p in procs)
     out = np.load(os.path.join(str(tmp_path), "rank0.npz"))
     games = out["games"]
-    assert out["states"].shape[0] == out["z"].shape[0] == out["pi"].shape[0] == games[:, 1].sum()
-    order = np.argsort(games[:, 0])
-    assert games[order[0], 0] == 0 and np.all(games[order][1:, 0] == np.cumsum(games[order][:-1, 1]))
-    assert set(np.unique(games[:, 15] >> 20)) == set(range(W)) and set(np.unique(games[:, 15] & 0xFFFFF)) <= set(range(4))
-    counts = [int(((games[:, 15] >> 20) == r).sum()) for r in range(W)]
+    assert out["states"].shape[0] == out["z"].shape[0] == out["pi"].shape[0] == games[:, _abi.GR_LENGTH].sum()
+    _assert_games_tile_the_samples(games)
+    rank = games[:, _abi.GR_SLOT] >> _abi.GR_SLOT_RANK_SHIFT
+    assert set(np.unique(rank)) == set(range(W)) and set(np.unique(games[:, _abi.GR_SLOT] & _abi.GR_SLOT_MASK)) <= set(range(4))
+    counts = [int((rank == r).sum()) for r in range(W)]
     assert min(counts) >= 1 and len(set(counts)) > 1, counts  # uneven by construction (different budgets, sitting out)
     for r in range(W):
-        loc = np.load(os.path.join(str(tmp_path), f"local{r}.npz"))
-        mine = games[(games[:, 15] >> 20) == r]
-        assert len(mine) == len(loc["games"]), (r, len(mine), len(loc["games"]))
-        for row, lrow in zip(mine[np.argsort(mine[:, 0])], loc["games"][np.argsort(loc["games"][:, 0])]):
-            assert np.array_equal(out["states"][row[0]:row[0] + row[1]], loc["states"][lrow[0]:lrow[0] + lrow[1]])
-            assert np.array_equal(out["pi"][row[0]:row[0] + row[1]], loc["pi"][lrow[0]:lrow[0] + lrow[1]])
-            assert np.array_equal(out["z"][row[0]:row[0] + row[1]], loc["z"][lrow[0]:lrow[0] + lrow[1]])
-            assert row[1] == lrow[1] and np.array_equal(row[2:15], lrow[2:15])
+        eu.assert_rank_samples_gathered(out, r, np.load(os.path.join(str(tmp_path), f"local{r}.npz")))
 
 
 def test_actor_loop_writes_reference_csv(tmp_path):
@@ -407,8 +400,7 @@ def test_game_range_rounds_equal_whole_batch_rounds():
             if (r + 1) % 20 == 0:
                 st, pi, z, games = a.harvest_tensors()
                 for row in games:
-                    s0, ln = int(row[0]), int(row[1])
-                    by_uid[int(row[11])] = (st[s0:s0 + ln].clone(), pi[s0:s0 + ln].clone(), z[s0:s0 + ln].clone(), row[1:].copy())
+                    by_uid[int(row[_abi.GR_UID])] = tuple(t.clone() for t in eu.samples_of(row, st, pi, z)) + (np.delete(row, _abi.GR_START),)
         return by_uid, a.counters(), e
 
     whole, c0, _ = play(None)
@@ -445,18 +437,19 @@ def test_harvest_is_deterministic_and_capacity_keeps_a_prefix():
         assert torch.equal(s1, s2) and torch.equal(p1, p2) and torch.equal(z1, z2) and np.array_equal(g1, g2)
     assert sum(len(g) for *_, g in big1) > 20
     for st, pi, z, g in big1 + small:  # rows tile the output without gaps, in game-record order
-        assert st.shape[0] == int(g[:, 1].sum()) and (len(g) == 0 or np.array_equal(g[:, 0], np.concatenate([[0], np.cumsum(g[:, 1])[:-1]])))
+        ln = g[:, _abi.GR_LENGTH]
+        assert st.shape[0] == int(ln.sum()) and (len(g) == 0 or np.array_equal(g[:, _abi.GR_START], np.concatenate([[0], np.cumsum(ln)[:-1]])))
     # a capacity of 60 samples binds (several games of ~25 samples finish per harvest): never more than 60 rows, games only delayed
     assert all(st.shape[0] <= 60 for st, *_ in small) and any(len(g) >= 2 for *_, g in small)
-    uid_big = [int(u) for *_, g in big1 for u in g[:, 11]]
-    uid_small = [int(u) for *_, g in small for u in g[:, 11]]
+    uid_big = [int(u) for *_, g in big1 for u in g[:, _abi.GR_UID]]
+    uid_small = [int(u) for *_, g in small for u in g[:, _abi.GR_UID]]
     assert len(set(uid_small)) == len(uid_small) and len(uid_small) >= 8  # every game at most once
-    first = {int(g[i, 11]): (st[int(g[i, 0]):int(g[i, 0]) + int(g[i, 1])], z[int(g[i, 0]):int(g[i, 0]) + int(g[i, 1])]) for st, _, z, g in big1 for i in range(len(g))}
-    for st, _, z, g in small:  # a game harvested late is the same game (content depends on seed, slot, uid only)
-        for i in range(len(g)):
-            u = int(g[i, 11])
+    first = {int(row[_abi.GR_UID]): eu.samples_of(row, st) for st, _, _, g in big1 for row in g}
+    for st, _, _, g in small:  # a game harvested late is the same game (content depends on seed, slot, uid only)
+        for row in g:
+            u = int(row[_abi.GR_UID])
             if u in first and u < 40:  # first game of a slot: not yet affected by the slots that stalled on a full harvest
-                assert torch.equal(st[int(g[i, 0]):int(g[i, 0]) + int(g[i, 1])], first[u][0])
+                assert torch.equal(eu.samples_of(row, st), first[u])
     assert set(uid_small[:8]) <= set(uid_big)
 
 
@@ -515,7 +508,7 @@ def test_actor_marks_or_drops_the_games_of_a_clamp_window():
         assert clean and not any("evaluator_clamped" in st for _, st in clean) and a.clamped_games == 0
         front = a.clamp_window.next_unharvested.copy()
         a.run_rounds(7)
-        done = a.engine.status()[0][:, 5].copy()
+        done = a.engine.status()[0][:, _abi.STC_GAMES_DONE].copy()
         a.clamp_window.on_event(done)  # what _check_evaluator_range does when the device record shows an event
         expect = int(sum(max(0, int(done[s]) - int(front[s]) + 1) for s in range(8)))  # per slot: unharvested finished games + the one in progress
         after = []

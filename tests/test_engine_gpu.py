@@ -10,6 +10,7 @@ import pytest
 import engine_util as eu
 import golden_mcts
 import parity_checks as pc
+from alpha_zero_amd import _abi
 
 pytestmark = pytest.mark.gpu
 
@@ -74,8 +75,8 @@ def test_gpu_env_vs_oracle_random_playouts_4096_games():
         acts[alive & ~has] = n * n
         out = eng.env_step(acts)
         traj.append((acts.copy(), out["board"].copy(), out["legal"].copy(), out["scalars"].copy()))
-        assert not out["scalars"][alive, 10].any()
-        alive &= out["scalars"][:, 5] == 0
+        assert not out["scalars"][alive, _abi.ENV_ILLEGAL].any()
+        alive &= out["scalars"][:, _abi.ENV_DONE] == 0
     eng.close()
     for g in range(0, G, 37):  # the oracle is the slow side: check every 37th game completely
         env = OracleGoEnv(n)
@@ -86,7 +87,8 @@ def test_gpu_env_vs_oracle_random_playouts_4096_games():
             env.step(int(acts[g]))
             assert np.array_equal(env.board, board[g])
             assert np.array_equal(env.legal_actions.astype(np.int8), legal[g])
-            assert env.ko == sc[g, 0] and env.caps == (sc[g, 1], sc[g, 2]) and env.steps == sc[g, 3]
+            assert (env.ko == sc[g, _abi.ENV_KO] and env.caps == (sc[g, _abi.ENV_CAPS_BLACK], sc[g, _abi.ENV_CAPS_WHITE])
+                    and env.steps == sc[g, _abi.ENV_STEPS])
 
 
 # ---- Python boundary on the GPU: env classes, uct_search drop-ins, Dihedral-8 -------------------------
@@ -127,8 +129,6 @@ def test_gpu_dihedral():
 @pytest.mark.parametrize("name", ["go9_p8_s200", "gomoku13_p8_s200"])
 def test_gpu_tiled_feature_layout_matches_reference(name, fmt):
     """AZSP_FEAT_BF16_TILED / AZSP_FEAT_F16_SPLIT observation planes on the device: golden games replay bit-exactly through the decoded tensor."""
-    from alpha_zero_amd import _abi
-
     pc.check_mcts_golden("gpu", name, feature_dtype=_abi.FEAT_BF16_TILED if fmt == "bf16_tiled" else _abi.FEAT_F16_SPLIT)
 
 
@@ -253,13 +253,7 @@ def _selfplay_properties(n, G, sims, blocks, filters, open_lo, open_hi, rounds, 
     digests = []
     # short games so that many finish: long random openings, then the search plays them out
     rng = np.random.Generator(np.random.PCG64(5))
-    plies = rng.integers(open_lo, open_hi + 1, size=G)
-    out = a.engine.env_step(None)
-    for t in range(int(plies.max())):
-        legal = out["legal"][:, :NP].astype(bool)
-        r = rng.random(legal.shape) * legal
-        acts = np.where((plies > t) & legal.any(axis=1) & (out["scalars"][:, 5] == 0), r.argmax(axis=1), -2).astype(np.int32)
-        out = a.engine.env_step(acts)
+    eu.random_openings(a.engine, rng.integers(open_lo, open_hi + 1, size=G), rng)
     games = samples = 0
     for _ in range(rounds // 50):
         a.run_rounds(50)
@@ -273,15 +267,7 @@ def _selfplay_properties(n, G, sims, blocks, filters, open_lo, open_hi, rounds, 
         assert np.all(np.isin(zc, (-1.0, 0.0, 1.0))) and np.allclose(pic.sum(axis=1), 1.0, atol=1e-4)
         occupied = (stc[:, 0] + stc[:, 1]).reshape(len(stc), NP) > 0   # planes 0 / 1: the current position's stones
         assert not np.any((pic[:, :NP] > 0) & occupied)               # no visit on an occupied point
-        for row in rows:
-            s0, ln = int(row[0]), int(row[1])
-            assert 0 < ln <= 2 * NP
-            black = stc[s0:s0 + ln, 16, 0, 0]
-            assert np.all(black[1:] != black[:-1])
-            if int(row[2]) != 0:
-                wb = 1 if int(row[2]) == 1 else 0
-                zz = zc[s0:s0 + ln]
-                assert np.all(zz[black == wb] == 1) and np.all(zz[black != wb] == -1)
+        eu.assert_game_samples(rows, stc, zc, max_length=2 * NP)
         games += len(rows)
         samples += len(zc)
     c = a.counters()
@@ -367,13 +353,7 @@ def test_gpu_gomoku13_full_size_c2_properties_and_same_seed_stream():
         assert "split-precision" in act.evaluator_path and "hand-written" in act.evaluator_path, act.evaluator_path
         assert "azsp_resblock_split" in act.evaluator_path  # the tower runs on the one-launch-per-block kernel (az_resblock_sp17.h)
         rng = np.random.Generator(np.random.PCG64(9))
-        plies = rng.integers(24, 35, size=G)
-        out = act.engine.env_step(None)
-        for t in range(int(plies.max())):
-            legal = out["legal"][:, :NP].astype(bool)
-            r = rng.random(legal.shape) * legal
-            acts = np.where((plies > t) & legal.any(axis=1) & (out["scalars"][:, 5] == 0), r.argmax(axis=1), -2).astype(np.int32)
-            out = act.engine.env_step(acts)
+        eu.random_openings(act.engine, rng.integers(24, 35, size=G), rng)
         digests, games, samples = [], 0, 0
         for _ in range(9):
             act.run_rounds(50)
@@ -386,17 +366,7 @@ def test_gpu_gomoku13_full_size_c2_properties_and_same_seed_stream():
                 assert np.all(np.isin(zc, (-1.0, 0.0, 1.0))) and np.allclose(pic.sum(axis=1), 1.0, atol=1e-4)
                 occupied = (stc[:, 0] + stc[:, 1]).reshape(len(stc), NP) > 0
                 assert not np.any((pic > 0) & occupied)
-                for row in rows:
-                    s0, ln = int(row[0]), int(row[1])
-                    assert 0 < ln <= 44
-                    black = stc[s0:s0 + ln, 16, 0, 0]
-                    assert np.all(black[1:] != black[:-1])
-                    if int(row[2]) != 0:
-                        wb = 1 if int(row[2]) == 1 else 0
-                        zz = zc[s0:s0 + ln]
-                        assert np.all(zz[black == wb] == 1) and np.all(zz[black != wb] == -1)
-                    else:
-                        assert np.all(zc[s0:s0 + ln] == 0)
+                eu.assert_game_samples(rows, stc, zc, max_length=44)
             games += len(rows)
             samples += len(zc)
         c = act.counters()
@@ -463,9 +433,9 @@ def test_gpu_game_range_rounds_and_half_batch_forwards_equal_whole_batch_rounds(
             st, pi, z, games = e.harvest(sample_capacity=2 * G * 25, max_games=2 * G)
             st, pi, z = st.cpu(), pi.cpu(), z.cpu()
             for row in games:  # the harvest kernel hands out output rows first come first served: key the games by their uid
-                a, ln = int(row[0]), int(row[1])
-                assert int(row[11]) not in games_by_uid
-                games_by_uid[int(row[11])] = (st[a:a + ln].clone(), pi[a:a + ln].clone(), z[a:a + ln].clone(), row[1:].copy())
+                uid = int(row[_abi.GR_UID])
+                assert uid not in games_by_uid
+                games_by_uid[uid] = tuple(t.clone() for t in eu.samples_of(row, st, pi, z)) + (np.delete(row, _abi.GR_START),)
         out.append((games_by_uid, act.counters()))
         del act
     (ga, c0), (gb, c1) = out

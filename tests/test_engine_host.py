@@ -66,6 +66,29 @@ def test_product_library_exports_every_abi_symbol():
     hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "azsp.h")).read()
     declared = set(re.findall(r"\b(azsp_[a-z_0-9]+)\s*\(", hdr))
     assert declared == set(_abi.SYMBOLS)
+    # the fixed-width rows: every enumerator of the header's enums equals its _abi mirror (the name without AZSP_) ...
+    rows = {}
+    for body in re.findall(r"\benum\s*\{(.*?)\}", hdr, re.S):
+        for value, name in enumerate(re.findall(r"\b(AZSP_[A-Z]+_[A-Z_]+)\b", re.sub(r"/\*.*?\*/", "", body, flags=re.S))):
+            rows[name[5:]] = value
+    assert {n.split("_")[0] for n in rows} == {"STC", "STQ", "ENV", "GR", "GX", "SQ"} and len(rows) == 52
+    assert rows == {n: getattr(_abi, n, None) for n in rows}
+    shift = int(re.search(r"#define AZSP_GR_SLOT_RANK_SHIFT (\d+)", hdr).group(1))
+    assert shift == _abi.GR_SLOT_RANK_SHIFT and _abi.GR_SLOT_MASK == (1 << shift) - 1 and "((1 << AZSP_GR_SLOT_RANK_SHIFT) - 1)" in hdr
+    # ... and each _COUNT is the width Engine allocates
+    import engine_util as eu
+    from alpha_zero_amd.core.engine import Engine, EngineConfig
+
+    binding, dev = eu.backend("host")
+    eng = Engine(binding, EngineConfig(game="go", board_size=5, num_games=2, num_parallel=1, num_simulations=2, stop_after_move=True, log_moves=True,
+                                       log_capacity=1), device=dev)
+    st, q = eng.status()
+    dst, dq = eng.dropin_step()[:2]
+    games = eng.harvest()[3]
+    widths = dict(STC_COUNT=st.shape[1], STQ_COUNT=q.shape[1], ENV_COUNT=eng.env_step(None)["scalars"].shape[1], GR_COUNT=games.shape[1],
+                  GX_COUNT=eng.last_extra.shape[1], SQ_COUNT=eng.get_search(0)[2].shape[0])
+    eng.close()
+    assert (dst.shape[1], dq.shape[1]) == (st.shape[1], q.shape[1]) and widths == {n: rows[n] for n in widths}
 
 
 def test_product_refuses_to_run_without_gpu():

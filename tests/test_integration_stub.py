@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import engine_util as eu
+from alpha_zero_amd import _abi
 
 
 class AzspConfig(C.Structure):  # copied from INTEGRATION.md: 26 int32, 4 float, 4 double, 1 uint64
@@ -44,8 +45,8 @@ def _run_stub(kind):
     states = torch.empty((4 * G * 50, 17, n, n), dtype=torch.int8, device=dev)
     pi = torch.empty((4 * G * 50, A), dtype=torch.float32, device=dev)
     z = torch.empty((4 * G * 50,), dtype=torch.float32, device=dev)
-    games = np.zeros((2 * G, 16), dtype=np.int32)
-    extra = np.zeros((2 * G, 4), dtype=np.int32)
+    games = np.zeros((2 * G, _abi.GR_COUNT), dtype=np.int32)
+    extra = np.zeros((2 * G, _abi.GX_COUNT), dtype=np.int32)
     got, thr_seen = 0, set()
     ns, ng = C.c_int32(0), C.c_int32(0)
     for r in range(3000):
@@ -60,9 +61,9 @@ def _run_stub(kind):
             assert lib.azsp_harvest(eng, C.c_void_p(states.data_ptr()), C.c_void_p(pi.data_ptr()), C.c_void_p(z.data_ptr()), states.shape[0],
                                     V(games.ctypes.data), 2 * G, C.byref(ns), C.byref(ng), None) == 0
             for k in range(ng.value):
-                thr = float(np.array([extra[k, 1], extra[k, 2]], dtype=np.int32).view(np.float64)[0])
-                thr_seen.add((int(games[k, 12]), thr))
-                assert games[k, 1] > 0 and abs(float(pi[games[k, 0]].sum()) - 1.0) < 1e-4
+                thr = float(np.array([extra[k, _abi.GX_THRESHOLD_LO], extra[k, _abi.GX_THRESHOLD_HI]], dtype=np.int32).view(np.float64)[0])
+                thr_seen.add((int(games[k, _abi.GR_TRAINING_STEPS]), thr))
+                assert games[k, _abi.GR_LENGTH] > 0 and abs(float(pi[games[k, _abi.GR_START]].sum()) - 1.0) < 1e-4
             got += ng.value
             if (123, -0.5) in thr_seen and got >= 2 * G:
                 break

@@ -6,8 +6,11 @@ import pytest
 import torch
 
 import engine_util as eu
+import golden_mcts
+import parity_checks as pc
 import stack_checks as sc
 from alpha_zero_amd import _abi
+from synth_eval import eval_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -20,14 +23,14 @@ def test_gpu_playouts_match_reference(game, n, k):
 @pytest.mark.parametrize("fmt", ["i8", "f16_split", "bf16"])
 @pytest.mark.parametrize("name", sc.MCTS)
 def test_gpu_search_and_actor_match_reference(name, fmt):
-    sc.check_mcts("gpu", name, sc.FEATS[fmt])
+    pc.check_mcts_golden("gpu", name, sc.FEATS[fmt], prefix=sc.MCTS_PREFIX)
 
 
 @pytest.mark.parametrize("k", [1, 4, 8])
 def test_gpu_every_feature_layout_is_the_plain_planes(k):
     """One position set (the first rounds of the go5 golden's games) written under every feature_dtype decodes to the I8 planes; at
     K = 8 the tiled / split tensors are byte for byte the 17-plane encodings (engine_util.tile_features / split_features)."""
-    G = sc.StackGolden("go5_p4_s48_k2")
+    G = golden_mcts.MctsGolden("go5_p4_s48_k2", sc.MCTS_PREFIX)
     got = {}
     raw = {}
     for fmt, fd in sc.FEATS.items():
@@ -39,7 +42,7 @@ def test_gpu_every_feature_layout_is_the_plain_planes(k):
                 if r == 20:
                     raw[fmt] = eng.features.clone().cpu()
 
-        sc.run_selfplay("gpu", G, fd, on_features=keep, num_stack=k, max_rounds=40)
+        eu.run_golden_selfplay("gpu", G, eval_batch, fd, num_stack=k, on_features=keep, max_rounds=40)
         got[fmt] = np.stack(seen)
     assert got["i8"].shape[2] == 2 * k + 1
     for fmt in sc.FEATS:
@@ -74,7 +77,7 @@ def test_gpu_split_evaluator_on_engine_features_k4(game, n, filters):
         eng.priors.copy_(torch.from_numpy(rng.dirichlet(np.ones(A), eng.rows).astype(np.float32)))
         eng.values.copy_(torch.from_numpy(rng.uniform(-0.5, 0.5, eng.rows).astype(np.float32)))
         eng.round()
-    planes = sc.decode_features(eng)
+    planes = eu.decode_features(eng)
     assert planes.shape == (eng.rows, 9, n, n) and planes[:, :8].any()
     pri = torch.zeros(eng.rows, A, device="cuda")
     val = torch.zeros(eng.rows, device="cuda")

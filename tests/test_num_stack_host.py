@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import engine_util as eu
+import parity_checks as pc
 import stack_checks as sc
 from alpha_zero_amd import _abi
 from alpha_zero_amd.core.engine import Engine, EngineConfig
@@ -23,18 +24,18 @@ def test_playouts_match_reference(game, n, k):
 
 @pytest.mark.parametrize("name", sc.MCTS)
 def test_search_and_actor_match_reference(name):
-    sc.check_mcts("host", name)
+    pc.check_mcts_golden("host", name, prefix=sc.MCTS_PREFIX)
 
 
 def test_samples_of_finished_games_have_2k_plus_1_planes():
-    assert sc.check_mcts("host", "go5_p4_s48_k2") == 3
+    assert pc.check_mcts_golden("host", "go5_p4_s48_k2", prefix=sc.MCTS_PREFIX)[1] == 3
 
 
 @pytest.mark.parametrize("fmt", ["f32", "bf16", "f16", "f16_split"])
 @pytest.mark.parametrize("name", ["go5_p4_s48_k2", "gomoku13_p8_s200_k1"])
 def test_feature_layouts_match_reference(name, fmt):
     """2K+1 planes written in every feature layout decode to the reference's planes (the decoder checks that channels 2K+1..31 stay zero)."""
-    sc.check_mcts("host", name, sc.FEATS[fmt])
+    pc.check_mcts_golden("host", name, sc.FEATS[fmt], prefix=sc.MCTS_PREFIX)
 
 
 @pytest.mark.parametrize("k", [0, 9, -1])
@@ -136,13 +137,7 @@ def test_sample_gather_two_ranks_gloo_k4(tmp_path):
     assert all(p.wait(timeout=300) == 0 for p in procs)
     out = np.load(os.path.join(str(tmp_path), "rank0.npz"))
     games = out["games"]
-    assert out["states"].shape[1:] == (9, 5, 5) and len(games) >= 2 and out["states"].shape[0] == games[:, 1].sum()
-    assert set(np.unique(games[:, 15] >> 20)) == {0, 1}
+    assert out["states"].shape[1:] == (9, 5, 5) and len(games) >= 2 and out["states"].shape[0] == games[:, _abi.GR_LENGTH].sum()
+    assert set(np.unique(games[:, _abi.GR_SLOT] >> _abi.GR_SLOT_RANK_SHIFT)) == {0, 1}
     for r in range(2):
-        loc = np.load(os.path.join(str(tmp_path), f"local{r}.npz"))
-        mine = games[(games[:, 15] >> 20) == r]
-        assert len(mine) == len(loc["games"])
-        for row, lrow in zip(mine[np.argsort(mine[:, 0])], loc["games"][np.argsort(loc["games"][:, 0])]):
-            assert np.array_equal(out["states"][row[0]:row[0] + row[1]], loc["states"][lrow[0]:lrow[0] + lrow[1]])
-            assert np.array_equal(out["pi"][row[0]:row[0] + row[1]], loc["pi"][lrow[0]:lrow[0] + lrow[1]])
-            assert np.array_equal(out["z"][row[0]:row[0] + row[1]], loc["z"][lrow[0]:lrow[0] + lrow[1]])
+        eu.assert_rank_samples_gathered(out, r, np.load(os.path.join(str(tmp_path), f"local{r}.npz")))

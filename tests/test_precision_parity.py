@@ -25,6 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _searched_policies(net, game, n, dtype, G, sims, P, stagger, seed=7, split_tower=None):
+    import engine_util as eu
     from alpha_zero_amd import _abi, _lib
     from alpha_zero_amd.core.pipeline import SelfPlayActor
 
@@ -33,26 +34,20 @@ def _searched_policies(net, game, n, dtype, G, sims, P, stagger, seed=7, split_t
                         use_split_evaluator=split_tower is not False)  # fp32: the split-precision kernels, or (False) the library's fp32 convolutions
     e = act.engine
     rng = np.random.Generator(np.random.PCG64(4321))
-    plies = rng.integers(0, stagger + 1, size=G)
-    out = e.env_step(None)
-    for t in range(int(plies.max())):
-        legal = out["legal"][:, : n * n].astype(bool)
-        r = rng.random(legal.shape) * legal
-        acts = np.where((plies > t) & legal.any(axis=1) & (out["scalars"][:, 5] == 0), r.argmax(axis=1), -2).astype(np.int32)
-        out = e.env_step(acts)
-    live = out["scalars"][:, 5] == 0
+    out = eu.random_openings(e, rng.integers(0, stagger + 1, size=G), rng)
+    live = out["scalars"][:, _abi.ENV_DONE] == 0
     for _ in range(4 * (sims // P + 4)):
         act.run_round()
         st, _ = e.status()
-        if np.all((st[:, 0] == _abi.ST_IDLE) | ~live):
+        if np.all((st[:, _abi.STC_STATUS] == _abi.ST_IDLE) | ~live):
             break
     st, q = e.status()
-    assert np.all((st[:, 0] == _abi.ST_IDLE) | ~live)
+    assert np.all((st[:, _abi.STC_STATUS] == _abi.ST_IDLE) | ~live)
     pis, vis, moves = [], [], []
     for g in range(G):
         pi, cn, qq = e.get_search(g, 0)
-        pis.append(pi), moves.append(int(qq[3])), vis.append(cn.astype(np.float64) / max(1.0, float(cn.sum())))
-    return np.array(pis), np.array(vis), np.array(moves), q[:, 0].copy(), live, act.tiled_features
+        pis.append(pi), moves.append(int(qq[_abi.SQ_MOVE])), vis.append(cn.astype(np.float64) / max(1.0, float(cn.sum())))
+    return np.array(pis), np.array(vis), np.array(moves), q[:, _abi.STQ_ROOT_Q].copy(), live, act.tiled_features
 
 
 def _compare(name, net, game, n, G, sims, P, stagger):

@@ -18,6 +18,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from alpha_zero_amd import _abi
 from alpha_zero_amd.core.network import AlphaZeroNet, InferenceNet, split_weights_f16
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -205,7 +206,7 @@ def test_gpu_no_unmarked_game_from_a_clamp_window():
 
     def take():
         st, pi, z, games = a.harvest_tensors()
-        rows_seen.extend((int(r[11]) % G, int(r[11]) // G, bool(m)) for r, m in zip(games, a.last_harvest_clamped))
+        rows_seen.extend((int(r[_abi.GR_UID]) % G, int(r[_abi.GR_UID]) // G, bool(m)) for r, m in zip(games, a.last_harvest_clamped))
 
     for _ in range(400):  # (a 9x9 game takes a few hundred rounds at this budget)
         a.run_rounds(10)
@@ -214,12 +215,12 @@ def test_gpu_no_unmarked_game_from_a_clamp_window():
             break
     assert a.poll_evaluator_range() == 0 and rows_seen and not any(m for _, _, m in rows_seen)
     n_clean = len(rows_seen)
-    done0 = a.engine.status()[0][:, 5].copy()            # the last clean poll: games with index < done0[slot] finished before the window
+    done0 = a.engine.status()[0][:, _abi.STC_GAMES_DONE].copy()            # the last clean poll: games with index < done0[slot] finished before the window
     front = a.clamp_window.next_unharvested.copy()
     good_bias = a.infer.b_sp[1].clone()
     a.infer.b_sp[1].fill_(1.0e6)                          # in place: the captured graph reads it -- the next forwards clamp
     a.run_rounds(3)
-    done1 = a.engine.status()[0][:, 5].copy()
+    done1 = a.engine.status()[0][:, _abi.STC_GAMES_DONE].copy()
     with warnings.catch_warnings(record=True) as w:
         warnings.simplefilter("always")
         assert a.poll_evaluator_range() > 0               # the detecting poll: repair + the window is remembered

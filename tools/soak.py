@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from alpha_zero_amd import _abi
 from alpha_zero_amd.core.network import AlphaZeroNet
 from alpha_zero_amd.core.pipeline import SelfPlayActor
 
@@ -34,16 +35,16 @@ for r in range(0, rounds, 50):
         assert np.all(np.isin(zc, (-1.0, 0.0, 1.0)))
         assert np.allclose(pic.sum(axis=1), 1.0, atol=1e-4), float(np.abs(pic.sum(axis=1) - 1).max())
         for row in rows:
-            s0, ln = int(row[0]), int(row[1])
+            s0, ln, winner = int(row[_abi.GR_START]), int(row[_abi.GR_LENGTH]), int(row[_abi.GR_WINNER])
             assert 0 < ln <= 2 * n * n
             black = stc[s0:s0 + ln, 16, 0, 0]
             assert black[0] == 1 and np.all(black[1:] != black[:-1])
             zz = zc[s0:s0 + ln]
-            if int(row[2]) != 0:  # winner exists: its samples are +1, the other's -1
-                wb = 1 if int(row[2]) == 1 else 0
+            if winner != 0:  # winner exists: its samples are +1, the other's -1
+                wb = 1 if winner == 1 else 0
                 assert np.all(zz[black == wb] == 1) and np.all(zz[black != wb] == -1)
             lens.append(ln)
-            results[int(row[2])] = results.get(int(row[2]), 0) + 1
+            results[winner] = results.get(winner, 0) + 1
         games += len(rows)
         samples += len(zc)
 cnt = actor.counters()

@@ -7,6 +7,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from alpha_zero_amd import _abi  # noqa: E402
 from alpha_zero_amd.core.network import AlphaZeroNet  # noqa: E402
 from alpha_zero_amd.core.pipeline import SelfPlayActor  # noqa: E402
 
@@ -38,6 +39,6 @@ for r in range(240):
     if harvest and (r + 1) % 40 == 0:
         gw = W.harvest_tensors()[3]
         gs = S.harvest_tensors()[3]
-        print("round", r, "harvested", len(gw), len(gs), "same uid sets", set(gw[:, 11].tolist()) == set(gs[:, 11].tolist()), flush=True)
+        print("round", r, "harvested", len(gw), len(gs), "same uid sets", set(gw[:, _abi.GR_UID].tolist()) == set(gs[:, _abi.GR_UID].tolist()), flush=True)
 else:
     print("no difference in 240 rounds")
