@@ -214,6 +214,9 @@ class InferenceNet(nn.Module):
         self.use_fused_block = True  # 64-filter towers: azsp_resblock_tiled instead of two azsp_conv3x3_tiled launches per block
         self.use_split_tower = True  # fp32 networks: azsp_conv3x3_split (hi + lo f16 pairs, three MFMA products) instead of the library
         self.use_split_heads = True  # ... and azsp_split_features / azsp_stem_split / azsp_head_split around it (whole evaluator hand-written)
+        # opt-in: the WHOLE fp32-class evaluator on boards without a tailored stem (19x19 / 13x13 Go, 15x15 Gomoku, 256 filters ...): the
+        # wave-per-tile stem k_stem_spg in front of the wave-per-tile tower, azsp_head_split behind it -- instead of the library stem and heads
+        self.use_split_any_board = False
         self.use_fused_fc = True
         self.mf = torch.channels_last if channels_last else torch.contiguous_format
         self.stem_pad = net.conv_block[0].padding[0]
@@ -342,7 +345,8 @@ class InferenceNet(nn.Module):
         """The evaluator the forward of this network runs on `device`: (path, fused block, wave-per-tile) with path one of
         'tiled'       the whole evaluator on the tiled bf16 / f16 kernels (azsp_stem_tiled -> tower -> azsp_head_tiled),
         'tiled_tower' the tiled tower behind a library stem and heads,
-        'split'       the whole fp32 evaluator on the split-precision kernels (azsp_stem_split -> azsp_conv3x3_split tower -> azsp_head_split),
+        'split'       the whole fp32 evaluator on the split-precision kernels (azsp_stem_split -> azsp_conv3x3_split tower -> azsp_head_split):
+                      the EVAL_KERNELS shapes, and with use_split_any_board (wave-per-tile = True) every other board of the wave-per-tile tower,
         'split_tower' the split tower behind a library fp32 stem and heads,
         'library'     library convolutions + the azsp_bias_act epilogue;
         fused block: the tower runs one launch per ResNetBlock; wave-per-tile: the split tower runs k_conv3x3_spg."""
@@ -360,12 +364,22 @@ class InferenceNet(nn.Module):
             if whole and self.use_split_heads:
                 return "split", fused, False
             if self.split_tower_shape(*tower):
-                return "split_tower", fused, tower not in self.SPLIT_TOWER_SHAPES
+                wave_per_tile = tower not in self.SPLIT_TOWER_SHAPES
+                if wave_per_tile and self.use_split_any_board and self.use_split_heads and self._split_any_board_ok(tower[1]):
+                    return "split", False, True
+                return "split_tower", fused, wave_per_tile
         return "library", False, False
+
+    def _split_any_board_ok(self, planes):
+        """use_split_any_board: what the wave-per-tile stem (pad 1 or 3, at most 32 input planes) and azsp_head_split (three head planes;
+        its workgroup of four boards keeps 4 * (3 * ceil4(planes^2) + actions + fc_width) floats in at most 64 KB of LDS) take."""
+        lds = 4 * (3 * ((planes * planes + 3) & ~3) + self.num_actions + self.fc_width) * 4
+        return self.stem_ok and self.stem_pad in (1, 3) and self.npol + self.nval == 3 and lds <= 64 * 1024
 
     def supports_split_features(self, board_size, device):
         """True when the WHOLE fp32 evaluator runs on the split-precision kernels (azsp_split_features -> azsp_stem_split ->
-        azsp_conv3x3_split tower -> azsp_head_split): the EVAL_KERNELS shapes of fp32 networks."""
+        azsp_conv3x3_split tower -> azsp_head_split): the EVAL_KERNELS shapes of fp32 networks, and with use_split_any_board every
+        board whose tower runs on the wave-per-tile kernel."""
         return self._path(board_size, device)[0] == "split"
 
     def _scratch(self, kind, slot, key, make):
@@ -510,7 +524,8 @@ class InferenceNet(nn.Module):
     def capture_state(self):
         """Everything a captured forward of this network bakes in besides the (in-place updated) weight tensors: a hipGraph captured
         under another capture_state() must not be replayed."""
-        return (id(self), self.act_shift, self.act_calibrated, self.split_fallback_reason, self.use_split_tower, self.use_fused_block)
+        return (id(self), self.act_shift, self.act_calibrated, self.split_fallback_reason, self.use_split_tower, self.use_fused_block,
+                self.use_split_any_board)
 
     # -- range safety: exact power-of-two activation scale -------------------------------------------------------------------
     MAX_ACT_SHIFT = 9   # beyond 2^-9 the scaled stem weights lose fp32-class accuracy (their hi halves become f16 subnormals)
@@ -691,6 +706,10 @@ class InferenceNet(nn.Module):
             return "hand-written: tiled stem / tower / head / FC kernels (libazsp)" + (", f16 activations and weights" if self.dtype == torch.float16 else "")
         if path == "tiled_tower":
             return "hand-written tower (azsp_conv3x3_tiled) behind a library stem and heads"
+        if path == "split" and wave_per_tile:
+            return ("fp32 class, hand-written on any board (use_split_any_board): split-precision stem and tower on the wave-per-tile kernels "
+                    "(azsp_stem_split: k_stem_spg, azsp_conv3x3_split: k_conv3x3_spg; hi + lo f16 pairs, three MFMA products, fp32 accumulation) / "
+                    "fp32 heads (azsp_head_split)")
         if path == "split":
             tower = ("azsp_resblock_split: one launch per ResNetBlock, intermediate activation in LDS; " if fused else "azsp_conv3x3_split: ")
             return (f"fp32 class, hand-written: split-precision stem / tower ({tower}hi + lo f16 pairs, three MFMA products, "

@@ -106,7 +106,7 @@ class SelfPlayActor:
                  c_puct_base=19652.0, c_puct_init=1.25, warm_up_steps=16, check_resign_after_steps=40, disable_resign_ratio=0.1,
                  resign_threshold=-1.0, komi=7.5, num_to_win=5, seed=1, rank=0, device="cuda", net_dtype=torch.float32,
                  use_graph=True, training_steps=0, binding=None, root_noise=True, deterministic=False, tiled_features=None, engine_kw=None,
-                 use_split_evaluator=True, auto_widen=None, num_stack=8):
+                 use_split_evaluator=True, auto_widen=None, num_stack=8, split_any_board=False):
         """net_dtype: precision class of the leaf evaluator.  The default is the REFERENCE'S: fp32 (pipeline.py:91-123 evaluates in fp32,
         no autocast anywhere) -- on the hand-written split-precision kernels (hi + lo f16 pairs, three MFMA products, fp32 accumulation:
         include/azsp.h azsp_conv3x3_split) for 9x9 x {128, 64} and 13x13 Gomoku x 64 networks, on library fp32 convolutions (announced
@@ -115,6 +115,9 @@ class SelfPlayActor:
         shape has hand-written kernels (tiled bf16 / f16, or the fp32-class stem's split layout); False = always NCHW planes.
         use_split_evaluator: False = an fp32 network is evaluated by the LIBRARY's fp32 convolutions even where the split-precision
         kernels exist (comparison runs: bench.py's fp32_library_companion, tests/test_precision_parity.py).
+        split_any_board: True = InferenceNet.use_split_any_board on every evaluator this actor builds: an fp32 network on a board without a
+        tailored stem (19x19 / 13x13 Go, 15x15 Gomoku, 256 filters) runs stem, tower and heads on the hand-written kernels and the engine
+        writes AZSP_FEAT_F16_SPLIT, instead of the split tower behind a library stem and heads.  Off by default.
         auto_widen: networks of a width without hand-written kernels run as a function-preserving widened copy (network.widen_for_kernels).
         None = on the GPU whenever the widened network actually reaches hand-written kernels (not for library comparison runs, not when
         the caller disabled the kernels' feature layouts); True / False force it.
@@ -132,6 +135,7 @@ class SelfPlayActor:
         self.net_dtype = net_dtype
         self.use_graph = use_graph and self.device.type == "cuda"
         self.use_split_evaluator = bool(use_split_evaluator)
+        self.split_any_board = bool(split_any_board)
         if auto_widen is None:  # widening only pays when the wider network lands on hand-written kernels
             auto_widen = (self.device.type == "cuda" and tiled_features is not False
                           and (net_dtype != torch.float32 or self.use_split_evaluator))
@@ -177,6 +181,7 @@ class SelfPlayActor:
         """The evaluator of `network`, still on the host (what it supports on self.device does not depend on where it lives)."""
         inf = InferenceNet(network, dtype=self.net_dtype, binding=self.binding if self.device.type == "cuda" else None)
         inf.use_split_tower = self.use_split_evaluator
+        inf.use_split_any_board = self.split_any_board
         return inf
 
     def _install(self, infer, training_steps):

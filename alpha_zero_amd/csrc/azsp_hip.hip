@@ -15,6 +15,7 @@
 #include "az_resblock_sp17.h"
 #include "az_conv_sp2.h"
 #include "az_conv_spg.h"
+#include "az_stem_spg.h"
 
 static hipError_t g_last = hipSuccess;
 #define AZ_HIP(x) ((g_last = (x)) == hipSuccess ? 0 : -1)
@@ -327,10 +328,11 @@ static int launch_spg(const void* x, const void* w, const float* bias, const voi
 // there are).  Default 1024 = one wave per SIMD of the chip: the measured crossover (tools/spg_ab.py, profiles/r06_spg_ab.txt: the kernel
 // reads its fragments through L1, a second wave per SIMD doubles its time).  AZSP_SPG_MAX_WAVES sets the initial value (0 = never),
 // azsp_small_batch_waves changes it at run time.
+static constexpr long long SPG_DEFAULT_WAVES = 1024;
 static long long& spg_max_waves() {
     static long long n = [] {
         const char* e = getenv("AZSP_SPG_MAX_WAVES");
-        const long long v = e ? atoll(e) : 1024LL;
+        const long long v = e ? atoll(e) : SPG_DEFAULT_WAVES;
         return v < 0 ? 0LL : v;
     }();
     return n;
@@ -404,11 +406,30 @@ int launch_split_features(const float* src, void* dst, long long boards, int S, 
     const long long nitems = boards * 4 * S * S;
     return launch_k(k_split_features, (unsigned)((nitems + 255) / 256), 256, 0, st, src, (unsigned char*)dst, nitems, cin, S * S, range);
 }
+// (k_stem_spg repeats k_conv3x3_spg's index, ring and accumulator set-up for the stem's geometry: a fix to one belongs in the other too.)
+// k_stem_spg (az_stem_spg.h): the stem with one WAVE per output tile (16 couts x 32 positions) -- any board, pad 1 or 3, 64 / 128 / 256 filters
+template <bool XLO0>
+static int launch_stem_spg(const void* x, const void* w, const float* bias, void* y, long long boards, int n, int C, int pad, int relu, void* st,
+                           unsigned* range) {
+    constexpr int NT = 1, NJ = 2;
+    const int off = pad - 1, S = n + 2 * off;
+    if ((pad != 1 && pad != 3) || n < 1 || S < 3 || S > 64 || (C != 64 && C != 128 && C != 256) || boards < 1 || boards > 0x7fffffffLL) return 1;
+    const long long nct = ((long long)S * S + 15) / 16, items = boards * ((nct + NJ - 1) / NJ) * (C / (16 * NT)), grid = (items + 3) / 4;
+    if (grid > 0x7fffffffLL) return 1;
+    return launch_k(k_stem_spg<XLO0, NT, NJ>, (unsigned)grid, 256, 0, st, (const unsigned char*)x, (const _Float16*)w, bias, (unsigned char*)y, (int)boards,
+                    n, off, C, relu, range);
+}
+// S: the BOARD (the output planes are S + 2 (pad - 1) wide).  The three tailored shapes run their weight-stationary stems unless the call
+// is small (small_batch on the output plane, as the tower: bit-identical results); every other shape runs the wave-per-tile stem.
+// The DEFAULT threshold does not move the tailored shapes (STEM_SPG_DEFAULT_SMALL): they switch only when the caller has raised it.
+static constexpr bool STEM_SPG_DEFAULT_SMALL = false;
 int launch_stem_split(const void* x, const void* w, const float* bias, void* y, long long boards, int S, int C, int pad, int relu, void* st,
                       int x_lo_zero, unsigned* range) {
     const bool sp17 = S == 13 && C == 64 && pad == 3;  // 13x13 boards -> 17x17 planes
-    if (!sp17 && (S != SpGeo9::S || (C != 128 && C != 64) || pad != 1)) return 1;
+    const bool sp9 = S == SpGeo9::S && (C == 128 || C == 64) && pad == 1;
+    const bool small = (pad == 1 || pad == 3) && small_batch(boards, S + 2 * (pad - 1), C) && (STEM_SPG_DEFAULT_SMALL || spg_max_waves() > SPG_DEFAULT_WAVES);
     return with_flag(x_lo_zero != 0, [&](auto XLO0) {
+        if (!(sp17 || sp9) || small) return launch_stem_spg<XLO0>(x, w, bias, y, boards, S, C, pad, relu, st, range);
         if (sp17) return launch_sp17<false, 4, XLO0>(x, w, bias, nullptr, y, boards, relu, st, range);
         return C == 128 ? launch_sp<false, 4, 2, XLO0>(x, w, bias, nullptr, y, boards, relu, st, range)
                         : launch_sp<false, 4, 1, XLO0>(x, w, bias, nullptr, y, boards, relu, st, range);

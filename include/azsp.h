@@ -384,8 +384,13 @@ int azsp_resblock_split(const void* x_dev, const void* w1_split_dev, const float
  *   features with feature_dtype = AZSP_FEAT_F16_SPLIT: that tensor IS the stem's input (what SelfPlayActor does).
  * azsp_stem_split: the stem convolution + BatchNorm + ReLU (network.py:101-110): x from azsp_split_features (board_size x
  *   board_size), w_split [2 planes][9 taps][C out][32 in] f16 (input channels >= the network's zero), y in the tower's split layout
- *   with planes of board_size + 2 (pad - 1): pad = 1 for Go, pad = 3 for Gomoku (network.py:101-105).  On the device: (board 9,
- *   C 128 or 64, pad 1) and (board 13, C 64, pad 3).
+ *   with planes S = board_size + 2 (pad - 1): pad = 1 for Go, pad = 3 for Gomoku (network.py:101-105).  On the device: tailored
+ *   weight-stationary stems for (board 9, C 128 or 64, pad 1) and (board 13, C 64, pad 3); every other board with pad 1 or 3, planes
+ *   3 <= S <= 64 and C = 64, 128 or 256 on the wave-per-tile stem k_stem_spg (csrc/az_stem_spg.h; one wave per 16 couts x 32 positions,
+ *   the embedding margin of pad 3 as zero fragments), AZSP_EINVAL otherwise.  The three tailored shapes run k_stem_spg too -- with
+ *   BIT-IDENTICAL results -- when the call is small by azsp_small_batch_waves (counted on the output planes) AND that limit has been
+ *   raised above its default of 1024: at the default the tailored stems keep every call (see azsp_small_batch_waves).  The host twin
+ *   (tests/hosttwin) restates the tailored shapes only and refuses the others.
  * azsp_head_split: both heads in fp32 in one pass over the tower output (network.py:118-156): the two 1x1 convolutions + BatchNorm +
  *   ReLU (head_w [3][C], head_b [3]: npol policy planes first), policy Linear + softmax over all A actions (pol_fc_wt = the Linear's
  *   weight TRANSPOSED, [npol*S*S][A], inputs in nn.Flatten order), value Linear + ReLU + Linear + tanh (val_fc1_wt transposed
@@ -395,7 +400,8 @@ int azsp_split_features(const float* planes_dev, void* dst_dev, int64_t boards, 
 int azsp_stem_split(const void* x_split32_dev, const void* w_split_dev, const float* bias_dev, void* y_dev, int64_t boards, int32_t board_size,
                     int32_t channels, int32_t pad, int32_t relu, uint32_t* range_rec_dev, void* stream);
 /* azsp_stem_split for inputs whose lo plane is all zero -- values that are exact in f16, i.e. the engine's AZSP_FEAT_F16_SPLIT features (0 / 1
- * observation planes): the lo plane is neither loaded nor multiplied (its product is exactly zero), the result is identical to azsp_stem_split's. */
+ * observation planes): the lo plane is neither loaded nor multiplied (its product is exactly zero), the result is identical to azsp_stem_split's.
+ * The same shapes as azsp_stem_split, on the same kernels (the host twin: the tailored shapes only). */
 int azsp_stem_split_exact(const void* x_split32_dev, const void* w_split_dev, const float* bias_dev, void* y_dev, int64_t boards, int32_t board_size,
                           int32_t channels, int32_t pad, int32_t relu, uint32_t* range_rec_dev, void* stream);
 int azsp_head_split(const void* x_dev, const float* head_w_dev, const float* head_b_dev, const float* pol_fc_wt_dev, const float* pol_fc_b_dev,
@@ -422,7 +428,10 @@ int azsp_split_range_status(uint32_t* events_host, float* max_abs_host, int32_t 
  * Sets the process-wide limit and returns the previous one; a negative argument only queries.  Default 1024 (one wave per SIMD of an
  * MI355X: the measured crossover, profiles/r06_spg_ab.txt), or the environment variable AZSP_SPG_MAX_WAVES; 0 = always the
  * weight-stationary kernels.  Shapes without a weight-stationary kernel (plane sizes 3 .. 64, 64 / 128 / 256 filters) always run
- * k_conv3x3_spg (beyond `waves`: k_conv3x3_spgw, 48-position tiles whose activations a workgroup shares through LDS). */
+ * k_conv3x3_spg (beyond `waves`: k_conv3x3_spgw, 48-position tiles whose activations a workgroup shares through LDS).
+ * azsp_stem_split / azsp_stem_split_exact obey the same limit on their three tailored shapes, but only once it exceeds the default:
+ * 0 = always the tailored stems, a huge value = the wave-per-tile stem k_stem_spg at any board count, the default = the tailored stems:
+ * a conservative choice, NOT a measured one (tools/stem_ab.py is the A/B that would decide it; no run of it is recorded). */
 int64_t azsp_small_batch_waves(int64_t waves);
 
 /* Replay sampling on the device (core/replay.py:72-83 UniformReplay.sample + core/pipeline.py:636-643: the batch
