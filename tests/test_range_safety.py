@@ -10,18 +10,15 @@ split-precision kernels carry every activation as an f16 pair and clamp |v| > 65
   * azsp_conv3x3_split refuses residual == y at 17x17 and computes it correctly at 9x9.
 """
 import ctypes
-import os
+import math
 import warnings
 
-import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
+import split_util as su
 from alpha_zero_amd import _abi
 from alpha_zero_amd.core.network import AlphaZeroNet, InferenceNet, split_weights_f16
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _loud_net(board, filters, blocks, gain, gomoku=False, seed=0):
@@ -68,20 +65,20 @@ def test_range_record_belongs_to_the_caller_host_twin():
     """range_rec_dev: events land in the record the call names; NULL = the library's default record (azsp_split_range_status)."""
     import engine_util as eu
 
-    bnd = eu.hosttwin_binding()
+    dll = eu.hosttwin_binding().dll
     ev, mx = ctypes.c_uint32(0), ctypes.c_float(0.0)
-    assert bnd.dll.azsp_split_range_status(None, None, 1, None) == 0
-    x = torch.tensor([1.0, -1e5, 65504.0, 1e-7, 0.0, 7e4, -2.5e-5, 60000.0]).reshape(1, 8, 1, 1).contiguous(memory_format=torch.channels_last)
-    s = torch.zeros(2 * 8, dtype=torch.float16)
-    rec_a, rec_b = np.zeros(2, dtype=np.uint32), np.zeros(2, dtype=np.uint32)
-    assert bnd.dll.azsp_split_layout(x.data_ptr(), s.data_ptr(), 1, 1, 8, 1, rec_a.ctypes.data, None) == 0
-    assert rec_a[0] == 2 and rec_a[1:].view(np.float32)[0] == 1e5 and rec_b[0] == 0
-    assert bnd.dll.azsp_split_range_status(ctypes.byref(ev), ctypes.byref(mx), 0, None) == 0 and ev.value == 0  # the default record saw nothing
-    assert bnd.dll.azsp_split_range_read(rec_a.ctypes.data, ctypes.byref(ev), ctypes.byref(mx), 1, None) == 0 and ev.value == 2 and mx.value == 1e5
-    assert rec_a[0] == 0 and rec_a[1] == 0  # reset
+    su.default_record(dll, reset=1)
+    x = torch.tensor([1.0, -1e5, 65504.0, 1e-7, 0.0, 7e4, -2.5e-5, 60000.0]).reshape(1, 8, 1, 1)
+    rec_a, rec_b = su.new_record("cpu"), su.new_record("cpu")
+    su.to_split(dll, x, "cpu", rec_a)
+    assert su.read_record(rec_a) == (2, 1e5) and su.read_record(rec_b)[0] == 0
+    assert su.default_record(dll)[0] == 0  # the default record saw nothing
+    assert dll.azsp_split_range_read(rec_a.data_ptr(), ctypes.byref(ev), ctypes.byref(mx), 1, None) == 0 and ev.value == 2 and mx.value == 1e5
+    assert not rec_a.any()  # reset
     x[0, 3, 0, 0] = float("nan")  # a NaN among the fp32 inputs is an event too (recorded as +inf)
-    assert bnd.dll.azsp_split_layout(x.data_ptr(), s.data_ptr(), 1, 1, 8, 1, rec_b.ctypes.data, None) == 0
-    assert rec_b[0] == 3 and np.isinf(rec_b[1:].view(np.float32)[0])
+    su.to_split(dll, x, "cpu", rec_b)
+    ev_b, mx_b = su.read_record(rec_b)
+    assert ev_b == 3 and math.isinf(mx_b)
 
 
 def test_activation_shift_is_function_preserving_host_twin():
@@ -262,12 +259,9 @@ def test_gpu_split_conv_residual_aliasing_contract(S, C):
     r = torch.randn(B, C, S, S, generator=g).abs()
     w = torch.randn(C, C, 3, 3, generator=g) * (2.0 / (9 * C)) ** 0.5
     b = torch.randn(C, generator=g) * 0.1
-    n = dll.azsp_split_bytes(B, S, C) // 2
-    xs, rs, ys = (torch.zeros(n, dtype=torch.float16, device="cuda") for _ in range(3))
-    for src, dst in ((x, xs), (r, rs)):
-        sc = src.cuda().contiguous(memory_format=torch.channels_last)
-        assert dll.azsp_split_layout(sc.data_ptr(), dst.data_ptr(), B, S, C, 1, None, None) == 0
-    wsp, bb = split_weights_f16(w).cuda(), b.cuda()
+    xs, rs = su.to_split(dll, x, "cuda"), su.to_split(dll, r, "cuda")
+    ys = torch.zeros_like(xs)
+    wsp, bb = su.split_params(w, b, "cuda")
     assert dll.azsp_conv3x3_split(xs.data_ptr(), wsp.data_ptr(), bb.data_ptr(), rs.data_ptr(), ys.data_ptr(), B, S, C, 1, None, None) == 0
     torch.cuda.synchronize()
     rc = dll.azsp_conv3x3_split(xs.data_ptr(), wsp.data_ptr(), bb.data_ptr(), rs.data_ptr(), rs.data_ptr(), B, S, C, 1, None, None)
@@ -285,24 +279,14 @@ def test_gpu_split_conv_keeps_f16_subnormal_operands():
     A convolution whose weights are all below f16's smallest normal number (6.1e-5) against fp64."""
     from alpha_zero_amd import _lib
 
-    dll = _lib.load().dll
+    bnd = _lib.load()
     B, C, S = 5, 64, 9
     g = torch.Generator().manual_seed(7)
     x = torch.randn(B, C, S, S, generator=g).abs() * 100.0
     w = torch.randn(C, C, 3, 3, generator=g) * 1e-5  # |w| mostly < 6.1e-5: hi = f16(w) is subnormal
     b = torch.zeros(C)
-    n = dll.azsp_split_bytes(B, S, C) // 2
-    xs, ys = torch.zeros(n, dtype=torch.float16, device="cuda"), torch.zeros(n, dtype=torch.float16, device="cuda")
-    xc = x.cuda().contiguous(memory_format=torch.channels_last)
-    assert dll.azsp_split_layout(xc.data_ptr(), xs.data_ptr(), B, S, C, 1, None, None) == 0
-    wsp, bb = split_weights_f16(w).cuda(), b.cuda()
-    assert float((wsp[0].float().abs() < 6.1e-5).float().mean()) > 0.9
-    assert dll.azsp_conv3x3_split(xs.data_ptr(), wsp.data_ptr(), bb.data_ptr(), None, ys.data_ptr(), B, S, C, 0, None, None) == 0
-    y = torch.empty_like(xc)
-    assert dll.azsp_split_layout(ys.data_ptr(), y.data_ptr(), B, S, C, 0, None, None) == 0
-    torch.cuda.synchronize()
-    y64 = F.conv2d(x.double(), w.double(), None, padding=1)
-    err = (y.cpu().double() - y64).abs().max().item() / y64.abs().max().item()
+    assert float((split_weights_f16(w)[0].float().abs() < 6.1e-5).float().mean()) > 0.9
+    err = su.rel_err(su.split_conv(bnd, x, None, w, b, 0, "cuda").y, su.ref64_conv(x, None, w, b, 0))
     assert err <= 5e-6, err  # flushed subnormals would leave y = 0: an error of 1
 
 
@@ -344,15 +328,14 @@ def test_calibration_pass_and_the_stem_fallback_reason_on_the_host_twin():
     assert 3e5 < peak < 1.9e6, peak
     p64, v64 = _ref64(net, x)
     inf = InferenceNet(net, dtype=torch.float32, binding=bnd)
-    assert bnd.dll.azsp_split_range_status(None, None, 1, None) == 0
+    su.default_record(bnd.dll, reset=1)
     pc, vc = inf.forward_split(x)  # (CPU tensors: no automatic calibration) -- clamps, and the twin's default record says so
-    ev = ctypes.c_uint32(0)
-    assert bnd.dll.azsp_split_range_status(ctypes.byref(ev), None, 1, None) == 0 and ev.value > 0
+    assert su.default_record(bnd.dll, reset=1)[0] > 0
     shift, worst = inf.calibrate_activation_scale(x)
     assert inf.act_calibrated and 3 <= shift <= inf.MAX_ACT_SHIFT and abs(worst / peak - 1) < 1e-3 and not inf.split_fallback_reason
-    assert bnd.dll.azsp_split_range_status(None, None, 1, None) == 0  # (the probing passes clamped by design)
+    su.default_record(bnd.dll, reset=1)  # (the probing passes clamped by design)
     p, v = inf.forward_split(x)
-    assert bnd.dll.azsp_split_range_status(ctypes.byref(ev), None, 1, None) == 0 and ev.value == 0
+    assert su.default_record(bnd.dll, reset=1)[0] == 0
     assert (p.double() - p64).abs().max().item() <= 2e-4 and (v.double() - v64).abs().max().item() <= 2e-4
     far = InferenceNet(_loud_net(9, 64, 1, gain=3e8), dtype=torch.float32, binding=bnd)
     # the STEM's folded weights are beyond the format; the tower goes with it: stem outputs of that size are beyond what its f16 pairs
@@ -388,7 +371,7 @@ def test_loud_stem_weights_fall_back_to_the_library_on_one_fallback_reason_on_th
     with torch.no_grad():
         lg, vr = net(x)
     assert (p - torch.softmax(lg, -1)).abs().max().item() <= 1e-4 and (v - vr.squeeze(1)).abs().max().item() <= 1e-4
-    assert bnd.dll.azsp_split_range_status(None, None, 1, None) == 0
+    su.default_record(bnd.dll, reset=1)
 
 
 def test_range_repair_policy_on_a_made_up_event_on_the_host_twin():

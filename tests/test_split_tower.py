@@ -2,66 +2,25 @@
 matrix cores: azsp_split_layout / azsp_conv3x3_split (include/azsp.h, alpha_zero_amd/csrc/az_conv_sp.h).
 
 Checker = torch in fp64 on the CPU (the same convolution, exact to ~1e-16), with the library's own fp32 convolution measured beside
-the kernel: the statement is "the kernel's error against fp64 is of the size of fp32 round-off", tolerance written in each test."""
+the kernel: the statement is "the kernel's error against fp64 is of the size of fp32 round-off", tolerance written in each test.
+Inputs, launch drivers and references are those of tests/split_util.py."""
 import json
 import os
 
 import pytest
 import torch
-import torch.nn.functional as F
 
-from alpha_zero_amd.core.network import AlphaZeroNet, InferenceNet, split_weights_f16
+import split_util as su
+from alpha_zero_amd.core.network import InferenceNet, split_weights_f16
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CASES = ((False, 1), (True, 1), (True, 0))  # (residual, relu) of one convolution
 
 
-def _inputs(boards, C, S, seed, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(boards, C, S, S, generator=g) * scale
-    x = torch.where(torch.rand(boards, C, S, S, generator=g) < 0.5, torch.zeros(()), x.abs())  # post-ReLU-like: half zeros
-    x[:, : C // 8] *= 37.0    # a few loud channels ...
-    x[:, -C // 8 :] *= 3e-3   # ... and a few quiet ones
-    r = torch.randn(boards, C, S, S, generator=g).abs() * scale
-    w = torch.randn(C, C, 3, 3, generator=g) * (2.0 / (9 * C)) ** 0.5
-    b = torch.randn(C, generator=g) * 0.1
-    return x, r, w, b
-
-
-def _run_split_conv(bnd, x, r, w, b, relu, device):
-    """x, r: [B,C,S,S] fp32 -> y [B,C,S,S] fp32 through split_layout -> conv3x3_split -> split_layout."""
-    B, C, S, _ = x.shape
-    dll = bnd.dll
-    xc = x.to(device).contiguous(memory_format=torch.channels_last)
-    n = dll.azsp_split_bytes(B, S, C) // 2
-    assert n == B * 2 * S * S * C
-    xs, ys = torch.zeros(n, dtype=torch.float16, device=device), torch.zeros(n, dtype=torch.float16, device=device)
-    assert dll.azsp_split_layout(xc.data_ptr(), xs.data_ptr(), B, S, C, 1, None, None) == 0
-    rs = None
-    if r is not None:
-        rc = r.to(device).contiguous(memory_format=torch.channels_last)
-        rs = torch.zeros(n, dtype=torch.float16, device=device)
-        assert dll.azsp_split_layout(rc.data_ptr(), rs.data_ptr(), B, S, C, 1, None, None) == 0
-    wsp, bb = split_weights_f16(w).to(device), b.float().to(device)
-    assert dll.azsp_conv3x3_split(xs.data_ptr(), wsp.data_ptr(), bb.data_ptr(), rs.data_ptr() if rs is not None else None, ys.data_ptr(),
-                                  B, S, C, relu, None, None) == 0
-    y = torch.empty_like(xc)
-    assert dll.azsp_split_layout(ys.data_ptr(), y.data_ptr(), B, S, C, 0, None, None) == 0
-    # the layout round trip of the input itself: 22-bit significands
-    back = torch.empty_like(xc)
-    assert dll.azsp_split_layout(xs.data_ptr(), back.data_ptr(), B, S, C, 0, None, None) == 0
-    if device != "cpu":
-        torch.cuda.synchronize()
-    # |v - hi - lo / 2048| <= 2^-22 |v| (+ the fp32 rounding of the join); below f16's normal range the lo half is a multiple of
-    # 2^-24 / 2048 = 2^-35: the excess over that absolute floor, relative to |v|
-    rt = (((back.cpu() - x).abs() - 2.0 ** -35).clamp_min(0) / x.abs().clamp_min(1e-30)).max().item()
-    return y.cpu().contiguous(), rt
-
-
-def _ref64(x, r, w, b, relu):
-    y = F.conv2d(x.double(), w.double(), b.double(), padding=1)
-    if r is not None:
-        y = y + r.double()
-    return torch.relu(y) if relu else y
+def _case_inputs(boards, C, S, seed, res, relu):
+    """conv_inputs for one of CASES: without the residual r is None, without the ReLU the activations have both signs."""
+    x, r, w, b = su.conv_inputs(boards, C, S, seed)
+    return (x if relu else x - 0.3), (r if res else None), w, b
 
 
 def test_split_abi_host_twin():
@@ -70,13 +29,10 @@ def test_split_abi_host_twin():
 
     bnd = eu.hosttwin_binding()
     for boards, res, relu in ((1, False, 1), (2, True, 1), (1, True, 0)):
-        x, r, w, b = _inputs(boards, 64, 9, 10 + boards)
-        if not relu:
-            x = x - 0.3
-        y, rt = _run_split_conv(bnd, x, r if res else None, w, b, relu, "cpu")
-        ref = _ref64(x, r if res else None, w, b, relu)
-        err = (y.double() - ref).abs().max().item() / ref.abs().max().item()
-        assert rt <= 2.0 ** -21, rt
+        x, r, w, b = _case_inputs(boards, 64, 9, 10 + boards, res, relu)
+        o = su.split_conv(bnd, x, r, w, b, relu, "cpu")
+        err = su.rel_err(o.y, su.ref64_conv(x, r, w, b, relu))
+        assert o.roundtrip <= 2.0 ** -21, o.roundtrip
         assert err <= 2e-6, (boards, res, relu, err)
     assert bnd.dll.azsp_split_bytes(3, 9, 128) == 3 * 2 * 81 * 128 * 2 and bnd.dll.azsp_split_bytes(1, 9, 12) == -1
     assert bnd.dll.azsp_conv3x3_split(None, None, None, None, None, 1, 9, 128, 1, None, None) != 0
@@ -93,17 +49,14 @@ def test_split_abi_host_twin_17x17_and_pad3_stem():
     import engine_util as eu
 
     bnd = eu.hosttwin_binding()
-    x, r, w, b = _inputs(1, 64, 17, 5)
-    y, rt = _run_split_conv(bnd, x, r, w, b, 1, "cpu")
-    ref = _ref64(x, r, w, b, 1)
-    assert (y.double() - ref).abs().max().item() / ref.abs().max().item() <= 2e-6 and rt <= 2.0 ** -21
-    net = _trained_like_gomoku_net(64, 1)
+    x, r, w, b = su.conv_inputs(1, 64, 17, 5)
+    o = su.split_conv(bnd, x, r, w, b, 1, "cpu")
+    assert su.rel_err(o.y, su.ref64_conv(x, r, w, b, 1)) <= 2e-6 and o.roundtrip <= 2.0 ** -21
+    net = su.gomoku13_net(64, 1)
     inf = InferenceNet(net, dtype=torch.float32, binding=bnd)
     xs = (torch.rand(2, 17, 13, 13, generator=torch.Generator().manual_seed(2)) > 0.6).float()
-    pri, v = inf.forward_split(xs)
-    with torch.no_grad():
-        lg, v64 = net.double()(xs.double())
-    dp, dv = (pri.double() - torch.softmax(lg, -1)).abs().max().item(), (v.double() - v64.squeeze(1)).abs().max().item()
+    pv = inf.forward_split(xs)
+    dp, dv = su.dist_to_fp64(net, xs)(pv)
     assert dp <= 2e-6 and dv <= 2e-6, (dp, dv)
     # shapes without a kernel are refused, not guessed
     z = torch.zeros(2 * 2 * 169 * 64, dtype=torch.float16)
@@ -118,19 +71,18 @@ def test_split_range_record_host_twin_and_weight_check():
 
     import engine_util as eu
 
-    bnd = eu.hosttwin_binding()
+    dll = eu.hosttwin_binding().dll
     ev, mx = ctypes.c_uint32(7), ctypes.c_float(7.0)
-    assert bnd.dll.azsp_split_range_status(ctypes.byref(ev), ctypes.byref(mx), 1, None) == 0  # reset whatever earlier tests left
-    assert bnd.dll.azsp_split_range_status(ctypes.byref(ev), ctypes.byref(mx), 0, None) == 0 and ev.value == 0 and mx.value == 0.0
-    x = torch.tensor([1.0, -3.0, 65504.0, 1e-7, 0.0, 3.0, -2.5e-5, 60000.0]).reshape(1, 8, 1, 1).contiguous(memory_format=torch.channels_last)
-    s = torch.zeros(2 * 8, dtype=torch.float16)
-    assert bnd.dll.azsp_split_layout(x.data_ptr(), s.data_ptr(), 1, 1, 8, 1, None, None) == 0
-    assert bnd.dll.azsp_split_range_status(ctypes.byref(ev), ctypes.byref(mx), 0, None) == 0 and ev.value == 0  # +-65504 itself is in range
+    assert dll.azsp_split_range_status(ctypes.byref(ev), ctypes.byref(mx), 1, None) == 0  # reset whatever earlier tests left
+    assert dll.azsp_split_range_status(ctypes.byref(ev), ctypes.byref(mx), 0, None) == 0 and ev.value == 0 and mx.value == 0.0
+    x = torch.tensor([1.0, -3.0, 65504.0, 1e-7, 0.0, 3.0, -2.5e-5, 60000.0]).reshape(1, 8, 1, 1)
+    su.to_split(dll, x, "cpu")
+    assert su.default_record(dll)[0] == 0  # +-65504 itself is in range
     x[0, 1, 0, 0], x[0, 5, 0, 0] = -1e5, 70000.0
-    assert bnd.dll.azsp_split_layout(x.data_ptr(), s.data_ptr(), 1, 1, 8, 1, None, None) == 0
-    assert bnd.dll.azsp_split_range_status(ctypes.byref(ev), None, 0, None) == 0 and ev.value == 2
-    assert bnd.dll.azsp_split_range_status(None, ctypes.byref(mx), 1, None) == 0 and mx.value == 1e5
-    assert bnd.dll.azsp_split_range_status(ctypes.byref(ev), ctypes.byref(mx), 0, None) == 0 and ev.value == 0 and mx.value == 0.0
+    su.to_split(dll, x, "cpu")
+    assert dll.azsp_split_range_status(ctypes.byref(ev), None, 0, None) == 0 and ev.value == 2  # (either output pointer may be null)
+    assert dll.azsp_split_range_status(None, ctypes.byref(mx), 1, None) == 0 and mx.value == 1e5
+    assert su.default_record(dll) == (0, 0.0)
     w = torch.randn(8, 8, 3, 3)
     assert split_weights_f16(w).shape == (2, 9, 8, 8)
     for bad in (7e4, float("inf"), float("nan")):
@@ -144,12 +96,9 @@ def test_split_tower_clamps_at_f16_range_host_twin():
     """Values beyond f16's largest finite number are clamped when they are split (documented in include/azsp.h), never inf / NaN."""
     import engine_util as eu
 
-    bnd = eu.hosttwin_binding()
-    x = torch.tensor([1e5, -1e5, 65504.0, 1e-7, 0.0, 3.0, -2.5e-5, 70000.0]).reshape(1, 8, 1, 1).contiguous(memory_format=torch.channels_last)
-    s = torch.zeros(2 * 8, dtype=torch.float16)
-    assert bnd.dll.azsp_split_layout(x.data_ptr(), s.data_ptr(), 1, 1, 8, 1, None, None) == 0
-    back = torch.empty_like(x)
-    assert bnd.dll.azsp_split_layout(s.data_ptr(), back.data_ptr(), 1, 1, 8, 0, None, None) == 0
+    dll = eu.hosttwin_binding().dll
+    x = torch.tensor([1e5, -1e5, 65504.0, 1e-7, 0.0, 3.0, -2.5e-5, 70000.0]).reshape(1, 8, 1, 1)
+    back = su.from_split(dll, su.to_split(dll, x, "cpu"), 1, 1, 8)
     want = x.clamp(-65504.0, 65504.0)
     assert torch.isfinite(back).all() and ((back - want).abs() <= want.abs() * 2.0 ** -21 + 1e-11).all(), back.flatten()
 
@@ -168,19 +117,12 @@ def test_gpu_split_conv_error_vs_fp64(boards, C):
 
     bnd = _lib.load()
     out = []
-    for res, relu in ((False, 1), (True, 1), (True, 0)):
-        x, r, w, b = _inputs(boards, C, 9, 100 + boards)
-        if not relu:
-            x = x - 0.3
-        y, rt = _run_split_conv(bnd, x, r if res else None, w, b, relu, "cuda")
-        ref = _ref64(x, r if res else None, w, b, relu)
-        lib = F.conv2d(x.cuda(), w.cuda(), b.cuda(), padding=1)
-        if res:
-            lib = lib + r.cuda()
-        lib = (torch.relu(lib) if relu else lib).cpu()
-        scale = ref.abs().max().item()
-        err, lib_err = (y.double() - ref).abs().max().item() / scale, (lib.double() - ref).abs().max().item() / scale
-        out.append(dict(boards=boards, C=C, residual=res, relu=relu, err=err, library_fp32_err=lib_err, layout_roundtrip_rel=rt))
+    for res, relu in CASES:
+        x, r, w, b = _case_inputs(boards, C, 9, 100 + boards, res, relu)
+        o = su.split_conv(bnd, x, r, w, b, relu, "cuda")
+        ref = su.ref64_conv(x, r, w, b, relu)
+        out.append(dict(boards=boards, C=C, residual=res, relu=relu, err=su.rel_err(o.y, ref),
+                        library_fp32_err=su.rel_err(su.library_conv(x, r, w, b, relu), ref), layout_roundtrip_rel=o.roundtrip))
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
     with open(os.path.join(ROOT, "gpurun_out", "split_conv_error.jsonl"), "a") as f:
         for o in out:
@@ -199,11 +141,9 @@ def test_gpu_split_conv_small_and_large_magnitudes():
     bnd = _lib.load()
     res = {}
     for name, scale in (("1e-4", 1e-4), ("1e-2", 1e-2), ("1e2", 1e2)):
-        x, r, w, b = _inputs(40, 128, 9, 7, scale=scale)
+        x, r, w, b = su.conv_inputs(40, 128, 9, 7, scale=scale)
         b = b * scale
-        y, _ = _run_split_conv(bnd, x, r, w, b, 1, "cuda")
-        ref = _ref64(x, r, w, b, 1)
-        res[name] = (y.double() - ref).abs().max().item() / ref.abs().max().item()
+        res[name] = su.rel_err(su.split_conv(bnd, x, r, w, b, 1, "cuda").y, su.ref64_conv(x, r, w, b, 1))
     print(json.dumps(res))
     # measured: 6.7e-7 / 5.7e-7 / 5.1e-7 -- the f16 MFMA takes subnormal hi halves as they are, the scaled lo halves carry the rest
     assert max(res.values()) <= 2e-6, res
@@ -225,38 +165,16 @@ def test_column_tile_map_in_the_header_is_the_generated_one():
     assert sorted(gen) == [p for p in range(81) if p != 72]  # every position but the corner (8, 0), once
 
 
-def _trained_like_gomoku_net(filters, blocks, seed=3, fc=64):
-    torch.manual_seed(seed)
-    net = AlphaZeroNet((17, 13, 13), 169, blocks, filters, fc, gomoku=True).eval()
-    with torch.no_grad():
-        for m in net.modules():
-            if isinstance(m, torch.nn.BatchNorm2d):
-                m.running_mean.normal_(0, 0.2), m.running_var.uniform_(0.5, 1.5), m.weight.uniform_(0.7, 1.3), m.bias.normal_(0, 0.2)
-    return net
-
-
-def _trained_like_net(filters, blocks, seed=3):
-    torch.manual_seed(seed)
-    net = AlphaZeroNet((17, 9, 9), 82, blocks, filters, 128).eval()
-    with torch.no_grad():
-        for m in net.modules():
-            if isinstance(m, torch.nn.BatchNorm2d):  # non-trivial running statistics, as after training
-                m.running_mean.normal_(0, 0.2), m.running_var.uniform_(0.5, 1.5), m.weight.uniform_(0.7, 1.3), m.bias.normal_(0, 0.2)
-    return net
-
-
 def test_split_evaluator_host_twin():
     """azsp_split_features -> azsp_stem_split -> azsp_conv3x3_split x 2 -> azsp_head_split through InferenceNet.forward_split on the host
     twin (plain loops on the same arithmetic): a 1-block 64-filter network on 3 positions vs the fp64 module."""
     import engine_util as eu
 
-    net = _trained_like_net(64, 1)
+    net = su.go9_net(64, 1)
     inf = InferenceNet(net, dtype=torch.float32, binding=eu.hosttwin_binding())
     x = (torch.rand(3, 17, 9, 9, generator=torch.Generator().manual_seed(2)) > 0.6).float()
     pri, v = inf.forward_split(x)
-    with torch.no_grad():
-        lg, v64 = net.double()(x.double())
-    dp, dv = (pri.double() - torch.softmax(lg, -1)).abs().max().item(), (v.double() - v64.squeeze(1)).abs().max().item()
+    dp, dv = su.dist_to_fp64(net, x)((pri, v))
     assert dp <= 2e-6 and dv <= 2e-6, (dp, dv)
     assert abs(pri.sum(1) - 1).max().item() <= 1e-5
 
@@ -272,17 +190,11 @@ def test_gpu_fp32_network_on_the_split_kernels(filters):
     5.6e-5 / 2.4e-5, library 1.9e-5 .. 9.3e-5 / 2.9e-5 .. 4.0e-5)."""
     from alpha_zero_amd import _lib
 
-    net = _trained_like_net(filters, 10)
+    net = su.go9_net(filters, 10)
     inf = InferenceNet(net, dtype=torch.float32, binding=_lib.load()).cuda()
     assert inf.supports_split_features(9, "cuda") and "hand-written" in inf.evaluator_path(9, "cuda")
     x = (torch.rand(203, 17, 9, 9, generator=torch.Generator().manual_seed(1)) > 0.6).float()
-    with torch.no_grad():
-        lg, v64 = net.double()(x.double())
-    p64, v64 = torch.softmax(lg, -1), v64.squeeze(1)
-
-    def dist(pv):
-        return (pv[0].cpu().double() - p64).abs().max().item(), (pv[1].cpu().double() - v64).abs().max().item()
-
+    dist = su.dist_to_fp64(net, x)
     d = dict(filters=filters)
     inf._split = None
     d["split_evaluator_vs_fp64"] = dist(inf(x.cuda()))
@@ -308,14 +220,12 @@ def test_gpu_split_stem_and_heads_vs_fp64(boards):
     from alpha_zero_amd import _lib
 
     for filters in (128, 64):
-        net = _trained_like_net(filters, 0, seed=boards)
+        net = su.go9_net(filters, 0, seed=boards)
         inf = InferenceNet(net, dtype=torch.float32, binding=_lib.load()).cuda()
         x = (torch.rand(boards, 17, 9, 9, generator=torch.Generator().manual_seed(boards)) > 0.6).float()
-        pri, v = inf(x.cuda())
+        pv = inf(x.cuda())
         assert inf._split is not None
-        with torch.no_grad():
-            lg, v64 = net.double()(x.double())
-        dp, dv = (pri.cpu().double() - torch.softmax(lg, -1)).abs().max().item(), (v.cpu().double() - v64.squeeze(1)).abs().max().item()
+        dp, dv = su.dist_to_fp64(net, x)(pv)
         assert dp <= 2e-6 and dv <= 4e-6, (filters, boards, dp, dv)
 
 
@@ -331,21 +241,14 @@ def test_gpu_split_conv17_error_vs_fp64(boards):
 
     bnd = _lib.load()
     out = []
-    for res, relu in ((False, 1), (True, 1), (True, 0)):
-        x, r, w, b = _inputs(boards, 64, 17, 300 + boards)
-        if not relu:
-            x = x - 0.3
-        y, rt = _run_split_conv(bnd, x, r if res else None, w, b, relu, "cuda")
-        ref = _ref64(x, r if res else None, w, b, relu)
-        lib = F.conv2d(x.cuda(), w.cuda(), b.cuda(), padding=1)
-        if res:
-            lib = lib + r.cuda()
-        lib = (torch.relu(lib) if relu else lib).cpu()
-        scale = ref.abs().max().item()
-        d = (y.double() - ref).abs()
-        err, lib_err = d.max().item() / scale, (lib.double() - ref).abs().max().item() / scale
+    for res, relu in CASES:
+        x, r, w, b = _case_inputs(boards, 64, 17, 300 + boards, res, relu)
+        o = su.split_conv(bnd, x, r, w, b, relu, "cuda")
+        ref = su.ref64_conv(x, r, w, b, relu)
+        d = (o.y.double() - ref).abs()
         worst = [int(v) for v in torch.nonzero(d == d.max())[0]]  # (board, channel, row, column) of the worst element: a layout bug shows here
-        out.append(dict(boards=boards, S=17, C=64, residual=res, relu=relu, err=err, library_fp32_err=lib_err, layout_roundtrip_rel=rt, worst=worst))
+        out.append(dict(boards=boards, S=17, C=64, residual=res, relu=relu, err=su.rel_err(o.y, ref),
+                        library_fp32_err=su.rel_err(su.library_conv(x, r, w, b, relu), ref), layout_roundtrip_rel=o.roundtrip, worst=worst))
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
     with open(os.path.join(ROOT, "gpurun_out", "split_conv17_error.jsonl"), "a") as f:
         for o in out:
@@ -362,17 +265,11 @@ def test_gpu_fp32_gomoku_network_on_the_split_kernels():
     Same bound as the 9x9 networks: within 2e-4 of fp64 and at most 4x + 2e-5 the library path's distance."""
     from alpha_zero_amd import _lib
 
-    net = _trained_like_gomoku_net(64, 6)
+    net = su.gomoku13_net(64, 6)
     inf = InferenceNet(net, dtype=torch.float32, binding=_lib.load()).cuda()
     assert inf.supports_split_features(13, "cuda") and "hand-written" in inf.evaluator_path(13, "cuda")
     x = (torch.rand(131, 17, 13, 13, generator=torch.Generator().manual_seed(1)) > 0.6).float()
-    with torch.no_grad():
-        lg, v64 = net.double()(x.double())
-    p64, v64 = torch.softmax(lg, -1), v64.squeeze(1)
-
-    def dist(pv):
-        return (pv[0].cpu().double() - p64).abs().max().item(), (pv[1].cpu().double() - v64).abs().max().item()
-
+    dist = su.dist_to_fp64(net, x)
     d = dict(filters=64, board=13)
     inf._split = None
     d["split_evaluator_vs_fp64"] = dist(inf(x.cuda()))
@@ -398,15 +295,13 @@ def test_gpu_split_gomoku_stem_and_heads_vs_fp64(boards):
     their own (a 0-block network = stem -> heads) vs the fp64 module."""
     from alpha_zero_amd import _lib
 
-    net = _trained_like_gomoku_net(64, 0, seed=boards, fc=80)
+    net = su.gomoku13_net(64, 0, seed=boards, fc=80)
     inf = InferenceNet(net, dtype=torch.float32, binding=_lib.load()).cuda()
     x = (torch.rand(boards, 17, 13, 13, generator=torch.Generator().manual_seed(boards)) > 0.6).float()
     inf._split = None
-    pri, v = inf(x.cuda())
+    pv = inf(x.cuda())
     assert inf._split is not None
-    with torch.no_grad():
-        lg, v64 = net.double()(x.double())
-    dp, dv = (pri.cpu().double() - torch.softmax(lg, -1)).abs().max().item(), (v.cpu().double() - v64.squeeze(1)).abs().max().item()
+    dp, dv = su.dist_to_fp64(net, x)(pv)
     assert dp <= 2e-6 and dv <= 4e-6, (boards, dp, dv)
 
 
@@ -414,26 +309,22 @@ def _check_pre_relu_record(bnd, device, S, C):
     """The convolution epilogues record |v| IN FRONT of the ReLU (include/azsp.h, RANGE: deliberately conservative): a strongly negative
     bias drives one channel's pre-activation below -65504; the ReLU zeroes the output, and the event is still counted with its
     magnitude -- by the kernels and by the host twin alike (they disagreed)."""
-    import ctypes
-
     dll = bnd.dll
-    ev, mx = ctypes.c_uint32(0), ctypes.c_float(0.0)
-    assert dll.azsp_split_range_status(None, None, 1, None) == 0
-    x, r, w, b = _inputs(3, C, S, 21)
+    su.default_record(dll, reset=1)
+    x, r, w, b = su.conv_inputs(3, C, S, 21)
     b = b.clone()
     b[5] = -1.0e5
-    y, _ = _run_split_conv(bnd, x, None, w, b, 1, device)
-    assert dll.azsp_split_range_status(ctypes.byref(ev), ctypes.byref(mx), 1, None) == 0
-    ref = _ref64(x, None, w, b, 0)  # pre-activations
-    assert ev.value >= 1 and abs(mx.value - ref[:, 5].abs().max().item()) <= 1e-2 * 1e5 and mx.value > 65504.0, (ev.value, mx.value)
+    y = su.split_conv(bnd, x, None, w, b, 1, device).y
+    ev, mx = su.default_record(dll, reset=1)
+    ref = su.ref64_conv(x, None, w, b, 0)  # pre-activations
+    assert ev >= 1 and abs(mx - ref[:, 5].abs().max().item()) <= 1e-2 * 1e5 and mx > 65504.0, (ev, mx)
     assert float(y[:, 5].abs().max()) == 0.0 and torch.isfinite(y).all()
     others = [c for c in range(C) if c != 5]
     err = (y[:, others].double() - torch.relu(ref[:, others])).abs().max().item() / ref.abs().max().item()
     assert err <= 2e-6, err
     # without the ReLU the same value is clamped to -65504 and recorded once more
-    y0, _ = _run_split_conv(bnd, x, None, w, b, 0, device)
-    assert dll.azsp_split_range_status(ctypes.byref(ev), ctypes.byref(mx), 1, None) == 0
-    assert ev.value >= 1 and float(y0[:, 5].min()) == -65504.0
+    y0 = su.split_conv(bnd, x, None, w, b, 0, device).y
+    assert su.default_record(dll, reset=1)[0] >= 1 and float(y0[:, 5].min()) == -65504.0
 
 
 @pytest.mark.parametrize("S,C", [(9, 64), (17, 64)])
@@ -458,22 +349,14 @@ def test_gpu_split_range_record_trips_and_resets(S, C):
     activation that leaves f16's range inside the convolution's epilogue (here: a 9-tap sum of 3e4-sized inputs, and a residual that
     pushes one output over) is clamped, counted and its magnitude reported; the layout conversion reports out-of-range inputs; reset
     clears the record.  The clamped result itself is finite (65504), never inf / NaN."""
-    import ctypes
-
     from alpha_zero_amd import _lib
 
     bnd = _lib.load()
     dll = bnd.dll
-
-    def status(reset=0):
-        ev, mx = ctypes.c_uint32(0), ctypes.c_float(0.0)
-        assert dll.azsp_split_range_status(ctypes.byref(ev), ctypes.byref(mx), reset, None) == 0
-        return ev.value, mx.value
-
-    status(1)
-    x, r, w, b = _inputs(5, C, S, 11)
-    y, _ = _run_split_conv(bnd, x, r, w, b, 1, "cuda")
-    assert status() == (0, 0.0)
+    su.default_record(dll, reset=1)
+    x, r, w, b = su.conv_inputs(5, C, S, 11)
+    su.split_conv(bnd, x, r, w, b, 1, "cuda")
+    assert su.default_record(dll) == (0, 0.0)
     # identity-like filter bank (centre tap of channel c -> c, weight 4): y = 4 x + b (+ r)
     w2 = torch.zeros(C, C, 3, 3)
     w2[torch.arange(C), torch.arange(C), 1, 1] = 4.0
@@ -481,17 +364,16 @@ def test_gpu_split_range_record_trips_and_resets(S, C):
     x2[3, 5, S - 1, 0] = 3e4          # 4 * 3e4 = 1.2e5 > 65504 in the epilogue of the convolution (the 9x9 kernel's corner position)
     x2[1, 7, 2, 3] = 2e4              # 8e4: an ordinary position
     b2 = torch.zeros(C)
-    y2, _ = _run_split_conv(bnd, x2, None, w2, b2, 1, "cuda")
-    ev, mx = status()
+    y2 = su.split_conv(bnd, x2, None, w2, b2, 1, "cuda").y
+    ev, mx = su.default_record(dll)
     assert ev >= 2 and mx == 120000.0, (ev, mx)
     assert torch.isfinite(y2).all() and y2[3, 5, S - 1, 0] == 65504.0 and y2[1, 7, 2, 3] == 65504.0 and abs(y2[0, 0, 0, 0].item() - 400.0) < 1e-3
-    assert status(1)[0] == ev and status() == (0, 0.0)
+    assert su.default_record(dll, reset=1)[0] == ev and su.default_record(dll) == (0, 0.0)
     # the conversion into the split layout reports what it clamps, too
     x3 = x.clone()
     x3[2, 1, 0, 0] = -1e6
-    xs = torch.zeros(dll.azsp_split_bytes(5, S, C) // 2, dtype=torch.float16, device="cuda")
-    assert dll.azsp_split_layout(x3.cuda().contiguous(memory_format=torch.channels_last).data_ptr(), xs.data_ptr(), 5, S, C, 1, None, None) == 0
-    assert status(1) == (1, 1e6)
+    su.to_split(dll, x3, "cuda")
+    assert su.default_record(dll, reset=1) == (1, 1e6)
 
 
 def test_split_feature_tensor_round_trip_host():
@@ -502,8 +384,7 @@ def test_split_feature_tensor_round_trip_host():
     x = (torch.rand(3, 17, 9, 9, generator=torch.Generator().manual_seed(5)) > 0.6).float()
     t = eu.split_features(x)
     assert (torch.from_numpy(eu.unsplit_features(t, 3, 9)).float() == x).all()
-    net = _trained_like_net(64, 1)
-    inf = InferenceNet(net, dtype=torch.float32, binding=eu.hosttwin_binding())
+    inf = InferenceNet(su.go9_net(64, 1), dtype=torch.float32, binding=eu.hosttwin_binding())
     p0, v0 = inf.forward_split(x)
     p1, v1 = inf.forward_split(t, split_features=(3, 9))
     assert torch.equal(p0, p1) and torch.equal(v0, v1)
@@ -517,7 +398,7 @@ def test_gpu_stem_on_engine_written_features_equals_the_general_stem(game, n, fi
     import engine_util as eu
     from alpha_zero_amd import _lib
 
-    net = _trained_like_net(filters, 2) if game == "go" else _trained_like_gomoku_net(filters, 2)
+    net = su.go9_net(filters, 2) if game == "go" else su.gomoku13_net(filters, 2)
     inf = InferenceNet(net, dtype=torch.float32, binding=_lib.load()).cuda()
     for rows in (1, 5, 300, 1031):
         x = (torch.rand(rows, 17, n, n, generator=torch.Generator().manual_seed(rows)) > 0.6).float()
@@ -527,50 +408,16 @@ def test_gpu_stem_on_engine_written_features_equals_the_general_stem(game, n, fi
 
 
 # ---- fused split-precision ResNetBlock at 17x17 x 64 (az_resblock_sp17.h, azsp_resblock_split) ------------------------------------
-def _resblock_inputs(boards, seed, S=17):
-    g = torch.Generator().manual_seed(seed)
-    C = 64
-    x = torch.randn(boards, C, S, S, generator=g)
-    x = torch.where(torch.rand(boards, C, S, S, generator=g) < 0.5, torch.zeros(()), x.abs())
-    x[:, :8] *= 37.0
-    x[:, -8:] *= 3e-3
-    ws = [torch.randn(C, C, 3, 3, generator=g) * (2.0 / (9 * C)) ** 0.5 for _ in range(2)]
-    bs = [torch.randn(C, generator=g) * 0.1 for _ in range(2)]
-    return x, ws, bs
-
-
-def _resblock_both_ways(bnd, x, ws, bs, device):
-    """(fused y, two-launch y) in the split layout, as raw f16 tensors, + the fused result as fp32 NCHW."""
-    B, C, S, _ = x.shape
-    dll = bnd.dll
-    n = dll.azsp_split_bytes(B, S, C) // 2
-    xs, ms, y2, yf = (torch.zeros(n, dtype=torch.float16, device=device) for _ in range(4))
-    xc = x.to(device).contiguous(memory_format=torch.channels_last)
-    assert dll.azsp_split_layout(xc.data_ptr(), xs.data_ptr(), B, S, C, 1, None, None) == 0
-    wsp = [split_weights_f16(w).to(device) for w in ws]
-    bb = [b.float().to(device) for b in bs]
-    assert dll.azsp_conv3x3_split(xs.data_ptr(), wsp[0].data_ptr(), bb[0].data_ptr(), None, ms.data_ptr(), B, S, C, 1, None, None) == 0
-    assert dll.azsp_conv3x3_split(ms.data_ptr(), wsp[1].data_ptr(), bb[1].data_ptr(), xs.data_ptr(), y2.data_ptr(), B, S, C, 1, None, None) == 0
-    assert dll.azsp_resblock_split(xs.data_ptr(), wsp[0].data_ptr(), bb[0].data_ptr(), wsp[1].data_ptr(), bb[1].data_ptr(), yf.data_ptr(), B, S, C, None, None) == 0
-    y = torch.empty_like(xc)
-    assert dll.azsp_split_layout(yf.data_ptr(), y.data_ptr(), B, S, C, 0, None, None) == 0
-    if device != "cpu":
-        torch.cuda.synchronize()
-    return yf, y2, y.cpu().contiguous()
-
-
 def test_split_resblock_abi_host_twin():
     """azsp_resblock_split through the ABI on the host twin: equals two azsp_conv3x3_split calls; argument checks (y == x refused,
     shapes without a fused kernel refused)."""
     import engine_util as eu
 
     bnd = eu.hosttwin_binding()
-    x, ws, bs = _resblock_inputs(2, 3)
-    yf, y2, y = _resblock_both_ways(bnd, x, ws, bs, "cpu")
+    x, ws, bs = su.resblock_inputs(2, 3)
+    yf, y2, y = su.split_resblock(bnd, x, ws, bs, "cpu")
     assert torch.equal(yf, y2)
-    mid = torch.relu(F.conv2d(x.double(), ws[0].double(), bs[0].double(), padding=1))
-    ref = torch.relu(F.conv2d(mid, ws[1].double(), bs[1].double(), padding=1) + x.double())
-    assert ((y.double() - ref).abs().max() / ref.abs().max()).item() <= 2e-6
+    assert su.rel_err(y, su.ref64_resblock(x, ws, bs)) <= 2e-6
     z = torch.zeros(2 * 2 * 17 * 17 * 64, dtype=torch.float16)
     assert bnd.dll.azsp_resblock_split(z.data_ptr(), z.data_ptr(), z.data_ptr(), z.data_ptr(), z.data_ptr(), z.data_ptr(), 1, 17, 64, None, None) != 0  # y == x
     zo = z.clone()
@@ -579,8 +426,8 @@ def test_split_resblock_abi_host_twin():
     assert bnd.dll.azsp_resblock_split(z.data_ptr(), z.data_ptr(), z.data_ptr(), z.data_ptr(), z.data_ptr(), zo.data_ptr(), 1, 9, 128, None, None) != 0
     # the 9x9 x 64 shape (round 6) through the ABI on the twin: equals the two launches, 1 - 3 boards
     for nb in (1, 2, 3):
-        x9, ws9, bs9 = _resblock_inputs(nb, 40 + nb, S=9)
-        yf9, y29, _ = _resblock_both_ways(bnd, x9, ws9, bs9, "cpu")
+        x9, ws9, bs9 = su.resblock_inputs(nb, 40 + nb, S=9)
+        yf9, y29, _ = su.split_resblock(bnd, x9, ws9, bs9, "cpu")
         assert torch.equal(yf9, y29)
     assert bnd.dll.azsp_resblock_split(None, z.data_ptr(), z.data_ptr(), z.data_ptr(), z.data_ptr(), zo.data_ptr(), 1, 17, 64, None, None) != 0
 
@@ -594,16 +441,10 @@ def test_gpu_split_resblock17_bit_identical_to_two_launches(boards):
     of the persistent loop.  Also against fp64: the block's error is of the size of two fp32 convolutions' round-off."""
     from alpha_zero_amd import _lib
 
-    x, ws, bs = _resblock_inputs(boards, 100 + boards)
-    yf, y2, y = _resblock_both_ways(_lib.load(), x, ws, bs, "cuda")
-    if not torch.equal(yf, y2):
-        B, C, S = boards, 64, 17
-        d = (yf.view(B, 2, C // 8, S * S, 8) != y2.view(B, 2, C // 8, S * S, 8)).any(dim=4).any(dim=1)  # [B, chunk, pos]
-        bad = d.nonzero()
-        raise AssertionError(f"{len(bad)} (board, chunk, position) cells differ; first {bad[:12].tolist()}; rows {sorted(set((bad[:, 2] // 17).tolist()))[:20]}")
-    mid = torch.relu(F.conv2d(x.double(), ws[0].double(), bs[0].double(), padding=1))
-    ref = torch.relu(F.conv2d(mid, ws[1].double(), bs[1].double(), padding=1) + x.double())
-    assert ((y.double() - ref).abs().max() / ref.abs().max()).item() <= 2e-6
+    x, ws, bs = su.resblock_inputs(boards, 100 + boards)
+    yf, y2, y = su.split_resblock(_lib.load(), x, ws, bs, "cuda")
+    su.assert_same_words(yf, y2, boards, 64, 17, f"fused block / two launches, boards={boards}")
+    assert su.rel_err(y, su.ref64_resblock(x, ws, bs)) <= 2e-6
 
 
 @pytest.mark.gpu
@@ -615,35 +456,25 @@ def test_gpu_split_resblock9_bit_identical_to_two_launches(boards):
     slot (256 slots) the first-tile, has-next and last-tile paths.  Also against fp64."""
     from alpha_zero_amd import _lib
 
-    x, ws, bs = _resblock_inputs(boards, 300 + boards, S=9)
-    yf, y2, y = _resblock_both_ways(_lib.load(), x, ws, bs, "cuda")
-    if not torch.equal(yf, y2):
-        B, C, S = boards, 64, 9
-        d = (yf.view(B, 2, C // 8, S * S, 8) != y2.view(B, 2, C // 8, S * S, 8)).any(dim=4).any(dim=1)  # [B, chunk, pos]
-        bad = d.nonzero()
-        raise AssertionError(f"{len(bad)} (board, chunk, position) cells differ; first {bad[:12].tolist()}; boards {sorted(set(bad[:, 0].tolist()))[:20]}")
-    mid = torch.relu(F.conv2d(x.double(), ws[0].double(), bs[0].double(), padding=1))
-    ref = torch.relu(F.conv2d(mid, ws[1].double(), bs[1].double(), padding=1) + x.double())
-    assert ((y.double() - ref).abs().max() / ref.abs().max()).item() <= 2e-6
+    x, ws, bs = su.resblock_inputs(boards, 300 + boards, S=9)
+    yf, y2, y = su.split_resblock(_lib.load(), x, ws, bs, "cuda")
+    su.assert_same_words(yf, y2, boards, 64, 9, f"fused block / two launches, boards={boards}")
+    assert su.rel_err(y, su.ref64_resblock(x, ws, bs)) <= 2e-6
 
 
 @pytest.mark.gpu
 def test_gpu_split_resblock9_records_intermediate_overflow():
     """The intermediate activation of the fused 9x9 block is split inside the kernel, too: a value beyond f16's range in m is recorded."""
-    import ctypes
-
     from alpha_zero_amd import _lib
 
     bnd = _lib.load()
-    dll = bnd.dll
-    assert dll.azsp_split_range_status(None, None, 1, None) == 0
-    x, ws, bs = _resblock_inputs(6, 77, S=9)
+    su.default_record(bnd.dll, reset=1)
+    x, ws, bs = su.resblock_inputs(6, 77, S=9)
     bs[0] = bs[0].clone()
     bs[0][3] = 3.0e5  # conv1's bias pushes one channel of m beyond 65504
-    yf, y2, _ = _resblock_both_ways(bnd, x, ws, bs, "cuda")
-    ev, mx = ctypes.c_uint32(0), ctypes.c_float(0.0)
-    assert dll.azsp_split_range_status(ctypes.byref(ev), ctypes.byref(mx), 1, None) == 0
-    assert ev.value > 0 and mx.value > 65504.0 and torch.equal(yf, y2)
+    yf, y2, _ = su.split_resblock(bnd, x, ws, bs, "cuda")
+    ev, mx = su.default_record(bnd.dll, reset=1)
+    assert ev > 0 and mx > 65504.0 and torch.equal(yf, y2)
 
 
 @pytest.mark.gpu
@@ -653,47 +484,21 @@ def test_gpu_split_resblock17_records_intermediate_overflow():
     from alpha_zero_amd import _lib
 
     dll = _lib.load().dll
-    x, ws, bs = _resblock_inputs(5, 9)
+    x, ws, bs = su.resblock_inputs(5, 9)
     ws[0] = ws[0] * 4000.0   # m ~ 1e5 .. 1e6
     ws[1] = ws[1] / 4000.0
-    B, C, S = 5, 64, 17
-    n = dll.azsp_split_bytes(B, S, C) // 2
-    xs, yf = torch.zeros(n, dtype=torch.float16, device="cuda"), torch.zeros(n, dtype=torch.float16, device="cuda")
-    xc = x.cuda().contiguous(memory_format=torch.channels_last)
-    rec = torch.zeros(2, dtype=torch.int32, device="cuda")
-    assert dll.azsp_split_layout(xc.data_ptr(), xs.data_ptr(), B, S, C, 1, rec.data_ptr(), None) == 0
-    wsp = [split_weights_f16(w).cuda() for w in ws]
-    bb = [b.float().cuda() for b in bs]
-    assert dll.azsp_resblock_split(xs.data_ptr(), wsp[0].data_ptr(), bb[0].data_ptr(), wsp[1].data_ptr(), bb[1].data_ptr(), yf.data_ptr(), B, S, C,
-                                   rec.data_ptr(), None) == 0
-    torch.cuda.synchronize()
-    r = rec.cpu()
-    assert int(r[0]) > 0 and float(r[1:].view(torch.float32)[0]) > 65504.0
+    B, C, S, _ = x.shape
+    rec = su.new_record("cuda")
+    xs = su.to_split(dll, x, "cuda", rec)
+    yf = torch.zeros_like(xs)
+    (w1, b1), (w2, b2) = (su.split_params(w, b, "cuda") for w, b in zip(ws, bs))
+    # (the fused entry alone: the first of split_resblock's two launches would report the same values into the record)
+    assert dll.azsp_resblock_split(xs.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), yf.data_ptr(), B, S, C, rec.data_ptr(), None) == 0
+    ev, mx = su.read_record(rec)
+    assert ev > 0 and mx > 65504.0
 
 
 # ---- round 6: the wave-per-tile kernel k_conv3x3_spg (small batches of the tailored shapes, every other shape) -------------------------
-def _raw_split_conv(bnd, x, r, w, b, relu, device="cuda"):
-    """azsp_conv3x3_split on fp32 NCHW inputs; returns the raw split-layout output (f16 words) and the joined fp32 NCHW output."""
-    B, C, S, _ = x.shape
-    dll = bnd.dll
-    n = dll.azsp_split_bytes(B, S, C) // 2
-    xs, ys = torch.zeros(n, dtype=torch.float16, device=device), torch.zeros(n, dtype=torch.float16, device=device)
-    xc = x.to(device).contiguous(memory_format=torch.channels_last)
-    assert dll.azsp_split_layout(xc.data_ptr(), xs.data_ptr(), B, S, C, 1, None, None) == 0
-    rs = None
-    if r is not None:
-        rs = torch.zeros(n, dtype=torch.float16, device=device)
-        assert dll.azsp_split_layout(r.to(device).contiguous(memory_format=torch.channels_last).data_ptr(), rs.data_ptr(), B, S, C, 1, None, None) == 0
-    wsp, bb = split_weights_f16(w).to(device), b.float().to(device)
-    assert dll.azsp_conv3x3_split(xs.data_ptr(), wsp.data_ptr(), bb.data_ptr(), rs.data_ptr() if rs is not None else None, ys.data_ptr(),
-                                  B, S, C, relu, None, None) == 0
-    y = torch.empty_like(xc)
-    assert dll.azsp_split_layout(ys.data_ptr(), y.data_ptr(), B, S, C, 0, None, None) == 0
-    if device != "cpu":
-        torch.cuda.synchronize()
-    return ys.cpu(), y.cpu().contiguous()
-
-
 def test_small_batch_knob_host_twin():
     """azsp_small_batch_waves: sets, returns the previous value, a negative argument only queries (the twin's loops ignore it)."""
     import engine_util as eu
@@ -703,10 +508,9 @@ def test_small_batch_knob_host_twin():
     assert b.dll.azsp_small_batch_waves(7) == old and b.dll.azsp_small_batch_waves(-1) == 7
     assert b.dll.azsp_small_batch_waves(old) == 7 and b.dll.azsp_small_batch_waves(-5) == old
     # shapes beyond the tailored ones go through the ABI since round 6 (19x19 x 64 here: the twin's plain loops vs fp64)
-    x, r, w, bb = _inputs(2, 64, 19, 5)
-    y, rt = _run_split_conv(b, x, r, w, bb, 1, "cpu")
-    ref = _ref64(x, r, w, bb, 1)
-    assert ((y.double() - ref).abs().max() / ref.abs().max()).item() <= 8e-7 and rt <= 2.0 ** -21
+    x, r, w, bb = su.conv_inputs(2, 64, 19, 5)
+    o = su.split_conv(b, x, r, w, bb, 1, "cpu")
+    assert su.rel_err(o.y, su.ref64_conv(x, r, w, bb, 1)) <= 8e-7 and o.roundtrip <= 2.0 ** -21
 
 
 @pytest.mark.gpu
@@ -719,23 +523,14 @@ def test_gpu_wave_per_tile_conv_is_bit_identical_to_the_weight_stationary_kernel
     from alpha_zero_amd import _lib
 
     bnd = _lib.load()
-    old = bnd.dll.azsp_small_batch_waves(-1)
-    try:
-        for boards in (1, 3, 19):
-            for res, relu in ((False, 1), (True, 1), (True, 0)):
-                x, r, w, b = _inputs(boards, C, S, 300 + boards)
-                if not relu:
-                    x = x - 0.3
-                bnd.dll.azsp_small_batch_waves(0)
-                ya, fa = _raw_split_conv(bnd, x, r if res else None, w, b, relu)
-                bnd.dll.azsp_small_batch_waves(1 << 20)
-                yb, fb = _raw_split_conv(bnd, x, r if res else None, w, b, relu)
-                if not torch.equal(ya, yb):
-                    d = (ya.view(boards, 2, C // 8, S * S, 8) != yb.view(boards, 2, C // 8, S * S, 8)).any(dim=4).any(dim=1).nonzero()
-                    raise AssertionError(f"S={S} C={C} boards={boards} res={res} relu={relu}: {len(d)} cells differ; first {d[:10].tolist()}; "
-                                         f"max |d| = {(fa - fb).abs().max().item():.3g}")
-    finally:
-        bnd.dll.azsp_small_batch_waves(old)
+    for boards in (1, 3, 19):
+        for res, relu in CASES:
+            x, r, w, b = _case_inputs(boards, C, S, 300 + boards, res, relu)
+            with su.small_batch_waves(bnd.dll, 0):
+                a = su.split_conv(bnd, x, r, w, b, relu, "cuda")
+            with su.small_batch_waves(bnd.dll, 1 << 20):
+                g = su.split_conv(bnd, x, r, w, b, relu, "cuda")
+            su.assert_same_words(a.raw, g.raw, boards, C, S, f"S={S} C={C} boards={boards} res={res} relu={relu}", a.y, g.y)
 
 
 @pytest.mark.gpu
@@ -746,17 +541,13 @@ def test_gpu_small_batch_resblock_is_bit_identical_to_the_fused_block(S):
     from alpha_zero_amd import _lib
 
     bnd = _lib.load()
-    old = bnd.dll.azsp_small_batch_waves(-1)
-    try:
-        for boards in (1, 2, 5, 25):
-            x, ws, bs = _resblock_inputs(boards, 400 + boards, S)
-            bnd.dll.azsp_small_batch_waves(0)
-            yf0, y20, _ = _resblock_both_ways(bnd, x, ws, bs, "cuda")
-            bnd.dll.azsp_small_batch_waves(1 << 20)
-            yf1, y21, _ = _resblock_both_ways(bnd, x, ws, bs, "cuda")
-            assert torch.equal(yf0, y20) and torch.equal(yf1, y21) and torch.equal(yf0, yf1), (S, boards)
-    finally:
-        bnd.dll.azsp_small_batch_waves(old)
+    for boards in (1, 2, 5, 25):
+        x, ws, bs = su.resblock_inputs(boards, 400 + boards, S)
+        with su.small_batch_waves(bnd.dll, 0):
+            yf0, y20, _ = su.split_resblock(bnd, x, ws, bs, "cuda")
+        with su.small_batch_waves(bnd.dll, 1 << 20):
+            yf1, y21, _ = su.split_resblock(bnd, x, ws, bs, "cuda")
+        assert torch.equal(yf0, y20) and torch.equal(yf1, y21) and torch.equal(yf0, yf1), (S, boards)
 
 
 @pytest.mark.gpu
@@ -768,27 +559,17 @@ def test_gpu_wave_per_tile_conv_on_shapes_without_a_tailored_kernel(S, C, boards
     from alpha_zero_amd import _lib
 
     bnd = _lib.load()
-    old = bnd.dll.azsp_small_batch_waves(-1)
-    try:
-        for res, relu in ((False, 1), (True, 1), (True, 0)):
-            x, r, w, b = _inputs(boards, C, S, 500 + boards)
-            if not relu:
-                x = x - 0.3
+    with su.small_batch_waves(bnd.dll):
+        for res, relu in CASES:
+            x, r, w, b = _case_inputs(boards, C, S, 500 + boards, res, relu)
             bnd.dll.azsp_small_batch_waves(0)        # k_conv3x3_spgw: 48 positions per wave, B fragments shared by the workgroup through LDS
-            ya, y = _raw_split_conv(bnd, x, r if res else None, w, b, relu)
+            a = su.split_conv(bnd, x, r, w, b, relu, "cuda")
             bnd.dll.azsp_small_batch_waves(1 << 20)  # k_conv3x3_spg: 16 couts x 32 positions per wave, no LDS
-            yb, _ = _raw_split_conv(bnd, x, r if res else None, w, b, relu)
-            assert torch.equal(ya, yb), (S, C, boards, res, relu)
-            ref = _ref64(x, r if res else None, w, b, relu)
-            lib = F.conv2d(x.cuda(), w.cuda(), b.cuda(), padding=1)
-            if res:
-                lib = lib + r.cuda()
-            lib = (torch.relu(lib) if relu else lib).cpu()
-            scale = ref.abs().max().item()
-            err, lib_err = (y.double() - ref).abs().max().item() / scale, (lib.double() - ref).abs().max().item() / scale
+            g = su.split_conv(bnd, x, r, w, b, relu, "cuda")
+            assert torch.equal(a.raw, g.raw), (S, C, boards, res, relu)
+            ref = su.ref64_conv(x, r, w, b, relu)
+            err, lib_err = su.rel_err(a.y, ref), su.rel_err(su.library_conv(x, r, w, b, relu), ref)
             os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
             with open(os.path.join(ROOT, "gpurun_out", "split_conv_generic_error.jsonl"), "a") as f:
                 f.write(json.dumps(dict(S=S, C=C, boards=boards, residual=res, relu=relu, err=err, library_fp32_err=lib_err)) + "\n")
             assert err <= (8e-7 if C <= 128 else 1.2e-6), (S, C, boards, res, relu, err, lib_err)  # (2304 products per output at 256 filters)
-    finally:
-        bnd.dll.azsp_small_batch_waves(old)
