@@ -14,6 +14,7 @@
 #include "az_conv_sp17.h"
 #include "az_resblock_sp17.h"
 #include "az_conv_sp2.h"
+#include "az_conv_sp2p.h"
 #include "az_conv_spg.h"
 #include "az_stem_spg.h"
 
@@ -352,11 +353,18 @@ int launch_conv3x3_split(const void* x, const void* w, const float* bias, const 
         return with_flag(res != nullptr, [&](auto RES) { return launch_sp17<RES, 8>(x, w, bias, res, y, boards, relu, st, range); });
     if (C == 64) return with_flag(res != nullptr, [&](auto RES) { return launch_sp<RES, 8, 1>(x, w, bias, res, y, boards, relu, st, range); });
     // 9x9 x 128: k_conv3x3_sp2, the 2 x 2 split of a CU's work between its waves (round 6, az_conv_sp2.h: half the LDS fragment reads per MFMA)
-    const int grid = persistent_grid(boards, 2);
-    if (grid < 0) return -1;
+    // The first boards / 2 PAIRS of boards run k_conv3x3_sp2p (az_conv_sp2p.h: the same kernel over two boards at a time, without the MFMAs
+    // that only multiply the zero padding -- bit-identical); an odd last board runs k_conv3x3_sp2 on offset pointers.
+    const long long pairs = boards / 2;
+    const int pgrid = persistent_grid(pairs, 2), grid = persistent_grid(boards - 2 * pairs, 2);
+    if (pgrid < 0 || grid < 0) return -1;
+    const size_t off = (size_t)(2 * pairs) * 2 * 128 * SpGeo9::P2 * 2;  // bytes of 2 * pairs boards in the split layout
     return with_flag(res != nullptr, [&](auto RES) {
-        return launch_k(k_conv3x3_sp2<RES>, grid, CW_THREADS, 0, st, (const unsigned char*)x, (const _Float16*)w, bias, (const unsigned char*)res,
-                        (unsigned char*)y, (int)boards, relu, range);
+        const auto xb = (const unsigned char*)x, rb = (const unsigned char*)res;
+        const auto yb = (unsigned char*)y;
+        if (pairs > 0 && launch_k(k_conv3x3_sp2p<RES>, pgrid, CW_THREADS, 0, st, xb, (const _Float16*)w, bias, rb, yb, (int)pairs, relu, range)) return -1;
+        if (!(boards & 1)) return 0;
+        return launch_k(k_conv3x3_sp2<RES>, grid, CW_THREADS, 0, st, xb + off, (const _Float16*)w, bias, RES ? rb + off : rb, yb + off, 1, relu, range);
     });
 }
 // Lazily allocated scratch, one buffer per purpose and device, never freed.  Calls on different streams of one device that need the same
