@@ -23,12 +23,18 @@ GR_SLOT_MASK = (1 << GR_SLOT_RANK_SHIFT) - 1
 GX_TS_END, GX_THRESHOLD_LO, GX_THRESHOLD_HI, GX_STRADDLED, GX_COUNT = range(5)
 # q float64[SQ_COUNT]: azsp_get_search
 SQ_ROOT_Q, SQ_CHILD_Q, SQ_ROOT_N, SQ_MOVE, SQ_COUNT = range(5)
+# pos int32[G][PS_COUNT] (PS_ACTION: PSA_*), result int32[G] (SS_*): azsp_set_states; warm int32[G] (1 / 0 / -1 / BM_SKIP): azsp_begin_moves
+PS_ACTION, PS_TO_PLAY, PS_STEPS, PS_KO, PS_LAST_PASS, PS_CAPS_BLACK, PS_CAPS_WHITE, PS_COUNT = range(8)
+PSA_KEEP, PSA_LOAD, PSA_IDLE = 0, 1, 2
+SS_OK, SS_INVALID, SS_GAME_OVER = 0, 1, 2
+BM_SKIP = -2
 
 SYMBOLS = [
     "azsp_create", "azsp_destroy", "azsp_last_error", "azsp_geometry", "azsp_set_tables", "azsp_set_injection",
     "azsp_reset_games", "azsp_env_step", "azsp_set_state", "azsp_begin_move", "azsp_select", "azsp_expand_backup",
     "azsp_round", "azsp_get_status", "azsp_get_search", "azsp_commit_move", "azsp_harvest", "azsp_counters", "azsp_dihedral", "azsp_bias_act",
     "azsp_conv3x3_tiled", "azsp_tile_layout", "azsp_tiled_bytes", "azsp_stem_tiled", "azsp_head_tiled", "azsp_replay_gather", "azsp_rng_probe", "azsp_harvest_moves", "azsp_fc_heads", "azsp_harvest_extra", "azsp_set_actor_state", "azsp_resblock_tiled", "azsp_select_range", "azsp_expand_backup_range", "azsp_split_bytes", "azsp_split_layout", "azsp_conv3x3_split", "azsp_split_features", "azsp_stem_split", "azsp_head_split", "azsp_conv3x3_tiled_f16", "azsp_stem_tiled_f16", "azsp_head_tiled_f16", "azsp_fc_heads_f16", "azsp_split_range_status", "azsp_stem_split_exact", "azsp_split_range_read", "azsp_resblock_split", "azsp_dropin_step", "azsp_small_batch_waves",
+    "azsp_set_states", "azsp_begin_moves", "azsp_read_searches",
 ]
 
 COUNTER_NAMES = ["sims", "node_visits", "backup_edges", "leaves", "dup_leaves", "terminal_hits", "moves", "games", "root_evals",
@@ -67,7 +73,8 @@ class Binding:
             "azsp_create": [P(AzspConfig), P(V)], "azsp_destroy": [V], "azsp_geometry": [V, P(AzspGeometry)],
             "azsp_set_tables": [V, V, V, V, I], "azsp_set_injection": [V, V, V, I], "azsp_reset_games": [V, V],
             "azsp_env_step": [V, V, V, V, V, V, V], "azsp_set_state": [V, I, V, V, I, I, I, I, I, I, V],
-            "azsp_begin_move": [V, V, I, V], "azsp_select": [V, V, V, V], "azsp_expand_backup": [V, V, V, V],
+            "azsp_begin_move": [V, V, I, V], "azsp_set_states": [V, V, V, I, V, V, V], "azsp_begin_moves": [V, V, V, V],
+            "azsp_read_searches": [V, V, V, V, V, V], "azsp_select": [V, V, V, V], "azsp_expand_backup": [V, V, V, V],
             "azsp_round": [V, V, V, V, V, V], "azsp_select_range": [V, V, V, I, I, V], "azsp_expand_backup_range": [V, V, V, I, I, V], "azsp_get_status": [V, V, V, V], "azsp_get_search": [V, I, I, V, V, V, V],
             "azsp_commit_move": [V, V, V], "azsp_dropin_step": [V, V, V, V, V, V, V, V, V, V, V, C.c_int64, V], "azsp_harvest": [V, V, V, V, I, V, I, P(I), P(I), V],
             "azsp_counters": [V, V, I, V], "azsp_dihedral": [V, V, I, V, V, I, I, I, I, I, I, V],

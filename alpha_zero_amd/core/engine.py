@@ -193,6 +193,47 @@ class Engine:
         self._ck(self.b.dll.azsp_set_state(self.h, slot, b.ctypes.data, h.ctypes.data, int(to_play), int(steps), int(ko),
                                            int(bool(last_was_pass)), int(caps[0]), int(caps[1]), self._stream()), "azsp_set_state")
 
+    # -- many caller-supplied positions at once (azsp_set_states / azsp_begin_moves / azsp_read_searches) --------------
+    def _dev_tensor(self, x, dtype, shape):
+        """`x` as one contiguous tensor of `dtype` and `shape` on the engine's device (a host array is copied there once)."""
+        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+        t = t.to(device=self.device, dtype=dtype).contiguous()
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"expected a tensor of shape {tuple(shape)}, got {tuple(t.shape)}")
+        return t
+
+    def set_states(self, boards, hist, pos):
+        """One launch loads / keeps / idles every slot (azsp_set_states).  boards int8[G, N, N] and hist int8[G, H, N, N] (newest first,
+        1 <= H <= 8) in reference colour ids, pos int32[G, PS_COUNT] (_abi.PS_*; column PS_ACTION holds _abi.PSA_LOAD / PSA_KEEP /
+        PSA_IDLE): tensors on the engine's device, or host arrays that are copied there once.  Returns the result codes int32[G]
+        (_abi.SS_*) as a device tensor; nothing is synchronised."""
+        hb = hist.shape[1] if hasattr(hist, "shape") and len(hist.shape) >= 2 else 0
+        if not 1 <= hb <= 8:
+            raise ValueError(f"set_states takes 1..8 history boards per slot, got {hb}")
+        b = self._dev_tensor(boards, torch.int8, (self.G, self.N, self.N))
+        h = self._dev_tensor(hist, torch.int8, (self.G, hb, self.N, self.N))
+        p = self._dev_tensor(pos, torch.int32, (self.G, _abi.PS_COUNT))
+        res = torch.empty((self.G,), dtype=torch.int32, device=self.device)
+        self._ck(self.b.dll.azsp_set_states(self.h, b.data_ptr(), h.data_ptr(), hb, p.data_ptr(), res.data_ptr(), self._stream()), "azsp_set_states")
+        return res
+
+    def begin_moves(self, noise=None, warm=None):
+        """Per-slot begin_move (azsp_begin_moves): noise float64[G, A] or None, warm int32[G] (1 / 0 = the slot's warm_up flag, -1 = derive
+        from its steps, _abi.BM_SKIP = leave the slot alone; None = -1 everywhere).  Device tensors, or host arrays copied once."""
+        n = self._dev_tensor(noise, torch.float64, (self.G, self.A)) if noise is not None else None
+        w = self._dev_tensor(warm if warm is not None else np.full(self.G, -1, dtype=np.int32), torch.int32, (self.G,))
+        self._ck(self.b.dll.azsp_begin_moves(self.h, n.data_ptr() if n is not None else None, w.data_ptr(), self._stream()), "azsp_begin_moves")
+
+    def read_searches(self):
+        """The last finished search of every slot as DEVICE tensors (azsp_read_searches; nothing is synchronised):
+        (pi float64[G, A], child_N float32[G, A], q float64[G, STQ_COUNT], status int32[G, STC_COUNT])."""
+        pi = torch.empty((self.G, self.A), dtype=torch.float64, device=self.device)
+        cn = torch.empty((self.G, self.A), dtype=torch.float32, device=self.device)
+        q = torch.empty((self.G, _abi.STQ_COUNT), dtype=torch.float64, device=self.device)
+        st = torch.empty((self.G, _abi.STC_COUNT), dtype=torch.int32, device=self.device)
+        self._ck(self.b.dll.azsp_read_searches(self.h, pi.data_ptr(), cn.data_ptr(), q.data_ptr(), st.data_ptr(), self._stream()), "azsp_read_searches")
+        return pi, cn, q, st
+
     # -- search ---------------------------------------------------------------------------------------
     def begin_move(self, noise=None, warm_up=-1):
         n = np.ascontiguousarray(noise, dtype=np.float64).reshape(self.G, self.A) if noise is not None else None

@@ -89,17 +89,21 @@ struct OpStatus {
     double* q;
     template <class E> AZ_HD void operator()(E& e) const {
         if (E::Wave::first()) {
-            int* s = status + (size_t)e.g * AZSP_STC_COUNT;
-            s[AZSP_STC_STATUS] = e.gr.status;
-            s[AZSP_STC_PLY] = e.gr.ply;
-            s[AZSP_STC_ROOT_N] = e.gr.root_N;
-            s[AZSP_STC_N_LEAVES] = e.gr.n_leaves;
-            s[AZSP_STC_LAST_MOVE] = e.gr.out_move;
-            s[AZSP_STC_GAMES_DONE] = e.gr.games_done;
-            s[AZSP_STC_ROOT_EVAL_PENDING] = e.gr.root_eval_pending;
-            s[AZSP_STC_NOISE_PENDING] = e.gr.noise_pending;
-            q[(size_t)e.g * AZSP_STQ_COUNT + AZSP_STQ_ROOT_Q] = e.gr.out_root_q;
-            q[(size_t)e.g * AZSP_STQ_COUNT + AZSP_STQ_CHILD_Q] = e.gr.out_child_q;
+            if (status) {
+                int* s = status + (size_t)e.g * AZSP_STC_COUNT;
+                s[AZSP_STC_STATUS] = e.gr.status;
+                s[AZSP_STC_PLY] = e.gr.ply;
+                s[AZSP_STC_ROOT_N] = e.gr.root_N;
+                s[AZSP_STC_N_LEAVES] = e.gr.n_leaves;
+                s[AZSP_STC_LAST_MOVE] = e.gr.out_move;
+                s[AZSP_STC_GAMES_DONE] = e.gr.games_done;
+                s[AZSP_STC_ROOT_EVAL_PENDING] = e.gr.root_eval_pending;
+                s[AZSP_STC_NOISE_PENDING] = e.gr.noise_pending;
+            }
+            if (q) {
+                q[(size_t)e.g * AZSP_STQ_COUNT + AZSP_STQ_ROOT_Q] = e.gr.out_root_q;
+                q[(size_t)e.g * AZSP_STQ_COUNT + AZSP_STQ_CHILD_Q] = e.gr.out_child_q;
+            }
         }
     }
 };
@@ -197,6 +201,151 @@ struct OpSetState {
         }
         E::Wave::sync();
         e.free_all_nodes();
+    }
+};
+// Batched position load (azsp_set_states): every slot's wave reads ITS row of the caller's device tensors -- no host packing, no copy
+// through d_packed, no synchronisation.  The bitboards are built by ballot: lane l of ballot k answers for point l + 64k, so the 64-bit
+// mask IS word k of the plane (the idiom of Rules::go_legal).  A LOAD slot ends in exactly the state OpSetState leaves it in.
+struct OpSetStates {
+    const int8_t* boards;  // [G][NP] reference colour ids
+    const int8_t* hist;    // [G][hist_boards][NP], newest first
+    int hist_boards;       // 1..8; the history rows beyond it are empty boards
+    const int* pos;        // [G][AZSP_PS_COUNT]
+    int* result;           // [G] AZSP_SS_*
+    template <class E> static AZ_HD u64 plane_word(const int8_t* b, int k, int id) {
+        return E::Wave::ballot([&](int lane) -> bool {
+            const int p = lane + 64 * k;
+            return p < E::NP && b[p] == id;
+        });
+    }
+    template <class E> AZ_HD void idle(E& e, int code) const {  // the tree is freed, nothing is pending, status AZS_IDLE
+        if (E::Wave::first()) {
+            e.gr.n_leaves = 0;
+            e.gr.root_eval_pending = 0;
+            e.gr.noise_pending = 0;
+            e.gr.noise_ready = 0;
+            e.gr.status = AZS_IDLE;
+            result[e.g] = code;
+        }
+        E::Wave::sync();
+        e.free_all_nodes();
+    }
+    template <class E> AZ_HD void operator()(E& e) const {
+        typedef typename E::Wave Wv;
+        typedef typename E::R R;
+        typedef typename E::O O;
+        const int W = E::W, NP = E::NP;
+        const bool go = E::GAME_ID == AZ_GO;
+        const int* ps = pos + (size_t)e.g * AZSP_PS_COUNT;
+        const int action = Wv::uni(ps[AZSP_PS_ACTION]);
+        if (action == AZSP_PSA_KEEP) {  // tree, status, history and noise state stay as they are
+            if (Wv::first()) result[e.g] = AZSP_SS_OK;
+            return;
+        }
+        if (action != AZSP_PSA_LOAD) {
+            idle(e, action == AZSP_PSA_IDLE ? AZSP_SS_OK : AZSP_SS_INVALID);
+            return;
+        }
+        const int b_id = 1, w_id = go ? -1 : 2;
+        const int to_play = Wv::uni(ps[AZSP_PS_TO_PLAY]), steps = Wv::uni(ps[AZSP_PS_STEPS]), ko = Wv::uni(ps[AZSP_PS_KO]);
+        const int last_pass = Wv::uni(ps[AZSP_PS_LAST_PASS]), caps_b = Wv::uni(ps[AZSP_PS_CAPS_BLACK]), caps_w = Wv::uni(ps[AZSP_PS_CAPS_WHITE]);
+        const int8_t* bd = boards + (size_t)e.g * NP;
+        typename E::B sb, sw;
+        for (int k = 0; k < W; ++k) {
+            sb.w[k] = plane_word<E>(bd, k, b_id);
+            sw.w[k] = plane_word<E>(bd, k, w_id);
+        }
+        const typename E::B occ = O::bor(sb, sw);
+        // the scalars must fit the fields of EnvState (int16 steps / ko, uint16 caps); a ko point is an EMPTY point of a Go board
+        bool bad = (to_play != b_id && to_play != w_id) || steps < 0 || steps > 32767 || caps_b < 0 || caps_b > 65535 || caps_w < 0 || caps_w > 65535 ||
+                   ko < -1 || ko >= NP || (!go && ko != -1);
+        if (!bad && ko >= 0) bad = O::test(occ, ko);
+        if (bad) {
+            idle(e, AZSP_SS_INVALID);
+            return;
+        }
+        if (go ? steps >= e.c.rc.max_steps : O::count(occ) == NP) {  // go.py:176-178 / gomoku.py:131-136: nothing left to search
+            idle(e, AZSP_SS_GAME_OVER);
+            return;
+        }
+        typename E::S s;
+        R::st(s.stones[0], sb);
+        R::st(s.stones[1], sw);
+        s.to_play = (uint8_t)(to_play == b_id ? 0 : 1);
+        s.steps = (int16_t)steps;
+        s.ko = (int16_t)ko;
+        s.flags = last_pass ? AZF_LASTPASS : 0;
+        s.caps[0] = (uint16_t)caps_b;
+        s.caps[1] = (uint16_t)caps_w;
+        s.winner = -1;
+        s.reward = 0;
+        s.area[0] = s.area[1] = 0;
+        const typename E::B own = s.to_play == 0 ? sb : sw, opp = s.to_play == 0 ? sw : sb;
+        const typename E::B legal = go ? R::go_legal(own, opp, s.ko) : O::inv(occ);
+        R::st(s.legal, legal);
+        for (int k = 0; k < 8; ++k) {
+            const int8_t* hb = hist + ((size_t)e.g * hist_boards + (k < hist_boards ? k : 0)) * NP;
+            for (int q = 0; q < 2; ++q)
+                for (int w = 0; w < W; ++w) {
+                    const u64 word = k < hist_boards ? plane_word<E>(hb, w, q == 0 ? b_id : w_id) : 0ull;
+                    if (Wv::first()) e.gr.hist[k][q][w] = word;
+                }
+        }
+        if (Wv::first()) {
+            e.gr.env = s;
+            e.gr.ply = 0;
+            e.gr.num_passes = 0;
+            e.gr.marked_player = -1;
+            e.gr.n_leaves = 0;
+            e.gr.root_eval_pending = 0;
+            e.gr.noise_pending = 0;
+            e.gr.noise_ready = 0;
+            e.gr.status = AZS_NEED_ROOT;
+            result[e.g] = AZSP_SS_OK;
+        }
+        Wv::sync();
+        e.free_all_nodes();
+    }
+};
+// azsp_begin_moves: OpBeginMove with one warm flag per slot, the slot's wave copying its own noise row out of the caller's device tensor
+struct OpBeginMoves {
+    const double* noise;  // [G][A] or null
+    const int* warm;      // [G]
+    double* dst;          // the engine's injected-noise rows [G][A] (drop-in mode: one row per game)
+    template <class E> AZ_HD void operator()(E& e) const {
+        const int wf = E::Wave::uni(warm[e.g]);
+        if (wf == AZSP_BM_SKIP) return;
+        const int A = E::A;
+        if (noise)
+            E::Wave::lanes([&](int lane) {
+                for (int a = lane; a < A; a += AZ_WAVE) dst[(size_t)e.g * A + a] = noise[(size_t)e.g * A + a];
+            });
+        if (E::Wave::first()) {
+            e.gr.noise_ready = 1;
+            e.gr.warm_override = wf;
+        }
+        E::Wave::sync();
+    }
+};
+// azsp_read_searches: the slot's wave copies its search outputs (the log slot search_done wrote) and its status row to the caller's tensors
+struct OpReadSearches {
+    double* pi;
+    float* child_n;
+    double* q;
+    int* status;
+    template <class E> AZ_HD void operator()(E& e) const {
+        const int A = E::A;
+        const size_t o = ((size_t)e.g * e.c.log_cap + e.log_slot()) * A;
+        const double* lp = e.m.log_pi + o;
+        const float* ln = e.m.log_childN + o;
+        E::Wave::lanes([&](int lane) {
+            for (int a = lane; a < A; a += AZ_WAVE) {
+                if (pi) pi[(size_t)e.g * A + a] = lp[a];
+                if (child_n) child_n[(size_t)e.g * A + a] = ln[a];
+            }
+        });
+        OpStatus st = {status, q};
+        st(e);
     }
 };
 struct OpEnvStep {
@@ -916,6 +1065,28 @@ int azsp_begin_move(void* e, const double* noise, int32_t warm_up, void* stream)
     if (!h) return AZSP_EINVAL;
     if (noise && azb::h2d((void*)h->mem.inj_noise, noise, sizeof(double) * (size_t)h->cfg.G * h->A, stream)) return AZSP_EDEVICE;
     OpBeginMove op = {warm_up};
+    return az_run(h, op, stream);
+}
+
+int azsp_set_states(void* e, const int8_t* boards, const int8_t* hist, int32_t hist_boards, const int32_t* pos, int32_t* result, void* stream) {
+    AzHandle* h = (AzHandle*)e;
+    if (!h || !boards || !hist || !pos || !result || hist_boards < 1 || hist_boards > 8) return AZSP_EINVAL;
+    OpSetStates op = {boards, hist, hist_boards, pos, result};
+    return az_run(h, op, stream);
+}
+
+int azsp_begin_moves(void* e, const double* noise, const int32_t* warm, void* stream) {
+    AzHandle* h = (AzHandle*)e;
+    // noise rows exist one per game in drop-in mode only (azsp_create sizes inj_noise [G][A] there)
+    if (!h || !warm || (noise && (!h->cfg.stop_after_move || h->cfg.inj_moves != 1))) return AZSP_EINVAL;
+    OpBeginMoves op = {noise, warm, (double*)h->mem.inj_noise};
+    return az_run(h, op, stream);
+}
+
+int azsp_read_searches(void* e, double* pi, float* cn, double* q, int32_t* status, void* stream) {
+    AzHandle* h = (AzHandle*)e;
+    if (!h) return AZSP_EINVAL;
+    OpReadSearches op = {pi, cn, q, status};
     return az_run(h, op, stream);
 }
 

@@ -14,6 +14,10 @@
  *                                      :123-152, envs/base.py:228-259)
  *   azsp_set_state                    the `env` argument of uct_search()        (core/mcts_v2.py:301-311)
  *   azsp_begin_move                   add_dirichlet_noise at the start of a search (core/mcts_v2.py:375-376, :565-566)
+ *   azsp_set_states                   the `env` arguments of G uct_search() calls at once: every slot loads, keeps or drops its
+ *                                     position from device tensors in one launch (core/mcts_v2.py:301-311)
+ *   azsp_begin_moves                  add_dirichlet_noise and the `warm_up` argument per slot (core/mcts_v2.py:375-376)
+ *   azsp_read_searches                the tuples G uct_search() calls return, into device tensors (core/mcts_v2.py:450)
  *   azsp_select                       Phase 1 of (parallel_)uct_search: best_child descents, virtual loss,
  *                                     and env.observation() of the leaves       (core/mcts_v2.py:572-611)
  *   azsp_expand_backup                Phases 2-3: expand + backup, then (when the budget is met) policy,
@@ -184,6 +188,44 @@ int azsp_set_state(void* engine, int32_t slot, const int8_t* board_host, const i
 /* Drop-in mode: hand the Dirichlet draw of this search to the engine (noise_host double[G][A] or NULL) and the
  * `warm_up` flag of uct_search (1: temperature 1.0, 0: temperature 0.1, -1: derive from env.steps <= warm_up_steps). */
 int azsp_begin_move(void* engine, const double* noise_host, int32_t warm_up, void* stream);
+
+/* Batched form of azsp_set_state: ONE launch in which the wave of every slot reads its own row of the caller's DEVICE tensors (no
+ * host packing, no copy, no synchronisation).  boards_dev int8[G][N*N] and hist_dev int8[G][hist_boards][N*N] (newest first, 1 <=
+ * hist_boards <= 8; the engine's history rows beyond hist_boards become empty boards) use reference colour ids; pos_dev
+ * int32[G][AZSP_PS_COUNT] holds the columns below; result_dev int32[G] receives one AZSP_SS_* code per slot.  A slot whose action
+ * is AZSP_PSA_LOAD ends in exactly the state azsp_set_state leaves it in (a fresh, unevaluated search root); AZSP_PSA_KEEP leaves the
+ * slot untouched (tree, status, history, noise state); AZSP_PSA_IDLE frees its tree and sets its status to AZSP_ST_IDLE.  A LOAD row
+ * that is refused (AZSP_SS_INVALID, AZSP_SS_GAME_OVER; any other action value is INVALID too) leaves the slot idle as well; the
+ * engine's fault flags are not touched.  (Plain #defines, not an enum: these are columns of a tensor the CALLER fills.) */
+#define AZSP_PS_ACTION 0      /* AZSP_PSA_* */
+#define AZSP_PS_TO_PLAY 1     /* ref id */
+#define AZSP_PS_STEPS 2
+#define AZSP_PS_KO 3          /* the ko point, -1 = none */
+#define AZSP_PS_LAST_PASS 4   /* 1: the last move was a pass */
+#define AZSP_PS_CAPS_BLACK 5
+#define AZSP_PS_CAPS_WHITE 6
+#define AZSP_PS_COUNT 7
+#define AZSP_PSA_KEEP 0
+#define AZSP_PSA_LOAD 1
+#define AZSP_PSA_IDLE 2
+#define AZSP_SS_OK 0
+#define AZSP_SS_INVALID 1     /* to_play is no colour id; negative (or over-wide) steps / captures; a ko point off the board, on a stone, or given at Gomoku */
+#define AZSP_SS_GAME_OVER 2   /* Go: steps >= max_steps; Gomoku: the board is full */
+int azsp_set_states(void* engine, const int8_t* boards_dev, const int8_t* hist_dev, int32_t hist_boards, const int32_t* pos_dev,
+                    int32_t* result_dev, void* stream);
+
+/* Batched form of azsp_begin_move (drop-in mode): noise_dev double[G][A] on the DEVICE or NULL, warm_dev int32[G] with one `warm_up`
+ * flag per slot (1 / 0 as azsp_begin_move, -1 = derive from env.steps) or AZSP_BM_SKIP = leave the slot alone: its noise row is not
+ * read and the state of a search it has pending is unchanged.  Each slot's wave copies its own noise row.  Does not synchronise. */
+#define AZSP_BM_SKIP (-2)
+int azsp_begin_moves(void* engine, const double* noise_dev, const int32_t* warm_dev, void* stream);
+
+/* Batched form of azsp_get_search + azsp_get_status into DEVICE tensors: pi_dev double[G][A], child_n_dev float[G][A] = the last
+ * finished search of every slot, q_dev double[G][AZSP_STQ_COUNT] and status_dev int32[G][AZSP_STC_COUNT] as azsp_get_status.  Each
+ * may be NULL.  The log slot it reads is the one the slot's search writes: in drop-in mode (log_moves = 0) log slot 0 of every game,
+ * i.e. azsp_get_search(slot, 0); with log_moves the slot of the game's current ply, min(ply, log_capacity - 1), which holds the
+ * search that has just finished while the status is AZSP_ST_MOVE_DONE.  Does not synchronise. */
+int azsp_read_searches(void* engine, double* pi_dev, float* child_n_dev, double* q_dev, int32_t* status_dev, void* stream);
 
 int azsp_select(void* engine, void* features_dev, uint8_t* valid_dev, void* stream);
 int azsp_expand_backup(void* engine, const float* priors_dev, const float* values_dev, void* stream);
