@@ -1,28 +1,54 @@
-// az_conv_sp2p.h -- k_conv3x3_sp2p<RES>: k_conv3x3_sp2 (az_conv_sp2.h: the fp32-class 3x3 convolution of the 9x9 x 128 tower, 2 x 2 wave split,
-// hand-over buffer, riders in the MFMA gaps) with one workgroup iteration covering a PAIR of adjacent boards (2p, 2p + 1), so that the
-// MFMAs which only multiply the zero padding can be skipped.
-//   On a 9x9 board 104 of the 729 (position, tap) pairs are off the board.  A column tile is 16 positions; inside ONE board no two disjoint
-//   tiles are off the board for the same tap in all 16 positions.  Over two boards three such tiles exist: row 0 (columns 1-8), row 8
+// az_conv_sp2p.h -- k_conv3x3_sp2p<RES>: the fp32-class 3x3 convolution of the 9x9 x 128 tower (az_conv_sp.h: hi + lo f16 pairs, three
+// v_mfma_f32_16x16x32_f16 products per multiply, fp32 accumulation) with a 2 x 2 SPLIT OF THE CU'S WORK BETWEEN ITS FOUR WAVES and one
+// workgroup iteration per PAIR of adjacent boards (2p, 2p + 1), so that the MFMAs which only multiply the zero padding can be skipped:
+//     y = relu(conv3x3(x, w) + bias [+ residual])              (alpha_zero/core/network.py:42-82, eval mode, BatchNorm folded;
+//                                                               the reference evaluates in fp32: core/pipeline.py:91-123)
+// The 2 x 2 split.  k_conv3x3_sp gives every wave 16 couts x all 128 cin: all four waves read EVERY B fragment of the board from LDS
+// (2 reads per 3 MFMAs).  Measured (tools/probes/split_form_probe.hip, profiles/r06_split_form_probe.txt): with those reads in the loop the
+// matrix cores sustain 1.50 PF/s; with half of them 1.70 PF/s.  Here wave (a, b) holds 32 couts (two 16-cout tiles) x the cin HALF b: the
+// same 288 weight registers, every fragment feeds 6 MFMAs instead of 3, a wave reads half the image.
+// The hand-over buffer.  The two cin halves of a cout tile meet through LDS: after a unit each wave joins (main + 2^-11 corr) the partial
+// sums of the tile its PARTNER finalises, hands them over (one ds_write_b128 per column tile), and runs the epilogue of its own tile with
+// the partner's partial added in.  Wave b = 1 loads its weight tiles swapped, so "own tile" is index 0 in both waves (compile-time register
+// indices); the bias enters through the own tile's main accumulator only.  12 KB (3 column tiles x 4 waves x 1 KB) beside the two x images
+// (120 KB) and the corner side buffer; the buffer is single, so a barrier orders a unit's hand-over writes behind the partner's reads of
+// the previous hand-over.
+// The riders.  A unit's MFMA stream is never interrupted: the hand-over, the finishing epilogue of the previous unit (join, residual,
+// stores), the residual loads, the B-fragment requests (one ds_read_b128 per MFMA gap), the LDS-DMA pieces of the next image and the
+// barriers ride in the gaps behind its MFMAs (send_op / fin_op / dma_piece below).
+// Arithmetic: result = (main_a + 2^-11 corr_a) + (main_b + 2^-11 corr_b) [+ residual]: two fp32 accumulation chains of 64 cin x 9 taps
+// instead of one of 128 x 9, joined once -- fp32 round-off class (tests/test_split_tower.py bounds), not bit-identical to k_conv3x3_sp;
+// k_conv3x3_spg<..., HALVES = 2> (az_conv_spg.h) repeats these chains bit for bit and runs the odd last board of a call.
+// The pair.  On a 9x9 board 104 of the 729 (position, tap) pairs are off the board.  A column tile is 16 positions; inside ONE board no two
+//   disjoint tiles are off the board for the same tap in all 16 positions.  Over two boards three such tiles exist: row 0 (columns 1-8), row 8
 //   (columns 1-8) and column 0 (rows 0-7) of both boards: each has 3 of the 9 taps off the board = 9 of the 90 (tile, tap) pairs of a board
 //   pair.  Their 6 MFMAs and 2 fragment reads per k-step are not issued: 972 MFMAs per wave and pair instead of 1080.  A skipped MFMA
-//   added exact zeros, the order of every output's sum is unchanged: bit-identical to k_conv3x3_sp2 -- up to the sign of a zero: a bias of
-//   exactly -0.0 turns +0 in k_conv3x3_sp2's first padding MFMA and passes unchanged through the C operand of a later first live MFMA here.
+//   would add exact zeros, the order of every output's sum is unchanged: bit-identical to multiplying the padding -- up to the sign of a
+//   zero: a bias of exactly -0.0 turns +0 in a first padding MFMA and passes unchanged through the C operand of a later first live MFMA here.
 // Tile map (sp2p_map_table, tools/gen_sp_map_pair.py): 10 column tiles per pair -- 0-2 local to board A, 3 = top edge, 4 = the same 8
 // positions of both boards, 5 = bottom edge, 6 = left edge, 7-9 local to board B; the corner (8, 0) of each board stays with the
 // board-batched corner phase (12 boards per batch).  A lane's lmap / omap entries carry the second image's LDS offset and the second board's
 // global offset: compile-time constants, the pair is adjacent boards.
-// Units (3, 2, 3, 2 column tiles; accumulator sets 0, 1, 0, 1 as in k_conv3x3_sp2): U0 = tiles 0-2 (image A only), U1 = tiles 3, 4,
+// Units (3, 2, 3, 2 column tiles; accumulator sets 0, 1, 0, 1): U0 = tiles 0-2 (image A only), U1 = tiles 3, 4,
 // U2 = tiles 5-7, U3 = tiles 8, 9 (image B only).  LDS buffer 0 always holds image A, buffer 1 image B: A is free behind U2, the next pair's
 // A arrives as 16 LDS-DMA pieces in U3 and is complete at U3's end barrier; B is free behind U3, this pair's B arrives in U0 and is complete
-// at U0's end barrier.  Barriers per pair: 8, as for two boards of k_conv3x3_sp2 (per unit the hand-over barrier; the end barriers of U0 and
+// at U0's end barrier.  Barriers per pair: 8 (per unit the hand-over barrier; the end barriers of U0 and
 // U3, which also free the hand-over buffer for the next unit; U2 and U3 open with the barrier that frees it behind a unit without one).
 // The MFMA slots of a unit are a compile-time list (Sp2pSched) of the live (k-step, column tile, cout tile, product) entries; the riders
 // (hand-over, finishing, residual loads, fragment requests, DMA pieces, barriers) are indexed over that list.
 #pragma once
-#include "az_conv_sp2.h"
+#include "az_conv_sp.h"
 
 #if defined(__HIPCC__)
 #define SP2P_NB 12  // boards per corner batch (an even number: whole pairs)
+
+// one v_fma_f32, opaque to the compiler: left to itself it pairs the four joins of a hand-over into two v_pk_fma_f32, and a packed fp32
+// instruction costs about four scalar ones beside the MFMA stream (measured: profiles/r06_packed_epilogue_ab.txt)
+__device__ __forceinline__ float sp2_fma_f32(float a, float s, float c) {
+    float r;
+    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(s), "v"(c));
+    return r;
+}
 
 struct Sp2pMap {
     unsigned char cell[10 * 16];  // board * 81 + position
@@ -120,7 +146,7 @@ constexpr Sp2pSched sp2p_sched(int u) {
             }
         s.live_n[t] = ln;
         s.kstart[t] = n;
-        for (int r6 = 0; r6 < 6; ++r6)  // (cout tile, product) outer, column tile inner: as k_conv3x3_sp2
+        for (int r6 = 0; r6 < 6; ++r6)  // (cout tile, product) outer, column tile inner
             for (int k = 0; k < ln; ++k) {
                 const int j = s.live[t][k];
                 s.t[n] = (unsigned char)t, s.jl[n] = (unsigned char)j, s.tt[n] = (unsigned char)(r6 / 3), s.prod[n] = (unsigned char)(r6 % 3);

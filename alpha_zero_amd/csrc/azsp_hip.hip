@@ -13,7 +13,6 @@
 #include "az_conv_sp.h"
 #include "az_conv_sp17.h"
 #include "az_resblock_sp17.h"
-#include "az_conv_sp2.h"
 #include "az_conv_sp2p.h"
 #include "az_conv_spg.h"
 #include "az_stem_spg.h"
@@ -287,7 +286,7 @@ static int launch_sp17(const void* x, const void* w, const float* bias, const vo
 // k_conv3x3_spg (az_conv_spg.h): the fp32-class convolution with one WAVE per output tile -- any plane size, 64 / 128 / 256 filters.
 // `latency`: small tiles (16 couts x 32 positions per wave) so that a handful of boards fill the chip; otherwise k_conv3x3_spgw:
 // 16 NT couts x 48 positions per wave, the B fragments shared by the four waves of a workgroup through LDS.
-// `halves` = 2: k_conv3x3_sp2's two accumulation chains (bit-identical to it at 9x9 x 128).
+// `halves` = 2: k_conv3x3_sp2p's two accumulation chains (bit-identical to it at 9x9 x 128).
 template <bool RES, int KSUB, int NT, int NJ, int HALVES>
 static int launch_spg_t(const void* x, const void* w, const float* bias, const void* res, void* y, long long boards, int S, int C, int relu, void* st,
                         unsigned* range) {
@@ -347,31 +346,30 @@ long long small_batch_waves(long long n) {
 int launch_conv3x3_split(const void* x, const void* w, const float* bias, const void* res, void* y, long long boards, int S, int C, int relu,
                          void* st, unsigned* range) {
     const bool sp17 = S == Sp17Geo::S && C == 64, sp9 = S == SpGeo9::S && (C == 128 || C == 64), small = small_batch(boards, S, C);
-    // no tailored (weight-stationary) kernel for the shape, or a handful of boards: one wave per tile; at 9x9 x 128 in k_conv3x3_sp2's summation order
+    // no tailored (weight-stationary) kernel for the shape, or a handful of boards: one wave per tile; at 9x9 x 128 in k_conv3x3_sp2p's summation order
     if (!(sp17 || sp9) || small) return launch_spg(x, w, bias, res, y, boards, S, C, relu, st, range, small, sp9 && C == 128 ? 2 : 1);
     if (sp17)  // 17x17 planes x 64 filters: the 13x13 Gomoku tower (half-board tiles)
         return with_flag(res != nullptr, [&](auto RES) { return launch_sp17<RES, 8>(x, w, bias, res, y, boards, relu, st, range); });
     if (C == 64) return with_flag(res != nullptr, [&](auto RES) { return launch_sp<RES, 8, 1>(x, w, bias, res, y, boards, relu, st, range); });
-    // 9x9 x 128: k_conv3x3_sp2, the 2 x 2 split of a CU's work between its waves (round 6, az_conv_sp2.h: half the LDS fragment reads per MFMA)
-    // The first boards / 2 PAIRS of boards run k_conv3x3_sp2p (az_conv_sp2p.h: the same kernel over two boards at a time, without the MFMAs
-    // that only multiply the zero padding -- bit-identical); an odd last board runs k_conv3x3_sp2 on offset pointers.
+    // 9x9 x 128: k_conv3x3_sp2p (az_conv_sp2p.h): the 2 x 2 split of a CU's work between its waves (half the LDS fragment reads per MFMA), one
+    // workgroup iteration per PAIR of adjacent boards, without the MFMAs that only multiply the zero padding.  It runs the first boards / 2
+    // pairs; an odd last board runs the wave-per-tile kernel on offset pointers (bit-identical; whatever the small-batch limit is, also 0).
     const long long pairs = boards / 2;
-    const int pgrid = persistent_grid(pairs, 2), grid = persistent_grid(boards - 2 * pairs, 2);
-    if (pgrid < 0 || grid < 0) return -1;
+    const int pgrid = persistent_grid(pairs, 2);
+    if (pgrid < 0) return -1;
     const size_t off = (size_t)(2 * pairs) * 2 * 128 * SpGeo9::P2 * 2;  // bytes of 2 * pairs boards in the split layout
-    return with_flag(res != nullptr, [&](auto RES) {
-        const auto xb = (const unsigned char*)x, rb = (const unsigned char*)res;
-        const auto yb = (unsigned char*)y;
-        if (pairs > 0 && launch_k(k_conv3x3_sp2p<RES>, pgrid, CW_THREADS, 0, st, xb, (const _Float16*)w, bias, rb, yb, (int)pairs, relu, range)) return -1;
-        if (!(boards & 1)) return 0;
-        return launch_k(k_conv3x3_sp2<RES>, grid, CW_THREADS, 0, st, xb + off, (const _Float16*)w, bias, RES ? rb + off : rb, yb + off, 1, relu, range);
+    const auto xb = (const unsigned char*)x, rb = (const unsigned char*)res;
+    const auto yb = (unsigned char*)y;
+    const int rc = with_flag(res != nullptr, [&](auto RES) {
+        return pairs > 0 ? launch_k(k_conv3x3_sp2p<RES>, pgrid, CW_THREADS, 0, st, xb, (const _Float16*)w, bias, rb, yb, (int)pairs, relu, range) : 0;
     });
+    if (rc || !(boards & 1)) return rc;
+    return launch_spg(xb + off, w, bias, res ? rb + off : nullptr, yb + off, 1, S, C, relu, st, range, true, 2);
 }
 // Lazily allocated scratch, one buffer per purpose and device, never freed.  Calls on different streams of one device that need the same
 // buffer would share it -- the evaluator runs one stream per network.
 enum Scratch {
     SCRATCH_SPG_BLOCK,  // the intermediate activations of azsp_resblock_split on a handful of boards: SPG_SCRATCH_BOARDS boards of 17x17 x 64
-    SCRATCH_SP9_TAIL,   // the intermediate activation of ONE 9x9 x 64 board: the odd last board of azsp_resblock_split at 9x9
     SCRATCH_COUNT
 };
 static constexpr long long SPG_SCRATCH_BOARDS = 256;
@@ -382,32 +380,34 @@ static void* device_scratch(Scratch which, size_t bytes) {
     if (!buf[which][dev] && AZ_HIP(hipMalloc(&buf[which][dev], bytes))) return nullptr;
     return buf[which][dev];
 }
+// A ResNetBlock of up to SPG_SCRATCH_BOARDS boards x 64 filters as two wave-per-tile convolutions (az_conv_spg.h) through the block scratch:
+// conv1 with ReLU into the scratch, conv2 with the residual x into y -- bit-identical to the fused block.  The scratch is sized once for
+// SPG_SCRATCH_BOARDS boards of 17x17 (19 MB), whoever asks first: a process that only ever meets the odd last 9x9 board allocates it too
+// (that tail had a 20 KB buffer of its own).
+static int launch_resblock_spg(const unsigned char* x, const void* w1, const float* b1, const void* w2, const float* b2, unsigned char* y, long long boards,
+                               int S, int C, void* st, unsigned* range) {
+    void* mid = device_scratch(SCRATCH_SPG_BLOCK, (size_t)SPG_SCRATCH_BOARDS * 2 * 8 * Sb17::S * Sb17::S * 16);
+    if (!mid) return -1;
+    const int rc = launch_spg(x, w1, b1, nullptr, mid, boards, S, C, 1, st, range, true, 1);
+    if (rc) return rc;
+    return launch_spg(mid, w2, b2, x, y, boards, S, C, 1, st, range, true, 1);
+}
 int launch_resblock_split(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* y, long long boards, int S, int C,
                           void* st, unsigned* range) {
     if (C != 64 || (S != Sb17::S && S != Sb9::S)) return 1;  // 17x17 planes (the 13x13 Gomoku tower) or 9x9 planes (9x9 Go, logs/go/9x9_12b64) x 64 filters
     const long long pairs = boards / 2;  // 9x9: the fused kernel takes blocks of TWO boards
     const int grid = persistent_grid(S == Sb9::S ? pairs : boards);  // 17x17: a board = two half-board tiles x two phases
     if (grid < 0) return -1;
-    if (small_batch(boards, S, C) && boards <= SPG_SCRATCH_BOARDS) {
-        // a handful of boards: two wave-per-tile convolutions (az_conv_spg.h) instead of one workgroup per board -- bit-identical results
-        void* mid = device_scratch(SCRATCH_SPG_BLOCK, (size_t)SPG_SCRATCH_BOARDS * 2 * 8 * Sb17::S * Sb17::S * 16);
-        if (!mid) return -1;
-        const int rc = launch_spg(x, w1, b1, nullptr, mid, boards, S, C, 1, st, range, true, 1);
-        if (rc) return rc;
-        return launch_spg(mid, w2, b2, x, y, boards, S, C, 1, st, range, true, 1);
-    }
     const auto xb = (const unsigned char*)x;
     const auto yb = (unsigned char*)y;
+    // a handful of boards: the wave-per-tile convolutions instead of one workgroup per board
+    if (small_batch(boards, S, C) && boards <= SPG_SCRATCH_BOARDS) return launch_resblock_spg(xb, w1, b1, w2, b2, yb, boards, S, C, st, range);
+    // the fused block: one launch per ResNetBlock; at 9x9 on the first boards / 2 pairs, and an odd last board runs as the handful above
     if (S == Sb17::S) return launch_k(k_resblock_sp<Sb17, 6>, grid, CW_THREADS, 0, st, xb, (const _Float16*)w1, b1, (const _Float16*)w2, b2, yb, (int)boards, range);
     if (pairs > 0 && launch_k(k_resblock_sp<Sb9, 6>, grid, CW_THREADS, 0, st, xb, (const _Float16*)w1, b1, (const _Float16*)w2, b2, yb, (int)pairs, range)) return -1;
     if (!(boards & 1)) return 0;
-    // an odd last board: the two unfused convolutions (bit-identical results)
-    void* mid = device_scratch(SCRATCH_SP9_TAIL, (size_t)Sb9::GTILEB);
-    if (!mid) return -1;
     const size_t off = (size_t)(boards - 1) * Sb9::GTILEB;
-    const int rc = launch_sp<false, 8, 1>(xb + off, w1, b1, nullptr, mid, 1, 1, st, range);
-    if (rc) return rc;
-    return launch_sp<true, 8, 1>(mid, w2, b2, xb + off, yb + off, 1, 1, st, range);
+    return launch_resblock_spg(xb + off, w1, b1, w2, b2, yb + off, 1, S, C, st, range);
 }
 int launch_split_features(const float* src, void* dst, long long boards, int S, int cin, void* st, unsigned* range) {
     if (cin < 1 || cin > 32 || S < 1) return 1;

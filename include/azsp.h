@@ -400,7 +400,8 @@ int azsp_resblock_tiled(const void* x_dev, const void* w1_packed_dev, const floa
  * network.py:101-105; half-board tiles, az_conv_sp17.h); since round 6 every other plane size 3 <= S <= 64 with C = 64, 128 or 256
  * on the wave-per-tile kernel (az_conv_spg.h: e.g. the 19x19 x 256 jumbo tower at the reference's own precision,
  * alpha_zero/training_go_jumbo.py:46-47) -- and the three shapes above too when the call is small (azsp_small_batch_waves below;
- * bit-identical results).  AZSP_EINVAL for other shapes.
+ * bit-identical results).  (9, 128) runs PAIRS of boards per workgroup (az_conv_sp2p.h); an odd last board always runs the wave-per-tile
+ * kernel, also with that limit at 0 (bit-identical results).  AZSP_EINVAL for other shapes.
  * range_rec_dev: the caller's range record -- two zero-initialised uint32 words in device memory, owned by the caller (one per
  * network: two evaluators in one process never see each other's events), read with azsp_split_range_read; NULL selects the library's
  * per-device default record (azsp_split_range_status). */
@@ -416,7 +417,7 @@ int azsp_conv3x3_split(const void* x_dev, const void* w_split_dev, const float* 
  * through HBM instead of five; results are bit-identical to two azsp_conv3x3_split calls (same MFMA order, same roundings).  w1 / w2 in
  * the packing of azsp_conv3x3_split, b1 / b2 float[64]; y must NOT alias x.  On the device: (S, C) = (17, 64), the 13x13 Gomoku tower
  * (half-board tiles, az_resblock_sp17.h), and (9, 64), the reference's 64-filter 9x9 Go towers (logs/go/9x9_12b64; two boards per tile, an odd
- * last board runs as the two unfused launches); AZSP_EINVAL for other shapes.  range_rec_dev as above. */
+ * last board runs as two wave-per-tile launches); AZSP_EINVAL for other shapes.  range_rec_dev as above. */
 int azsp_resblock_split(const void* x_dev, const void* w1_split_dev, const float* bias1_dev, const void* w2_split_dev, const float* bias2_dev,
                         void* y_dev, int64_t boards, int32_t board_size, int32_t channels, uint32_t* range_rec_dev, void* stream);
 
@@ -469,7 +470,8 @@ int azsp_split_range_status(uint32_t* events_host, float* max_abs_host, int32_t 
  * arrives in) -- the batch-1 forwards of a drop-in uct_search (alpha_zero/core/mcts_v2.py:301-450 evaluates one leaf at a time).
  * Sets the process-wide limit and returns the previous one; a negative argument only queries.  Default 1024 (one wave per SIMD of an
  * MI355X: the measured crossover, profiles/r06_spg_ab.txt), or the environment variable AZSP_SPG_MAX_WAVES; 0 = always the
- * weight-stationary kernels.  Shapes without a weight-stationary kernel (plane sizes 3 .. 64, 64 / 128 / 256 filters) always run
+ * weight-stationary kernels -- except the odd last board of a (9, 128) convolution or a (9, 64) block, which their two-board workgroups
+ * cannot take: it runs k_conv3x3_spg whatever the limit.  Shapes without a weight-stationary kernel (plane sizes 3 .. 64, 64 / 128 / 256 filters) always run
  * k_conv3x3_spg (beyond `waves`: k_conv3x3_spgw, 48-position tiles whose activations a workgroup shares through LDS).
  * azsp_stem_split / azsp_stem_split_exact obey the same limit on their three tailored shapes, but only once it exceeds the default:
  * 0 = always the tailored stems, a huge value = the wave-per-tile stem k_stem_spg at any board count, the default = the tailored stems:

@@ -43,7 +43,10 @@ def test_tower_roofline_of_the_headline_kernel():
     if pj.get("cycles_per_mfma"):  # a round-6 PMC pass: the decomposition of frac
         assert abs(r["issue_efficiency"] - (16.0 / r["instruction_form_ceiling"]) / pj["cycles_per_mfma"]) < 2e-3
         assert abs(r["clock_fraction"] - pj["gpu_cycles_per_launch_mean"] / 1.74e-3 / 2.4e9) < 1e-3 and 0.5 < r["clock_fraction"] < 1.0
-        assert 0.99 < r["issued_over_algorithmic_mfma"] < 1.03  # 9x9 x 128: 81 positions in 5 column tiles + 1 / 16
+        # k_conv3x3_sp2p on 256 CUs at 32 768 boards: a wave works through 128 pairs x 972 MFMAs (the padding-only ones are skipped) + 22 corner
+        # batches x 48 = 125 472 MFMAs on 1024 waves = 128 483 328 (the counter's value), x 16 384 flop over 3 x 2 x 32 768 x 81 x 128 x 128 x 9
+        # = 0.8964: the skip puts the issued count UNDER the algorithmic one (which multiplies the padding)
+        assert abs(r["issued_over_algorithmic_mfma"] - 0.8964) < 0.005
         assert abs(r["decomposition_product"] - r["instruction_form_ceiling"] * r["issue_efficiency"] * r["clock_fraction"] / r["issued_over_algorithmic_mfma"]) < 1e-3
         assert abs(r["decomposition_product"] - r["frac"]) < 0.03  # the three factors explain the fraction
 

@@ -1,6 +1,6 @@
 """k_conv3x3_sp2p (alpha_zero_amd/csrc/az_conv_sp2p.h): the 9x9 x 128 fp32-class convolution over PAIRS of boards, without the MFMAs that only
-multiply the zero padding of the edge tiles.  It sums every output in k_conv3x3_sp2's order, so it must agree word for word with the
-wave-per-tile kernel (k_conv3x3_spg, HALVES = 2), which takes no part in the pair scheme; and it must keep the fp64 bound of
+multiply the zero padding of the edge tiles.  A skipped MFMA would add exact zeros, so it must agree word for word with the
+wave-per-tile kernel (k_conv3x3_spg, HALVES = 2: the same two accumulation chains), which takes no part in the pair scheme and multiplies the padding; and it must keep the fp64 bound of
 tests/test_split_tower.py.  Board counts follow the persistent loop's paths on the device at hand (slots = CUs / 2 pairs in flight)."""
 import functools
 
@@ -42,8 +42,8 @@ def test_gpu_pair_kernel_is_bit_identical_to_the_wave_per_tile_kernel(count):
     bnd = _lib.load()
     boards = _boards(count)
     for res, relu in CASES:
-        a = _conv(bnd, boards, res, relu, 0)         # tailored path: k_conv3x3_sp2p on the pairs, k_conv3x3_sp2 on an odd last board
-        g = _conv(bnd, boards, res, relu, 1 << 20)   # k_conv3x3_spg everywhere
+        a = _conv(bnd, boards, res, relu, 0)         # tailored path: k_conv3x3_sp2p on the pairs, a one-board k_conv3x3_spg launch on an odd last board
+        g = _conv(bnd, boards, res, relu, 1 << 20)   # k_conv3x3_spg on the whole call
         su.assert_same_words(a.raw, g.raw, boards, C, S, f"boards={boards} res={res} relu={relu}", a.y, g.y)
     # res == y (include/azsp.h allows it): a wave loads the residual of its own elements before it stores them
     x, r, w, b, _ = _inputs(boards)

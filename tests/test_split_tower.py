@@ -517,7 +517,8 @@ def test_small_batch_knob_host_twin():
 @pytest.mark.parametrize("S,C", [(9, 128), (9, 64), (17, 64)])
 def test_gpu_wave_per_tile_conv_is_bit_identical_to_the_weight_stationary_kernels(S, C):
     """k_conv3x3_spg (one wave per 16-cout x 32-position tile, fragments straight from global memory) against the tailored kernel of the
-    same shape -- k_conv3x3_sp2 (two accumulation chains), k_conv3x3_sp<.., 8, 1>, k_conv3x3_sp17 -- on the same inputs: the raw hi / lo
+    same shape -- k_conv3x3_sp2p (two accumulation chains; board pairs, so an odd last board is itself a wave-per-tile launch on offset
+    pointers, compared here with the whole call's), k_conv3x3_sp<.., 8, 1>, k_conv3x3_sp17 -- on the same inputs: the raw hi / lo
     f16 words of the output are equal, with and without residual and ReLU.  The evaluator's result for a position therefore does not
     depend on whether it arrives in a batch of 1 (drop-in uct_search) or of 32 768 (the self-play actor)."""
     from alpha_zero_amd import _lib

@@ -33,7 +33,7 @@ def parse(txt):
 
 
 def short_name(n):
-    """`k_conv3x3_sp2`, `k_resblock_sp<Sb17>` ... from a mangled or demangled kernel name: the label names what the pass MEASURED."""
+    """`k_conv3x3_sp2p`, `k_resblock_sp<Sb17>` ... from a mangled or demangled kernel name: the label names what the pass MEASURED."""
     m = re.match(r"_Z(\d+)", n)
     base = n[m.end():m.end() + int(m.group(1))] if m else re.split(r"[<(]", n.replace("void ", ""))[0].strip()
     g = re.search(r"Sb\d+", n)

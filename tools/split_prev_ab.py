@@ -1,6 +1,6 @@
 """Same-box, same-process A/B of the fp32-class tower kernels of two builds of the library: the one in the tree against another build
 (default tools/probes/libazsp_prev.so), timed alternately on the same post-ReLU-like activations, with a bitwise comparison of the outputs.
-Cases: the 9x9 x 128 convolution (k_conv3x3_sp2, plain and with a residual), the fused 17x17 x 64 and 9x9 x 64 blocks (k_resblock_sp<Sb17 | Sb9>).
+Cases: the 9x9 x 128 convolution (k_conv3x3_sp2p, plain and with a residual), the fused 17x17 x 64 and 9x9 x 64 blocks (k_resblock_sp<Sb17 | Sb9>).
 (+ the bf16 19x19 x 256 convolution, k_conv3x3_op19q).  PREV_AB_CASES=<substring> selects cases.
 usage: python tools/split_prev_ab.py [other_lib] [rounds]"""
 import ctypes
