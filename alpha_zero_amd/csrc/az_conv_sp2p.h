@@ -27,7 +27,8 @@
 //   zero: a bias of exactly -0.0 turns +0 in a first padding MFMA and passes unchanged through the C operand of a later first live MFMA here.
 // Tile map (sp2p_map_table, tools/gen_sp_map_pair.py): 10 column tiles per pair -- 0-2 local to board A, 3 = top edge, 4 = the same 8
 // positions of both boards, 5 = bottom edge, 6 = left edge, 7-9 local to board B; the corner (8, 0) of each board stays with the
-// board-batched corner phase (12 boards per batch).  A lane's lmap / omap entries carry the second image's LDS offset and the second board's
+// board-batched corner phase (12 boards per batch).  A local tile is two whole board rows (columns 1-8), tile 4 one row of both boards, so that
+// a tile's store fills whole write sectors (sp2p_sector_complete below).  A lane's lmap / omap entries carry the second image's LDS offset and the second board's
 // global offset: compile-time constants, the pair is adjacent boards.
 // Units (3, 2, 3, 2 column tiles; accumulator sets 0, 1, 0, 1): U0 = tiles 0-2 (image A only), U1 = tiles 3, 4,
 // U2 = tiles 5-7, U3 = tiles 8, 9 (image B only).  LDS buffer 0 always holds image A, buffer 1 image B: A is free behind U2, the next pair's
@@ -54,17 +55,17 @@ struct Sp2pMap {
     unsigned char cell[10 * 16];  // board * 81 + position
 };
 constexpr Sp2pMap sp2p_map_table = {{
-    // generated by tools/gen_sp_map_pair.py (seed 9, trial 1): board * 81 + position of (column tile, lane & 15)
-     10,  13,  20,  28,  11,  15,  17,  26,  32,  47,  49,  65,  37,  40,  48,  70,
-     12,  14,  22,  50,  21,  29,  33,  38,  51,  57,  62,  67,  56,  59,  60,  69,
-     19,  24,  30,  31,  23,  34,  43,  52,  58,  66,  68,  71,  35,  39,  41,  42,
+    // generated by tools/gen_sp_map_pair.py (seed 9, trial 28; 126 sector-complete stores): board * 81 + position of (column tile, lane & 15)
+     46,  48,  50,  52,  47,  49,  51,  64,  65,  67,  69,  71,  53,  66,  68,  70,
+     10,  12,  14,  16,  11,  13,  15,  28,  29,  31,  33,  35,  17,  30,  32,  34,
+     20,  22,  24,  37,  19,  21,  23,  25,  26,  39,  41,  43,  38,  40,  42,  44,
       1,   2,   3,   4,  82,  83,  84,  85,  86,  87,  88,  89,   5,   6,   7,   8,
-     16,  25,  44,  46,  97, 106, 125, 127, 134, 136, 142, 145,  53,  55,  61,  64,
+     55,  56,  57,  58, 136, 137, 138, 139, 140, 141, 142, 143,  59,  60,  61,  62,
      73,  74,  75,  76, 154, 155, 156, 157, 158, 159, 160, 161,  77,  78,  79,  80,
       0,   9,  18,  27,  81,  90,  99, 108, 117, 126, 135, 144,  36,  45,  54,  63,
-     91,  94, 101, 109,  92,  96,  98, 107, 113, 128, 130, 146, 118, 121, 129, 151,
-     93,  95, 103, 131, 102, 110, 114, 119, 132, 138, 143, 148, 137, 140, 141, 150,
-    100, 105, 111, 112, 104, 115, 124, 133, 139, 147, 149, 152, 116, 120, 122, 123,
+    127, 129, 131, 133, 128, 130, 132, 145, 146, 148, 150, 152, 134, 147, 149, 151,
+     91,  93,  95,  97,  92,  94,  96, 109, 110, 112, 114, 116,  98, 111, 113, 115,
+    101, 103, 105, 118, 100, 102, 104, 106, 107, 120, 122, 124, 119, 121, 123, 125,
 }};
 constexpr int SP2P_NCT = 10, SP2P_KS = 18;
 // tap (dy, dx) = (tap / 3 - 1, tap % 3 - 1) of position pos lies on the zero padding
@@ -116,9 +117,24 @@ constexpr bool sp2p_skips_as_designed(const Sp2pMap& m) {
         }
     return true;
 }
+// 32-byte sectors of the output that ONE tile's store fills whole: neighbouring positions (p, p + 1) of a board inside a tile (a lane pair stores
+// the 16 B of a position and chunk; a chunk plane is 81 x 16 B, so the pair is one sector in the chunks of one parity).  The table keeps whole
+// board rows together (rows 1-7, columns 1-8: 7 pairs each, as in the two horizontal edge tiles): a line that leaves the L2 between the stores
+// of two tiles is then written back in whole sectors and granules instead of twice in halves (tools/gen_sp_map_pair.py)
+constexpr int sp2p_sector_complete(const Sp2pMap& m) {
+    int n = 0;
+    for (int t = 0; t < SP2P_NCT; ++t)
+        for (int a = 0; a < 16; ++a)
+            for (int b = 0; b < 16; ++b) {
+                const int p = m.cell[t * 16 + a], q = m.cell[t * 16 + b];
+                n += (q == p + 1 && p / SpGeo9::P2 == q / SpGeo9::P2) ? 1 : 0;
+            }
+    return n;
+}
 static_assert(sp2p_map_complete(sp2p_map_table), "pair map: every position of both boards but the two corners exactly once");
 static_assert(sp2p_map_conflict_free(sp2p_map_table), "pair map: conflict-free lane groups in every tile");
 static_assert(sp2p_skips_as_designed(sp2p_map_table) && sp2p_skips(sp2p_map_table) == 9, "pair map: the three edge tiles skip 3 taps each, 9 of 90 (tile, tap) pairs");
+static_assert(sp2p_sector_complete(sp2p_map_table) == 126, "pair map: 9 rows of both boards in one tile each, 7 whole sectors per row");
 static __device__ const Sp2pMap sp2p_map = sp2p_map_table;
 
 // ---- the units of a pair and their live MFMA slots -------------------------------------------------------------------------------
@@ -259,7 +275,9 @@ k_conv3x3_sp2p(const unsigned char* __restrict__ x, const _Float16* __restrict__
         const unsigned long long base = (unsigned long long)(src + (size_t)c * GBLK);
         const unsigned long long mask = live ? dmask[pc] : 0ull;
         const unsigned dst = dstbuf + (unsigned)(c * LBLK + pc * 1024);
-        asm volatile("s_mov_b64 exec, %0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b64 exec, -1"
+        // nt: the image is read by this workgroup and by the one of the other cout group on the same XCD at about the same time, then never again;
+        // as streaming lines it stops pushing the half-written output lines out of the L2 (fewer bytes written, the same bytes fetched: DESIGN 3.1)
+        asm volatile("s_mov_b64 exec, %0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3 nt\n\ts_mov_b64 exec, -1"
                      :
                      : "s"(mask), "s"(dst), "v"(dsrc[pc]), "s"(base)
                      : "memory");

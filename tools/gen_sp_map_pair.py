@@ -8,8 +8,19 @@ local to board A, tiles 7-9 (the same positions) to board B.
 Bank rule of tools/gen_sp_map.py: lanes n in A = {0-3, 12-15} hit bank class cell(n) mod 16, lanes n in B = {4-11} class cell(n) + 8 mod 16,
 and a tile is conflict-free iff the 16 classes are all different.  The second board's image lies a multiple of 256 B behind the first, so
 a spanning tile with board A's 8 positions in the A lanes and the same 8 positions of board B in the B lanes is conflict-free iff the 8
-cells differ mod 8.  The local tiles come from a seeded random search: per class mod 8 two cells per tile, an even number of
-(c, c + 8) couples per tile.  Prints the table as a C initializer; the header static_asserts the properties again."""
+cells differ mod 8.
+
+Which of the remaining 56 positions (rows 1-7, columns 1-8) go where is free inside those rules, and decides how a tile's output stores
+meet the memory system.  A lane pair stores the 16 bytes of one position and channel chunk; a chunk plane is 81 x 16 B, so a board row's
+columns 1-8 are 128 contiguous bytes, at every 16-byte alignment over the 16 chunks.  The L2 writes 64-byte granules (4 positions) back,
+32-byte sectors (2 positions) at the least: a granule whose positions sit in ONE tile is filled by one store instruction; one whose
+positions sit in several tiles is filled piecemeal, units apart, and leaves the L2 once per piece if the line is evicted in between.  So
+the table keeps WHOLE ROWS together: a row's 8 cells differ mod 8, hence a row is a valid mixed tile, and two rows form a conflict-free local
+tile iff their first cells differ by an even number mod 16 (per class mod 8 the two cells are either equal mod 16 -- one in the A lanes,
+one in the B lanes -- or a (c, c + 8) couple that shares a lane group, and the couples must split evenly).  Rows 1, 3, 5, 7 pair among
+themselves, as do rows 2, 4, 6, one of which is the mixed tile: 9 choices x the order of the tiles, taken by a seeded shuffle.  Prints
+the table as a C initializer with the number of sector-complete stores -- neighbouring positions (p, p + 1) of a board inside one tile: each
+is one 32-byte sector stored whole in the chunks of one parity --; the header static_asserts the rules and the count again."""
 import random
 
 P, C0, S, CORNER = 11, 12, 9, 72
@@ -27,33 +38,33 @@ BOTTOM = [8 * S + x for x in range(1, 9)]
 LEFT = [y * S for y in range(8)]
 for edge in (TOP, BOTTOM, LEFT):
     assert sorted(cell(p) % 8 for p in edge) == list(range(8)), edge
-rest = [p for p in range(S * S) if p != CORNER and p not in TOP + BOTTOM + LEFT]
-assert len(rest) == 56
-by8 = {c: sorted(p for p in rest if cell(p) % 8 == c) for c in range(8)}
-assert all(len(v) == 7 for v in by8.values()), "7 cells per class mod 8"
+ROWS = {y: [y * S + x for x in range(1, 9)] for y in range(1, 8)}
+assert all(sorted(cell(p) % 8 for p in r) == list(range(8)) for r in ROWS.values())
+
+
+def local_tile(ya, yb):
+    """(A lanes' positions, B lanes' positions) of the tile made of rows ya and yb, or None if the couples do not split evenly"""
+    a, b, couples = [], [], []
+    for c in range(8):
+        p, = [v for v in ROWS[ya] if cell(v) % 8 == c]
+        q, = [v for v in ROWS[yb] if cell(v) % 8 == c]
+        if cell(p) % 16 == cell(q) % 16:
+            a.append(p), b.append(q)
+        else:
+            couples.append((p, q))
+    if len(couples) % 2:
+        return None
+    for i, (p, q) in enumerate(couples):  # half of the couples in the A lanes, half in the B lanes
+        (a if i % 2 == 0 else b).extend((p, q))
+    return sorted(a), sorted(b)
 
 
 def search(rng):
-    """(mixed tile's 8 positions, three local tiles as (A lanes' positions, B lanes' positions)) or None."""
-    mixed, tiles = [], [([], [], []) for _ in range(3)]  # per tile: A picks, B picks, (c, c + 8) couples
-    for c in range(8):
-        pool = by8[c][:]
-        rng.shuffle(pool)
-        mixed.append(pool.pop())
-        for t in range(3):
-            p, q = pool.pop(), pool.pop()
-            if cell(p) % 16 == cell(q) % 16:
-                tiles[t][0].append(p), tiles[t][1].append(q)
-            else:
-                tiles[t][2].append((p, q))
-    out = []
-    for a, b, couples in tiles:
-        if len(couples) % 2:
-            return None
-        for i, (p, q) in enumerate(couples):  # half of the couples in the A lanes, half in the B lanes
-            (a if i % 2 == 0 else b).extend((p, q))
-        out.append((sorted(a), sorted(b)))
-    return sorted(mixed), out
+    """(mixed tile's row, three local tiles) for one shuffle of the rows: first row alone, then pairs in order; None if a pair is not a tile"""
+    order = list(ROWS)
+    rng.shuffle(order)
+    tiles = [local_tile(order[1 + 2 * t], order[2 + 2 * t]) for t in range(3)]
+    return None if None in tiles else (ROWS[order[0]], tiles)
 
 
 rng = random.Random(SEED)
@@ -88,6 +99,7 @@ for row in rows:
     assert banks == list(range(16)), (row, banks)
 flat = sorted(v for row in rows for v in row)
 assert flat == sorted(b * 81 + p for b in range(2) for p in range(81) if p != CORNER)
-print(f"    // generated by tools/gen_sp_map_pair.py (seed {SEED}, trial {trial}): board * 81 + position of (column tile, lane & 15)")
+sector_complete = sum(1 for row in rows for v in row if v + 1 in row and v // 81 == (v + 1) // 81)
+print(f"    // generated by tools/gen_sp_map_pair.py (seed {SEED}, trial {trial}; {sector_complete} sector-complete stores): board * 81 + position of (column tile, lane & 15)")
 for row in rows:
     print("    " + ", ".join(f"{v:3d}" for v in row) + ",")

@@ -4,7 +4,16 @@ script patches copies under a build directory and compiles them to tools/probes/
 times through AZ_BENCH_LIB.  Variants: FULL (unpatched), HALF_FRAG (B fragments of every second k-step are not read from LDS: the ring
 slot keeps its old contents), NO_FRAG (no fragment reads after the first k-steps), NO_DMA (the next tile's LDS-DMA pieces are not
 issued), VMCNT0 (NOT an ablation: every counted s_waitcnt vmcnt(N) before a tile barrier replaced by vmcnt(0) -- tools/vmcnt_check.py compares
-its outputs bit for bit with the product's), NO_CORNER (9x9: no corner phase), NO_STORE (no output stores and no residual loads; the compiler then drops the whole epilogue arithmetic as dead code)."""
+its outputs bit for bit with the product's), NO_CORNER (9x9: no corner phase), NO_STORE (no output stores and no residual loads; the compiler then drops the whole epilogue arithmetic as dead code).
+
+The pair kernel (az_conv_sp2p.h, k_conv3x3_sp2p) has variants of its own, named SP2P_<X>; they patch a copy of az_conv_sp2p.h only:
+SP2P_NO_STORE (no output stores, unit and corner phase; the epilogue arithmetic stays alive through the range report, so the residual loads stay
+too), SP2P_NO_RES (the residual loads of the units and of the corner phase read zeros instead of memory; stores kept), SP2P_NO_DMA (every
+LDS-DMA piece is issued with an empty exec mask: no image is fetched), SP2P_VMCNT0 (NOT an ablation: the counted wait in front of an end
+barrier becomes vmcnt(0); outputs must stay bit-identical), and the cache-policy variants, which keep every output bit: SP2P_NT_RES (the
+residual loads carry nt), SP2P_NT_STORE (the output stores carry nt), SP2P_NT_ALL (both), SP2P_PLAIN_DMA (the global_load_lds_dwordx4 of
+dma_piece WITHOUT the nt the product gives it; profiles/sp2p_ablation.txt measured the three nt items on the header that had none).
+tools/split_bench.py times several builds in one process (AZ_BENCH_LIBS), tools/split_pmc.py launches them for a counter pass."""
 import os
 import shutil
 import subprocess
@@ -56,12 +65,68 @@ def patch(text, variant, name):
     return text
 
 
+def patch_sp2p(text, variant):
+    """one variant of the pair kernel: a patched copy of az_conv_sp2p.h"""
+    def rep(old, new, n):
+        nonlocal text
+        assert text.count(old) == n, (variant, old[:70], text.count(old))
+        text = text.replace(old, new)
+
+    ST_HI = "if (store_ok) *(cv_u32x2*)(out + gq) = (cv_u32x2){hpk[0], hpk[1]};"
+    ST_LO = "} else if (store_ok) *(__attribute__((address_space(1))) cv_u32x2*)(out_lo + gq) = (cv_u32x2){lpk[0], lpk[1]};"
+    CST_HI = "*(cv_u32x2*)(y + co) = (cv_u32x2){sp_pack(h[0], h[1]), sp_pack(h[2], h[3])};"
+    CST_LO = "*(cv_u32x2*)(y + co + YPLANE) = (cv_u32x2){sp_pack(l[0], l[1]), sp_pack(l[2], l[3])};"
+    LD_HI = "rr[set][rj][rp] = *(const cv_u32x2*)(rbase + out_off(j0 + rj));"
+    LD_LO = "rr[set][rj][rp] = *(const __attribute__((address_space(1))) cv_u32x2*)(rbase_lo + out_off(j0 + rj));"
+    CLD_HI = "rr[0][0][0] = *(const cv_u32x2*)(res + co);"
+    CLD_LO = "rr[0][0][1] = *(const cv_u32x2*)(res + co + YPLANE);"
+    DMA = "global_load_lds_dwordx4 %2, %3 nt\\n"
+    if variant in ("SP2P_NO_STORE",):
+        rep(ST_HI, "if (false) {}", 1)
+        rep(ST_LO, "} else if (false) {}", 1)
+        rep(CST_HI, "", 1)
+        rep(CST_LO, "", 1)
+    if variant in ("SP2P_NO_RES",):
+        for old in (LD_HI, LD_LO):
+            rep(old, "rr[set][rj][rp] = (cv_u32x2){0u, 0u};", 1)
+        rep(CLD_HI, "rr[0][0][0] = (cv_u32x2){0u, 0u};", 1)
+        rep(CLD_LO, "rr[0][0][1] = (cv_u32x2){0u, 0u};", 1)
+    if variant in ("SP2P_NO_DMA",):
+        rep("const unsigned long long mask = live ? dmask[pc] : 0ull;", "const unsigned long long mask = live && false ? dmask[pc] : 0ull;", 1)
+    if variant in ("SP2P_VMCNT0",):
+        rep('if (pstore) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(VM_YOUNGER) : "memory");', 'if (false) asm volatile("s_nop 0");', 1)
+        rep('else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // first pair', 'asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // first pair', 1)
+    if variant in ("SP2P_NT_RES", "SP2P_NT_ALL"):
+        rep(LD_HI, "rr[set][rj][rp] = __builtin_nontemporal_load((const cv_u32x2*)(rbase + out_off(j0 + rj)));", 1)
+        rep(LD_LO, "rr[set][rj][rp] = __builtin_nontemporal_load((const __attribute__((address_space(1))) cv_u32x2*)(rbase_lo + out_off(j0 + rj)));", 1)
+        rep(CLD_HI, "rr[0][0][0] = __builtin_nontemporal_load((const cv_u32x2*)(res + co));", 1)
+        rep(CLD_LO, "rr[0][0][1] = __builtin_nontemporal_load((const cv_u32x2*)(res + co + YPLANE));", 1)
+    if variant in ("SP2P_PLAIN_DMA",):
+        rep(DMA, "global_load_lds_dwordx4 %2, %3\\n", 1)
+    if variant in ("SP2P_NT_STORE", "SP2P_NT_ALL"):
+        rep(ST_HI, "if (store_ok) __builtin_nontemporal_store((cv_u32x2){hpk[0], hpk[1]}, (cv_u32x2*)(out + gq));", 1)
+        rep(ST_LO, "} else if (store_ok) __builtin_nontemporal_store((cv_u32x2){lpk[0], lpk[1]}, (__attribute__((address_space(1))) cv_u32x2*)(out_lo + gq));", 1)
+        rep(CST_HI, "__builtin_nontemporal_store((cv_u32x2){sp_pack(h[0], h[1]), sp_pack(h[2], h[3])}, (cv_u32x2*)(y + co));", 1)
+        rep(CST_LO, "__builtin_nontemporal_store((cv_u32x2){sp_pack(l[0], l[1]), sp_pack(l[2], l[3])}, (cv_u32x2*)(y + co + YPLANE));", 1)
+    return text
+
+
+SP2P_VARIANTS = ("SP2P_NO_STORE", "SP2P_NO_RES", "SP2P_NO_DMA", "SP2P_VMCNT0", "SP2P_NT_RES", "SP2P_NT_STORE", "SP2P_NT_ALL", "SP2P_PLAIN_DMA")
+
+
 def build(variant):
     bd = os.path.join("/tmp", "sp_abl_" + variant)
     shutil.rmtree(bd, ignore_errors=True)
     shutil.copytree(os.path.join(ROOT, "alpha_zero_amd", "csrc"), os.path.join(bd, "alpha_zero_amd", "csrc"))
     shutil.copytree(os.path.join(ROOT, "include"), os.path.join(bd, "include"))
-    if variant != "FULL":
+    if variant.startswith("SP2P_"):
+        assert variant in SP2P_VARIANTS, variant
+        p = os.path.join(bd, "alpha_zero_amd", "csrc", "az_conv_sp2p.h")
+        src = open(p).read()
+        dst = patch_sp2p(src, variant)
+        assert dst != src, variant
+        open(p, "w").write(dst)
+    elif variant != "FULL":
         for name in ("az_conv_sp.h", "az_conv_sp17.h"):
             p = os.path.join(bd, "alpha_zero_amd", "csrc", name)
             src = open(p).read()

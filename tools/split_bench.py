@@ -1,5 +1,8 @@
 """Times azsp_conv3x3_split (the fp32-class split-precision tower convolution) against the library's fp32 convolution + fused epilogue at
-the bench shape (9x9, 128 filters, 32768 rows).  Post-ReLU-like activations (half zeros), He-scaled weights."""
+the bench shape (9x9, 128 filters, 32768 rows).  Post-ReLU-like activations (half zeros), He-scaled weights.
+AZ_BENCH_LIBS=<a.so,b.so,...> (builds of tools/probes/make_sp_abl.py): the split convolution of the tree's library and of every listed
+build on the same data in ONE process, AZ_BENCH_ROUNDS (default 4) rounds of 20 launches per build in alternating order (round 0 warms the
+clocks up), with a bitwise comparison of each build's output against the tree's; nothing else is timed in that mode."""
 import ctypes
 import json
 import os
@@ -39,7 +42,7 @@ assert b.dll.azsp_split_layout(x.data_ptr(), xs.data_ptr(), B, S, C, 1, None, st
 assert b.dll.azsp_split_layout(res.data_ptr(), rs.data_ptr(), B, S, C, 1, None, st) == 0
 
 
-def split(r):
+def split(r, b=b, ys=ys):
     assert b.dll.azsp_conv3x3_split(xs.data_ptr(), wsp.data_ptr(), bias.data_ptr(), rs.data_ptr() if r is not None else None, ys.data_ptr(), B, S, C, 1, None, st) == 0
 
 
@@ -51,6 +54,45 @@ def lib(r):
 
 flops = 2.0 * B * S * S * C * C * 9
 out = {"rows": B, "shape": [S, C]}
+if os.environ.get("AZ_BENCH_LIBS"):
+    from alpha_zero_amd import _abi
+
+    libs = [("tree", b)] + [  # ("tree": the tree's library, or the build AZ_BENCH_LIB names)
+            (os.path.basename(p).replace("libazsp_abl_", "").replace(".so", ""), _abi.Binding(ctypes.CDLL(p), "A/B build"))
+                            for p in os.environ["AZ_BENCH_LIBS"].split(",") if p]
+    ROUNDS = int(os.environ.get("AZ_BENCH_ROUNDS", "4"))
+    yo = torch.zeros_like(ys)
+    table = {}
+    for r in (None, res):
+        case = "residual" if r is not None else "plain"
+        split(r)
+        torch.cuda.synchronize()
+        yref = ys.clone()
+        tot = {k: 0.0 for k, _ in libs}
+        for k, lb in libs:
+            yo.zero_()  # (a build without stores must not inherit the previous build's output)
+            for _ in range(3):
+                split(r, lb, yo)
+            torch.cuda.synchronize()
+            table.setdefault(k, {})[f"{case}_bit_identical"] = bool(torch.equal(yo, yref))
+        for rnd in range(ROUNDS):
+            for k, lb in (libs if rnd % 2 == 0 else libs[::-1]):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(20):
+                    split(r, lb, yo)
+                e1.record()
+                torch.cuda.synchronize()
+                tot[k] += e0.elapsed_time(e1) / 20 if rnd > 0 else 0.0
+        for k, _ in libs:
+            table[k][f"{case}_ms"] = round(tot[k] / (ROUNDS - 1), 4)
+    print(f"{'build':16s} {'plain ms':>9s} {'vs tree':>8s} {'bits':>5s} {'resid ms':>9s} {'vs tree':>8s} {'bits':>5s}")
+    for k, _ in libs:
+        t = table[k]
+        print(f"{k:16s} {t['plain_ms']:9.4f} {t['plain_ms'] / table['tree']['plain_ms']:8.4f} {str(t['plain_bit_identical']):>5s} "
+              f"{t['residual_ms']:9.4f} {t['residual_ms'] / table['tree']['residual_ms']:8.4f} {str(t['residual_bit_identical']):>5s}", flush=True)
+    print(json.dumps({"rows": B, "rounds": ROUNDS, "builds": table}))
+    sys.exit(0)
 for name, f in (("split", split), ("library_fp32", lib)):
     for r in (None, res):
         for _ in range(3):
