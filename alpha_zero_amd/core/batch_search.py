@@ -16,7 +16,45 @@ import numpy as np
 import torch
 
 from .. import _abi
+from ..envs.base import BoardGameEnv
 from .engine import Engine, EngineConfig
+
+
+def dropin_engine(game, board_size, num_games, num_simulations, num_parallel, c_puct_base, c_puct_init, root_noise, komi=7.5, max_steps=0,
+                  num_to_win=5, num_stack=8, binding=None, device=None):
+    """The engine of a drop-in search, `uct_search`'s with one game and a BatchSearch's with `capacity`: it stops after every move
+    (`stop_after_move`), hands out int8 observation planes and logs no moves.  Without a `binding` it runs the product library on the GPU."""
+    if binding is None:
+        from .. import _lib
+
+        binding, device = _lib.load(require_gpu=True), device or "cuda"
+    cfg = EngineConfig(game=game, board_size=board_size, num_games=num_games, num_parallel=num_parallel, num_simulations=num_simulations,
+                       c_puct_base=c_puct_base, c_puct_init=c_puct_init, root_noise=root_noise, komi=komi, max_steps=max_steps or 0,
+                       num_to_win=num_to_win, num_stack=num_stack, stop_after_move=True, feature_dtype=_abi.FEAT_I8, log_moves=False)
+    return Engine(binding, cfg, device=device)
+
+
+def env_settings(env):
+    """The keyword arguments of `dropin_engine` / `BatchSearch` that are read off an env: its game, rules and backend."""
+    return dict(game="go" if env.has_pass_move else "gomoku", board_size=env.board_size, komi=getattr(env, "komi", 7.5),
+                max_steps=getattr(env, "max_steps", 0) or 0, num_to_win=getattr(env, "num_to_win", 5), num_stack=getattr(env, "num_stack", 8),
+                binding=getattr(env, "_binding", None), device=getattr(env, "_device", None))
+
+
+def check_env(env):
+    if not isinstance(env, BoardGameEnv) and not (hasattr(env, "board_deltas") and hasattr(env, "legal_actions")):
+        raise ValueError(f"Expect `env` to be a valid BoardGameEnv instance, got {env}")
+
+
+def check_num_simulations(num_simulations):
+    if not 1 <= num_simulations:
+        raise ValueError(f"Expect `num_simulations` to a positive integer, got {num_simulations}")
+
+
+def check_planes(eval_func, planes, num_stack):
+    cin = getattr(eval_func, "in_channels", None)  # known for evaluators that wrap a network (core/evaluate.py DeviceEvaluator)
+    if cin is not None and cin != planes:
+        raise ValueError(f"the evaluator's network takes {cin} input planes, but the observations (num_stack = {num_stack}) have {planes}")
 
 
 def evaluator_device(eval_func):
@@ -60,8 +98,9 @@ def _key(game, n, komi, max_steps, num_to_win, num_stack):
 
 
 def env_position(env):
-    """(board int8[N, N], hist int8[K, N, N] newest first, pos row int32[PS_COUNT] with action LOAD) of an env, read the way the
-    drop-in search reads it (core/mcts_v2.py _load_position)."""
+    """(board int8[N, N], hist int8[K, N, N] newest first, pos row int32[PS_COUNT] with action LOAD) of an env: the one reader of an
+    env's position, for the single search (core/mcts_v2.py _load_position) and the batched one.  K = env.num_stack rows (a reference
+    env's deque); the engine pads them to its 8."""
     hist = np.stack([np.asarray(b, dtype=np.int8) for b in env.board_deltas])
     ko, caps = getattr(env, "ko", -1), getattr(env, "_caps", (0, 0))
     p = getattr(env, "position", None)  # a reference GoEnv keeps these on its Position
@@ -73,6 +112,80 @@ def env_position(env):
     row[[_abi.PS_ACTION, _abi.PS_TO_PLAY, _abi.PS_STEPS, _abi.PS_KO, _abi.PS_LAST_PASS, _abi.PS_CAPS_BLACK, _abi.PS_CAPS_WHITE]] = (
         _abi.PSA_LOAD, env.to_play, env.steps, ko, int(last_pass), caps[0], caps[1])
     return np.asarray(env.board, dtype=np.int8), hist, row
+
+
+def simulate_with_callback(eng, eval_func, slots, num_parallel=None):
+    """The simulation loop (mcts_v2.py:378-421 / :568-625) of the searches in `slots` with the caller's HOST callback.  One host round
+    trip per leaf batch: azsp_dropin_step uploads eval_func's outputs, runs expand / backup + the selection of the next leaves, and
+    returns status, valid flags and the leaves' observation planes from one packed read-back (rounds 1-5 paid eight stream
+    synchronisations per simulation here).
+
+    num_parallel says how the valid leaf rows reach `eval_func`.  None, the batched searches: always ONE eval_func(obs[rows], True) for
+    the rows of all slots.  A number, the single search of slot 0 (`uct_search` with 1, `parallel_uct_search` with its P): the
+    reference's calls, unbatched for a root evaluation and for every leaf of uct_search."""
+    pri = np.zeros((eng.rows, eng.A), dtype=np.float32)
+    val = np.zeros(eng.rows, dtype=np.float32)
+    st, _, valid, obs = eng.dropin_step(None, None)
+    for _ in range(1 << 20):
+        if all(st[s, _abi.STC_STATUS] == _abi.ST_MOVE_DONE for s in slots):  # (scalar reads: np.all over st[slots] cost uct_search 6 % of its moves/s with a free evaluator)
+            return
+        if valid.any():
+            if num_parallel is not None and (st[0, _abi.STC_ROOT_EVAL_PENDING] or num_parallel == 1):  # mcts_v2.py:365, :414, :555
+                p, v = eval_func(obs[0], False)
+                pri[0], val[0] = np.asarray(p, dtype=np.float32), v
+            else:
+                rows = np.flatnonzero(valid)
+                ps, vs = eval_func(obs[rows], True)  # mcts_v2.py:614 per game
+                for r, p, v in zip(rows, ps, vs):
+                    pri[r], val[r] = np.asarray(p, dtype=np.float32), v
+        st, _, valid, obs = eng.dropin_step(pri, val)
+    raise RuntimeError("the searches did not finish")
+
+
+def simulate_on_device(eng, evaluator, num_simulations, num_parallel, slots):
+    """The same loop for an evaluator that lives on the engine's device (anything with `device_eval(x) -> (priors, values)` on device
+    tensors, e.g. core/evaluate.py DeviceEvaluator): select writes the leaves' observation planes into `eng.features`, the evaluator reads
+    them there and its outputs go straight into `eng.priors` / `eng.values`, expand / backup reads those -- NO host round trip per
+    simulation.  The host only polls the status rows of `slots`: a search that still owes `left` simulations cannot finish in fewer than
+    left / (simulations one iteration can complete) iterations (1 for uct_search -- a terminal leaf makes select descend again in the
+    same launch, mcts_v2.py:378-411 --, at most 2P attempts for parallel_uct_search, :572), so that many iterations are queued without
+    looking (half of them: a search with terminal leaves needs fewer, and iterations queued after the search is done would be no-ops in
+    the engine -- nothing pending, status MOVE_DONE -- but each still costs a forward).  ~8 polls per 100-simulation move instead of 100
+    round trips.  With several slots the queue is sized by the slot that owes the most: a finished slot ignores rounds.  Every row is
+    evaluated, valid or not, like the batched actor does: the engine ignores outputs of rows it did not ask for.  Same searches as the
+    callback loop with the same evaluator (tests/dropin_checks.py)."""
+    per_iter = 1 if num_parallel == 1 else 2 * num_parallel
+    into = getattr(evaluator, "device_eval_into", None)
+    eng.round()  # nothing to back up yet: selects the first leaves (or asks for the roots' evaluations)
+    for _ in range(1 << 20):
+        st, _ = eng.status()
+        rows = st[slots]
+        pending = rows[:, _abi.STC_STATUS] != _abi.ST_MOVE_DONE
+        if not pending.any():
+            return
+        left = max(num_simulations - int(rows[pending, _abi.STC_ROOT_N].min()), 1)
+        for _ in range(max(1, (left // 2) // per_iter)):
+            if into is not None:
+                into(eng.features, eng.priors, eng.values)
+            else:
+                pri, val = evaluator.device_eval(eng.features)
+                eng.priors.copy_(pri.reshape(eng.priors.shape))
+                eng.values.copy_(val.reshape(eng.values.shape))
+            eng.round()
+    raise RuntimeError("the searches did not finish")
+
+
+def choose_move(env, search_pi, child_n, root_legal, warm_up, deterministic):
+    """The move of a finished search (mcts_v2.py:427-434 / :634-641): the most visited child, or `np.random.choice` draws from `search_pi` until
+    the move is legal and, in the warm-up phase, no pass."""
+    move = None
+    if deterministic:
+        move = np.argmax(child_n)
+    else:
+        while move is None or (warm_up and env.has_pass_move and move == env.pass_move) or root_legal[move] != 1:
+            move = np.random.choice(np.arange(search_pi.shape[0]), p=search_pi)
+    assert root_legal[move] == 1
+    return move
 
 
 class SearchResults:
@@ -95,27 +208,19 @@ class BatchSearch:
                  komi=7.5, max_steps=0, num_to_win=5, num_stack=8, binding=None, device=None):
         if capacity < 1:
             raise ValueError(f"capacity must be at least 1, got {capacity}")
-        if not 1 <= num_simulations:
-            raise ValueError(f"Expect `num_simulations` to a positive integer, got {num_simulations}")
-        if binding is None:
-            from .. import _lib
-
-            binding, device = _lib.load(require_gpu=True), device or "cuda"
+        check_num_simulations(num_simulations)
         self.game, self.capacity, self.num_simulations, self.num_parallel = game, int(capacity), int(num_simulations), int(num_parallel)
         self.key = _key(game, board_size, komi, max_steps, num_to_win, num_stack)
-        cfg = EngineConfig(game=game, board_size=board_size, num_games=self.capacity, num_parallel=num_parallel, num_simulations=num_simulations,
-                           c_puct_base=c_puct_base, c_puct_init=c_puct_init, root_noise=root_noise, komi=komi, max_steps=max_steps or 0,
-                           num_to_win=num_to_win, num_stack=num_stack, stop_after_move=True, feature_dtype=_abi.FEAT_I8, log_moves=False)
-        self.eng = Engine(binding, cfg, device=device)
+        self.eng = dropin_engine(game, board_size, self.capacity, num_simulations, num_parallel, c_puct_base, c_puct_init, root_noise, komi,
+                                 max_steps, num_to_win, num_stack, binding, device)
         self.slots = np.zeros(0, dtype=np.int64)  # the active slots (a position is loaded, or a sub-tree was kept), ascending
         self._status = np.full(self.capacity, _abi.ST_IDLE, dtype=np.int32)  # host mirror of the slots' status after load / search / commit
 
     @classmethod
     def for_env(cls, env, capacity, num_simulations, num_parallel=1, c_puct_base=19652.0, c_puct_init=1.25, root_noise=False):
         """A BatchSearch for positions of `env`'s game, board size, komi / max_steps / num_to_win and num_stack, on `env`'s backend."""
-        return cls("go" if env.has_pass_move else "gomoku", env.board_size, capacity, num_simulations, num_parallel, c_puct_base, c_puct_init, root_noise,
-                   komi=getattr(env, "komi", 7.5), max_steps=getattr(env, "max_steps", 0) or 0, num_to_win=getattr(env, "num_to_win", 5), num_stack=getattr(env, "num_stack", 8),
-                   binding=getattr(env, "_binding", None), device=getattr(env, "_device", None))
+        return cls(capacity=capacity, num_simulations=num_simulations, num_parallel=num_parallel, c_puct_base=c_puct_base, c_puct_init=c_puct_init,
+                   root_noise=root_noise, **env_settings(env))
 
     def close(self):
         if self.eng is not None:
@@ -174,21 +279,17 @@ class BatchSearch:
         self.slots = np.flatnonzero(self._status != _abi.ST_IDLE)
         return res[s]
 
-    def check_envs(self, envs):
-        for env in envs:
-            if not (hasattr(env, "board_deltas") and hasattr(env, "legal_actions")):
-                raise ValueError(f"Expect `env` to be a valid BoardGameEnv instance, got {env}")
-            if env_key(env) != self.key:
-                raise ValueError(f"all envs of a batch must share game, board size, komi / max_steps / num_to_win and num_stack with the "
-                                 f"engine: {env_key(env)} != {self.key}")
-
     def load_envs(self, envs, slots=None, keep=()):
         """`load` for env objects (alpha_zero_amd.envs or the reference's): board, board_deltas, to_play, steps, ko, captures and
         last-pass are read the way the drop-in search reads them; ONE set_states for all of them."""
         envs = list(envs)
         if len(envs) > self.capacity:
             raise ValueError(f"{len(envs)} positions do not fit the {self.capacity} slots of this BatchSearch")
-        self.check_envs(envs)
+        for env in envs:
+            check_env(env)
+            if env_key(env) != self.key:
+                raise ValueError(f"all envs of a batch must share game, board size, komi / max_steps / num_to_win and num_stack with the "
+                                 f"engine: {env_key(env)} != {self.key}")
         for env in envs:
             if env.is_game_over():
                 raise RuntimeError("Game is over.")
@@ -208,10 +309,7 @@ class BatchSearch:
         every iteration the valid leaf rows of ALL slots go to `eval_func(obs, True)` in ONE call and it returns (priors, values) for
         them -- a batched search needs a batch-capable eval_func.  The reference's unbatched call `eval_func(obs, False)` (P = 1 and
         root evaluations) is the one contract of uct_search this class does not keep."""
-        cin = getattr(eval_func, "in_channels", None)
-        if cin is not None and cin != self.eng.planes:
-            raise ValueError(f"the evaluator's network takes {cin} input planes, but the positions' observations (num_stack = "
-                             f"{self.eng.cfg.num_stack}) have {self.eng.planes}")
+        check_planes(eval_func, self.eng.planes, self.eng.cfg.num_stack)
         eng, G, sl = self.eng, self.capacity, self.slots
         if len(sl) == 0:
             return
@@ -225,51 +323,10 @@ class BatchSearch:
                 0, torch.from_numpy(sl).to(eng.device), nz)
         eng.begin_moves(full_noise, warm)
         if is_resident(eval_func, eng):
-            self._search_resident(eval_func)
+            simulate_on_device(eng, eval_func, self.num_simulations, self.num_parallel, sl)
         else:
-            self._search_callback(eval_func)
+            simulate_with_callback(eng, eval_func, sl)
         self._status[sl] = _abi.ST_MOVE_DONE
-
-    def _search_resident(self, evaluator):
-        """core/mcts_v2.py _simulate_on_device for G slots: all status rows are polled, and the iterations queued without looking are
-        sized by the slot that owes the most simulations -- over-queuing is harmless, a finished slot (MOVE_DONE, nothing pending)
-        ignores rounds, it only costs forwards."""
-        eng, sl = self.eng, self.slots
-        per_iter = 1 if self.num_parallel == 1 else 2 * self.num_parallel
-        into = getattr(evaluator, "device_eval_into", None)
-        eng.round()  # nothing to back up yet: selects the first leaves (or asks for the roots' evaluations)
-        for _ in range(1 << 20):
-            st, _ = eng.status()
-            rows = st[sl]
-            pending = rows[:, _abi.STC_STATUS] != _abi.ST_MOVE_DONE
-            if not pending.any():
-                return
-            left = max(self.num_simulations - int(rows[pending, _abi.STC_ROOT_N].min()), 1)
-            for _ in range(max(1, (left // 2) // per_iter)):
-                if into is not None:
-                    into(eng.features, eng.priors, eng.values)
-                else:
-                    pri, val = evaluator.device_eval(eng.features)
-                    eng.priors.copy_(pri.reshape(eng.priors.shape))
-                    eng.values.copy_(val.reshape(eng.values.shape))
-                eng.round()
-        raise RuntimeError("the searches did not finish")
-
-    def _search_callback(self, eval_func):
-        eng, sl = self.eng, self.slots
-        pri = np.zeros((eng.rows, eng.A), dtype=np.float32)
-        val = np.zeros(eng.rows, dtype=np.float32)
-        st, _, valid, obs = eng.dropin_step(None, None)
-        for _ in range(1 << 20):
-            if np.all(st[sl, _abi.STC_STATUS] == _abi.ST_MOVE_DONE):
-                return
-            rows = np.flatnonzero(valid)
-            if len(rows):
-                ps, vs = eval_func(obs[rows], True)  # the leaves of ALL slots in one call (mcts_v2.py:614 per game)
-                for r, p, v in zip(rows, ps, vs):
-                    pri[r], val[r] = np.asarray(p, dtype=np.float32), v
-            st, _, valid, obs = eng.dropin_step(pri, val)
-        raise RuntimeError("the searches did not finish")
 
     # -- results --------------------------------------------------------------------------------------
     def results(self):

@@ -132,7 +132,7 @@ class DeviceEvaluator:
     def device_eval_into(self, x, priors_out, values_out):
         """The evaluator between an engine's own tensors: x = its feature rows, outputs written in place into its priors / values (fp32).
         On a HIP device the forward is replayed from a hipGraph captured per (buffers, evaluator state): a batch-1 forward of the drop-in
-        searches is ~14 launches of a few microseconds each, i.e. launch-bound from Python (core/mcts_v2.py _simulate_on_device).  A change
+        searches is ~14 launches of a few microseconds each, i.e. launch-bound from Python (core/batch_search.py simulate_on_device).  A change
         of the evaluator's state (InferenceNet.capture_state: activation scale, fallback to the library, kernel switches) leaves the
         capture unused.  Every captured forward owns a scratch slot of the network: no other forward, of whatever batch size, can free
         the buffers it replays into, and the slot is released with the graph."""

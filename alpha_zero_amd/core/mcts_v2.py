@@ -16,8 +16,8 @@ import weakref
 import numpy as np
 
 from .. import _abi
-from ..envs.base import BoardGameEnv
-from .engine import Engine, EngineConfig
+from .batch_search import (BatchSearch, check_env, check_num_simulations, check_planes, choose_move, dropin_engine, env_key, env_position,
+                           env_settings, is_resident, simulate_on_device, simulate_with_callback)
 
 _POOL = {}  # config key -> idle _Searcher objects
 
@@ -47,18 +47,8 @@ def _release(searcher):
 class _Searcher:
     def __init__(self, key, env, sims, P, base, init, root_noise):
         self.key = key
-        binding, device = getattr(env, "_binding", None), getattr(env, "_device", None)
-        if binding is None:
-            from .. import _lib
-
-            binding, device = _lib.load(require_gpu=True), "cuda"
-        game = "go" if env.has_pass_move else "gomoku"
-        cfg = EngineConfig(game=game, board_size=env.board_size, num_games=1, num_parallel=P, num_simulations=sims, c_puct_base=base,
-                           c_puct_init=init, root_noise=root_noise, komi=getattr(env, "komi", 7.5),
-                           max_steps=getattr(env, "max_steps", 0) or 0, num_to_win=getattr(env, "num_to_win", 5),
-                           num_stack=getattr(env, "num_stack", 8), stop_after_move=True, feature_dtype=_abi.FEAT_I8, log_moves=False)
-        self.eng = Engine(binding, cfg, device=device)
-        self.P = P
+        self.eng = dropin_engine(num_games=1, num_simulations=sims, num_parallel=P, c_puct_base=base, c_puct_init=init, root_noise=root_noise,
+                                 **env_settings(env))
 
 
 def _get_searcher(env, sims, P, base, init, root_noise):
@@ -72,86 +62,18 @@ def _get_searcher(env, sims, P, base, init, root_noise):
 
 
 def _load_position(s, env):
-    # K = env.num_stack rows, newest first (a reference env's deque): Engine.set_state pads them to the engine's 8
-    hist = np.stack([np.asarray(b, dtype=np.int8) for b in env.board_deltas])
-    ko, caps = getattr(env, "ko", -1), getattr(env, "_caps", (0, 0))
-    pos = getattr(env, "position", None)  # a reference GoEnv keeps these on its Position
-    if pos is not None:
-        ko = -1 if pos.ko is None else pos.ko[0] * env.board_size + pos.ko[1]
-        caps = tuple(pos.caps)
-    last_pass = bool(env.has_pass_move and len(env.history) > 0 and env.history[-1].move == env.pass_move)
-    s.eng.set_state(0, np.asarray(env.board, dtype=np.int8), hist, env.to_play, env.steps, ko, last_pass, caps)
-
-
-def _simulate_with_callback(eng, eval_func, P, num_parallel, A):
-    """The simulation loop (mcts_v2.py:378-421 / :568-625) with the caller's HOST callback.  One host round trip per leaf batch:
-    azsp_dropin_step uploads eval_func's outputs, runs expand / backup + the selection of the next leaves, and returns status, valid
-    flags and the leaves' observation planes from one packed read-back (rounds 1-5 paid eight stream synchronisations per simulation here)."""
-    pri = np.zeros((eng.rows, A), dtype=np.float32)
-    val = np.zeros(eng.rows, dtype=np.float32)
-    st, q, valid, obs = eng.dropin_step(None, None, P)
-    for _ in range(1 << 20):
-        if st[0, _abi.STC_STATUS] == _abi.ST_MOVE_DONE:
-            return
-        if valid.any():
-            if st[0, _abi.STC_ROOT_EVAL_PENDING] or num_parallel == 1:  # root evaluation / uct_search leaves: unbatched call (mcts_v2.py:365, :414, :555)
-                p, v = eval_func(obs[0], False)
-                pri[0], val[0] = np.asarray(p, dtype=np.float32), v
-            else:
-                rows = np.flatnonzero(valid)
-                ps, vs = eval_func(obs[rows], True)  # mcts_v2.py:614
-                for r, p, v in zip(rows, ps, vs):
-                    pri[r], val[r] = np.asarray(p, dtype=np.float32), v
-        st, q, valid, obs = eng.dropin_step(pri, val, P)
-    raise RuntimeError("the search did not finish")
-
-
-def _simulate_on_device(eng, evaluator, num_simulations, num_parallel):
-    """The same loop for an evaluator that lives on the engine's device (anything with `device_eval(x) -> (priors, values)` on device
-    tensors, e.g. core/evaluate.py DeviceEvaluator): select writes the leaves' observation planes into `eng.features`, the evaluator reads
-    them there and its outputs go straight into `eng.priors` / `eng.values`, expand / backup reads those -- NO host round trip per
-    simulation.  The host only polls the status words: a search that still owes `left` simulations cannot finish in fewer than
-    left / (simulations one iteration can complete) iterations (1 for uct_search -- a terminal leaf makes select descend again in the
-    same launch, mcts_v2.py:378-411 --, at most 2P attempts for parallel_uct_search, :572), so that many iterations are queued without
-    looking (half of them: a search with terminal leaves needs fewer, and iterations queued after the search is done would be no-ops in the engine -- nothing pending, status
-    MOVE_DONE -- but each still costs a forward).  ~8 polls per 100-simulation move instead of 100 round trips.  Every row is evaluated,
-    valid or not, like the batched actor does: the engine ignores outputs of rows it did not ask for.  Same searches as the callback
-    loop with the same evaluator (tests/dropin_checks.py)."""
-    per_iter = 1 if num_parallel == 1 else 2 * num_parallel
-    into = getattr(evaluator, "device_eval_into", None)
-
-    def iterate(n):
-        for _ in range(n):
-            if into is not None:
-                into(eng.features, eng.priors, eng.values)
-            else:
-                pri, val = evaluator.device_eval(eng.features)
-                eng.priors.copy_(pri.reshape(eng.priors.shape))
-                eng.values.copy_(val.reshape(eng.values.shape))
-            eng.round()
-
-    eng.round()  # nothing to back up yet: selects the first leaf (or asks for the root's evaluation)
-    for _ in range(1 << 20):
-        st, _ = eng.status()
-        if st[0, _abi.STC_STATUS] == _abi.ST_MOVE_DONE:
-            return
-        left = max(num_simulations - int(st[0, _abi.STC_ROOT_N]), 1)
-        iterate(max(1, (left // 2) // per_iter))
-    raise RuntimeError("the search did not finish")
+    board, hist, row = env_position(env)
+    s.eng.set_state(0, board, hist, row[_abi.PS_TO_PLAY], row[_abi.PS_STEPS], row[_abi.PS_KO], row[_abi.PS_LAST_PASS],
+                    (row[_abi.PS_CAPS_BLACK], row[_abi.PS_CAPS_WHITE]))
 
 
 def _search(env, eval_func, root_node, c_puct_base, c_puct_init, num_simulations, num_parallel, root_noise, warm_up, deterministic):
-    if not isinstance(env, BoardGameEnv) and not (hasattr(env, "board_deltas") and hasattr(env, "legal_actions")):
-        raise ValueError(f"Expect `env` to be a valid BoardGameEnv instance, got {env}")
-    if not 1 <= num_simulations:
-        raise ValueError(f"Expect `num_simulations` to a positive integer, got {num_simulations}")
+    check_env(env)
+    check_num_simulations(num_simulations)
     if env.is_game_over():
         raise RuntimeError("Game is over.")
-    planes = 2 * getattr(env, "num_stack", 8) + 1
-    cin = getattr(eval_func, "in_channels", None)  # known for evaluators that wrap a network (core/evaluate.py DeviceEvaluator)
-    if cin is not None and cin != planes:
-        raise ValueError(f"the evaluator's network takes {cin} input planes, but the env's observations (num_stack = "
-                         f"{getattr(env, 'num_stack', 8)}) have {planes}")
+    num_stack = getattr(env, "num_stack", 8)
+    check_planes(eval_func, 2 * num_stack + 1, num_stack)
     if root_node is not None:
         if not isinstance(root_node, Node) or not root_node._alive:
             raise ValueError("`root_node` must be the handle returned by the previous search (or None)")
@@ -163,25 +85,20 @@ def _search(env, eval_func, root_node, c_puct_base, c_puct_init, num_simulations
     else:
         s = _get_searcher(env, num_simulations, num_parallel, c_puct_base, c_puct_init, root_noise)
         _load_position(s, env)
-    eng, A = s.eng, s.eng.A
+    eng = s.eng
     root_legal = env.legal_actions
     noise = None
     if root_noise:  # add_dirichlet_noise (mcts_v2.py:259-260): the engine applies the legal mask itself
         noise = np.random.dirichlet(np.ones_like(root_legal) * 0.03)
     eng.begin_move(noise, warm_up=1 if warm_up else 0)
-    if getattr(eval_func, "device_eval", None) is not None and not (eng.features_tiled or eng.features_split):
-        # a device-resident evaluator (core/evaluate.py DeviceEvaluator): the leaves never visit the host -- see _simulate_on_device
-        _simulate_on_device(eng, eval_func, num_simulations, num_parallel)
+    if is_resident(eval_func, eng):
+        # a device-resident evaluator (core/evaluate.py DeviceEvaluator): the leaves never visit the host -- see simulate_on_device
+        simulate_on_device(eng, eval_func, num_simulations, num_parallel, [0])
     else:
-        _simulate_with_callback(eng, eval_func, s.P, num_parallel, A)
+        simulate_with_callback(eng, eval_func, [0], num_parallel)
     pi64, child_n, _ = eng.get_search(0, 0)
     search_pi = pi64 if env.has_pass_move else pi64.astype(np.float32)  # float64 for Go, float32 for Gomoku
-    move = None
-    if deterministic:
-        move = np.argmax(child_n)
-    else:
-        while move is None or (warm_up and env.has_pass_move and move == env.pass_move) or root_legal[move] != 1:
-            move = np.random.choice(np.arange(search_pi.shape[0]), p=search_pi)
+    move = choose_move(env, search_pi, child_n, root_legal, warm_up, deterministic)
     eng.commit_move([int(move)])
     st, q = eng.status()
     next_root = None
@@ -190,7 +107,6 @@ def _search(env, eval_func, root_node, c_puct_base, c_puct_init, num_simulations
         next_root = Node(s, out["board"][0].copy(), int(out["scalars"][0][_abi.ENV_TO_PLAY]), int(out["scalars"][0][_abi.ENV_STEPS]))
     else:
         _release(s)
-    assert root_legal[move] == 1
     return (move, search_pi, float(q[0, _abi.STQ_ROOT_Q]), float(q[0, _abi.STQ_CHILD_Q]), next_root)
 
 
@@ -236,14 +152,10 @@ class BatchRoots:
 
 
 def _search_many(envs, eval_func, root_nodes, c_puct_base, c_puct_init, num_simulations, num_parallel, root_noise, warm_up, deterministic):
-    from .batch_search import BatchSearch, env_key
-
     envs = list(envs)
     for env in envs:
-        if not isinstance(env, BoardGameEnv) and not (hasattr(env, "board_deltas") and hasattr(env, "legal_actions")):
-            raise ValueError(f"Expect `env` to be a valid BoardGameEnv instance, got {env}")
-    if not 1 <= num_simulations:
-        raise ValueError(f"Expect `num_simulations` to a positive integer, got {num_simulations}")
+        check_env(env)
+    check_num_simulations(num_simulations)
     if not envs:
         raise ValueError("Expect at least one env")
     if len({id(e) for e in envs}) != len(envs):
@@ -253,11 +165,8 @@ def _search_many(envs, eval_func, root_nodes, c_puct_base, c_puct_init, num_simu
             raise RuntimeError("Game is over.")
     if len({env_key(e) for e in envs}) != 1:
         raise ValueError("all envs of a batch must share game, board size, komi / max_steps / num_to_win and num_stack")
-    planes = 2 * getattr(envs[0], "num_stack", 8) + 1
-    cin = getattr(eval_func, "in_channels", None)
-    if cin is not None and cin != planes:
-        raise ValueError(f"the evaluator's network takes {cin} input planes, but the envs' observations (num_stack = "
-                         f"{getattr(envs[0], 'num_stack', 8)}) have {planes}")
+    num_stack = getattr(envs[0], "num_stack", 8)
+    check_planes(eval_func, 2 * num_stack + 1, num_stack)
     params = (env_key(envs[0]), int(num_simulations), int(num_parallel), float(c_puct_base), float(c_puct_init), bool(root_noise),
               id(getattr(envs[0], "_binding", None)))
     n = len(envs)
@@ -309,17 +218,9 @@ def _search_many(envs, eval_func, root_nodes, c_puct_base, c_puct_init, num_simu
     bs.search(eval_func, noise, warm[order])
     pis, child_ns, root_qs = bs.results().cpu()
     moves, search_pis = [], []
-    for i, env in enumerate(envs):  # the np.random.choice draws of env 0 until its move is acceptable, then env 1, ... (the rule of _search)
-        search_pi, root_legal = pis[row_of[i]], legals[i]
-        move = None
-        if deterministic:
-            move = np.argmax(child_ns[row_of[i]])
-        else:
-            while move is None or (warm[i] and env.has_pass_move and move == env.pass_move) or root_legal[move] != 1:
-                move = np.random.choice(np.arange(search_pi.shape[0]), p=search_pi)
-        assert root_legal[move] == 1
-        moves.append(move)
-        search_pis.append(search_pi)
+    for i, env in enumerate(envs):  # the np.random.choice draws of env 0 until its move is acceptable, then env 1, ...
+        search_pis.append(pis[row_of[i]])
+        moves.append(choose_move(env, search_pis[i], child_ns[row_of[i]], legals[i], warm[i], deterministic))
     child_qs, reusable = bs.commit([int(moves[i]) for i in order])
     handle = BatchRoots(bs, params, envs, slot_of, [reusable[row_of[i]] for i in range(n)],
                         [child_ns[row_of[i]][moves[i]] > 0 for i in range(n)])  # a child node exists iff the move was ever selected

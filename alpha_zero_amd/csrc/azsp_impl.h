@@ -160,52 +160,70 @@ struct OpRngProbe {
 };
 // packed position uploaded by azsp_set_state: u64 stones[2][W], u64 hist[8][2][W], int scalars[8] (PK_*)
 enum { PK_TO_PLAY, PK_STEPS, PK_KO, PK_LAST_PASS, PK_CAPS_BLACK, PK_CAPS_WHITE };
+// Nothing of a search is pending in the slot of `e`'s wave, its tree is freed and its status is `status`.
+template <class E> AZ_HD void drop_search(E& e, int status) {
+    if (E::Wave::first()) {
+        e.gr.n_leaves = 0;
+        e.gr.root_eval_pending = 0;
+        e.gr.noise_pending = 0;
+        e.gr.noise_ready = 0;
+        e.gr.status = status;
+    }
+    E::Wave::sync();
+    e.free_all_nodes();
+}
+// Installs a caller's position as the root of the slot of `e`'s wave (azsp_set_state and the LOAD rows of azsp_set_states): the two
+// stone planes, the scalars (to_play 0 = black) and the 8 x 2 x W history words, which `hist_word(k, q, w)` yields -- it is called by the
+// whole wave (it may ballot).  The slot is left at ply 0 with no tree, nothing pending and status AZS_NEED_ROOT.
+template <class E, class H>
+AZ_HD void install_position(E& e, const typename E::B& sb, const typename E::B& sw, int to_play, int steps, int ko, int last_pass, int caps_b,
+                            int caps_w, H hist_word) {
+    typedef typename E::R R;
+    typedef typename E::O O;
+    typename E::S s;
+    R::st(s.stones[0], sb);
+    R::st(s.stones[1], sw);
+    s.to_play = (uint8_t)to_play;
+    s.steps = (int16_t)steps;
+    s.ko = (int16_t)ko;
+    s.flags = last_pass ? AZF_LASTPASS : 0;
+    s.caps[0] = (uint16_t)caps_b;
+    s.caps[1] = (uint16_t)caps_w;
+    s.winner = -1;
+    s.reward = 0;
+    s.area[0] = s.area[1] = 0;
+    const typename E::B own = to_play == 0 ? sb : sw, opp = to_play == 0 ? sw : sb;
+    const typename E::B legal = E::GAME_ID == AZ_GO ? R::go_legal(own, opp, s.ko) : O::inv(O::bor(sb, sw));
+    R::st(s.legal, legal);
+    for (int k = 0; k < 8; ++k)
+        for (int q = 0; q < 2; ++q)
+            for (int w = 0; w < E::W; ++w) {
+                const u64 word = hist_word(k, q, w);
+                if (E::Wave::first()) e.gr.hist[k][q][w] = word;
+            }
+    if (E::Wave::first()) {
+        e.gr.env = s;
+        e.gr.ply = 0;
+        e.gr.num_passes = 0;
+        e.gr.marked_player = -1;
+    }
+    drop_search(e, AZS_NEED_ROOT);
+}
 struct OpSetState {
     int slot;
     const u64* packed;
     template <class E> AZ_HD void operator()(E& e) const {
         if (e.g != slot) return;
-        typedef typename E::R R;
-        typedef typename E::O O;
         const int W = E::W;
-        const int* sc = (const int*)(packed + 2 * W + 16 * W);
-        typename E::S s;
-        for (int q = 0; q < 2; ++q)
-            for (int w = 0; w < W; ++w) s.stones[q][w] = packed[q * W + w];
-        s.to_play = (uint8_t)sc[PK_TO_PLAY];
-        s.steps = (int16_t)sc[PK_STEPS];
-        s.ko = (int16_t)sc[PK_KO];
-        s.flags = sc[PK_LAST_PASS] ? AZF_LASTPASS : 0;
-        s.caps[0] = (uint16_t)sc[PK_CAPS_BLACK];
-        s.caps[1] = (uint16_t)sc[PK_CAPS_WHITE];
-        s.winner = -1;
-        s.reward = 0;
-        s.area[0] = s.area[1] = 0;
-        const typename E::B sb = R::ld(s.stones[0]), sw = R::ld(s.stones[1]);
-        const typename E::B own = s.to_play == 0 ? sb : sw, opp = s.to_play == 0 ? sw : sb;
-        const typename E::B legal = E::GAME_ID == AZ_GO ? R::go_legal(own, opp, s.ko) : O::inv(O::bor(own, opp));
-        R::st(s.legal, legal);
-        if (E::Wave::first()) {
-            e.gr.env = s;
-            for (int k = 0; k < 8; ++k)
-                for (int q = 0; q < 2; ++q)
-                    for (int w = 0; w < W; ++w) e.gr.hist[k][q][w] = packed[2 * W + (k * 2 + q) * W + w];
-            e.gr.ply = 0;
-            e.gr.num_passes = 0;
-            e.gr.marked_player = -1;
-            e.gr.n_leaves = 0;
-            e.gr.root_eval_pending = 0;
-            e.gr.noise_pending = 0;
-            e.gr.noise_ready = 0;
-            e.gr.status = AZS_NEED_ROOT;
-        }
-        E::Wave::sync();
-        e.free_all_nodes();
+        const u64* pk = packed;
+        const int* sc = (const int*)(pk + 2 * W + 16 * W);
+        install_position(e, E::R::ld(pk), E::R::ld(pk + W), sc[PK_TO_PLAY], sc[PK_STEPS], sc[PK_KO], sc[PK_LAST_PASS], sc[PK_CAPS_BLACK],
+                         sc[PK_CAPS_WHITE], [&](int k, int q, int w) -> u64 { return pk[2 * W + (k * 2 + q) * W + w]; });
     }
 };
 // Batched position load (azsp_set_states): every slot's wave reads ITS row of the caller's device tensors -- no host packing, no copy
 // through d_packed, no synchronisation.  The bitboards are built by ballot: lane l of ballot k answers for point l + 64k, so the 64-bit
-// mask IS word k of the plane (the idiom of Rules::go_legal).  A LOAD slot ends in exactly the state OpSetState leaves it in.
+// mask IS word k of the plane (the idiom of Rules::go_legal).  A LOAD slot goes through install_position, like the slot of OpSetState.
 struct OpSetStates {
     const int8_t* boards;  // [G][NP] reference colour ids
     const int8_t* hist;    // [G][hist_boards][NP], newest first
@@ -219,20 +237,11 @@ struct OpSetStates {
         });
     }
     template <class E> AZ_HD void idle(E& e, int code) const {  // the tree is freed, nothing is pending, status AZS_IDLE
-        if (E::Wave::first()) {
-            e.gr.n_leaves = 0;
-            e.gr.root_eval_pending = 0;
-            e.gr.noise_pending = 0;
-            e.gr.noise_ready = 0;
-            e.gr.status = AZS_IDLE;
-            result[e.g] = code;
-        }
-        E::Wave::sync();
-        e.free_all_nodes();
+        if (E::Wave::first()) result[e.g] = code;
+        drop_search(e, AZS_IDLE);
     }
     template <class E> AZ_HD void operator()(E& e) const {
         typedef typename E::Wave Wv;
-        typedef typename E::R R;
         typedef typename E::O O;
         const int W = E::W, NP = E::NP;
         const bool go = E::GAME_ID == AZ_GO;
@@ -268,43 +277,11 @@ struct OpSetStates {
             idle(e, AZSP_SS_GAME_OVER);
             return;
         }
-        typename E::S s;
-        R::st(s.stones[0], sb);
-        R::st(s.stones[1], sw);
-        s.to_play = (uint8_t)(to_play == b_id ? 0 : 1);
-        s.steps = (int16_t)steps;
-        s.ko = (int16_t)ko;
-        s.flags = last_pass ? AZF_LASTPASS : 0;
-        s.caps[0] = (uint16_t)caps_b;
-        s.caps[1] = (uint16_t)caps_w;
-        s.winner = -1;
-        s.reward = 0;
-        s.area[0] = s.area[1] = 0;
-        const typename E::B own = s.to_play == 0 ? sb : sw, opp = s.to_play == 0 ? sw : sb;
-        const typename E::B legal = go ? R::go_legal(own, opp, s.ko) : O::inv(occ);
-        R::st(s.legal, legal);
-        for (int k = 0; k < 8; ++k) {
-            const int8_t* hb = hist + ((size_t)e.g * hist_boards + (k < hist_boards ? k : 0)) * NP;
-            for (int q = 0; q < 2; ++q)
-                for (int w = 0; w < W; ++w) {
-                    const u64 word = k < hist_boards ? plane_word<E>(hb, w, q == 0 ? b_id : w_id) : 0ull;
-                    if (Wv::first()) e.gr.hist[k][q][w] = word;
-                }
-        }
-        if (Wv::first()) {
-            e.gr.env = s;
-            e.gr.ply = 0;
-            e.gr.num_passes = 0;
-            e.gr.marked_player = -1;
-            e.gr.n_leaves = 0;
-            e.gr.root_eval_pending = 0;
-            e.gr.noise_pending = 0;
-            e.gr.noise_ready = 0;
-            e.gr.status = AZS_NEED_ROOT;
-            result[e.g] = AZSP_SS_OK;
-        }
-        Wv::sync();
-        e.free_all_nodes();
+        if (Wv::first()) result[e.g] = AZSP_SS_OK;
+        const int8_t* hs = hist + (size_t)e.g * hist_boards * NP;
+        install_position(e, sb, sw, to_play == b_id ? 0 : 1, steps, ko, last_pass, caps_b, caps_w, [&](int k, int q, int w) -> u64 {
+            return k < hist_boards ? plane_word<E>(hs + (size_t)k * NP, w, q == 0 ? b_id : w_id) : 0ull;
+        });
     }
 };
 // azsp_begin_moves: OpBeginMove with one warm flag per slot, the slot's wave copying its own noise row out of the caller's device tensor

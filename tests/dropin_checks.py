@@ -68,7 +68,7 @@ def check_dropin_search(kind, name, max_moves=12, device_route=False):
     """The reference's own actor loop shape (pipeline.py:289-346) driven by OUR uct_search / envs, with the global NumPy
     random state replayed from the golden file: moves, pi, Q must equal the reference's outputs.
     device_route: the evaluator is an object with `device_eval` (tensors on the engine's device in and out): the searches run the
-    device-resident loop (core/mcts_v2.py _simulate_on_device: no host round trip per simulation, status polled a few times per move,
+    device-resident loop (core/batch_search.py simulate_on_device: no host round trip per simulation, status polled a few times per move,
     every row evaluated whether asked for or not) and must reproduce the same reference searches."""
     from alpha_zero_amd.core.mcts_v2 import parallel_uct_search, uct_search
 
@@ -133,6 +133,51 @@ def check_search_errors(kind):
     env.step(25)
     with pytest.raises(RuntimeError, match="Game is over"):
         uct_search(env, ef, None, 19652.0, 1.25, 10)
+
+
+def check_eval_func_call_pattern(kind, n=5, sims=24, P=4):
+    """How the searches call a host `eval_func` (the synthetic evaluator answers `obs[0]` unbatched and `obs[0:1]` batched alike, so the
+    golden searches cannot tell the two apart).  uct_search: every call unbatched with one observation, as the reference calls it
+    (mcts_v2.py:365, :414).  parallel_uct_search: the evaluation of a fresh root is the one unbatched call (:555), every other call is
+    batched with 1..P leaf rows (:614).  The batched searches: always batched, with the leaf rows of all envs in one call."""
+    from alpha_zero_amd.core.mcts_v2 import parallel_uct_search, parallel_uct_search_many, uct_search, uct_search_many
+
+    one = (17, n, n)
+    calls, inner = [], make_eval_func(n * n + 1)
+
+    def ef(obs, batched=False):
+        calls.append((bool(batched), tuple(np.shape(obs))))
+        return inner(obs, batched)
+
+    def play(search, moves, **kw):
+        """`moves` searches of one game with the handle passed back; returns the calls of each search."""
+        env, root, per_search = make_env(kind, "go", n), None, []
+        for _ in range(moves):
+            del calls[:]
+            move, _, _, _, root = search(env, ef, root, 19652.0, 1.25, num_simulations=sims, deterministic=True, **kw)
+            assert root is not None
+            per_search.append(list(calls))
+            env.step(int(move))
+        return per_search
+
+    for cs in play(uct_search, 3):
+        print("uct_search", len(cs), sorted(set(cs)))
+        assert cs and all(c == (False, one) for c in cs), cs
+    per_search = play(parallel_uct_search, 3, num_parallel=P)
+    for k, cs in enumerate(per_search):
+        print("parallel_uct_search", k, len(cs), sorted(set(cs)))
+    assert per_search[0][0] == (False, one)  # the fresh root's evaluation
+    rest = per_search[0][1:] + per_search[1] + per_search[2]
+    assert rest and all(b and len(s) == 4 and 1 <= s[0] <= P and s[1:] == one for b, s in rest), rest
+    for search, kw, most in ((uct_search_many, {}, 3), (parallel_uct_search_many, dict(num_parallel=P), 3 * P)):
+        envs, roots = [make_env(kind, "go", n) for _ in range(3)], None
+        del calls[:]
+        for _ in range(2):
+            moves, _, _, _, roots = search(envs, ef, roots, 19652.0, 1.25, num_simulations=sims, deterministic=True, **kw)
+            for env, move in zip(envs, moves):
+                env.step(int(move))
+        print(search.__name__, len(calls), sorted(set(calls)))
+        assert calls and all(b and len(s) == 4 and 1 <= s[0] <= most and s[1:] == one for b, s in calls), calls
 
 
 def check_dihedral(kind):

@@ -23,6 +23,10 @@ def test_search_errors():
     dc.check_search_errors("host")
 
 
+def test_eval_func_call_pattern():
+    dc.check_eval_func_call_pattern("host")
+
+
 def test_dihedral():
     dc.check_dihedral("host")
 

@@ -106,12 +106,17 @@ def test_gpu_uct_search_dropin_matches_reference(name):
 
 @pytest.mark.parametrize("name", ["go9_p8_s200", "gomoku13_p1_s100", "go5_p1_s40_det"])
 def test_gpu_uct_search_dropin_with_a_device_resident_evaluator_matches_reference(name):
-    """The device-resident simulation loop (no host round trip per simulation; core/mcts_v2.py _simulate_on_device) on the reference's goldens."""
+    """The device-resident simulation loop (no host round trip per simulation; core/batch_search.py simulate_on_device) on the reference's goldens."""
     dc.check_dropin_search("gpu", name, max_moves=8, device_route=True)
 
 
 def test_gpu_search_errors():
     dc.check_search_errors("gpu")
+
+
+@pytest.mark.gpu
+def test_gpu_eval_func_call_pattern():
+    dc.check_eval_func_call_pattern("gpu")
 
 
 def test_gpu_dropin_step_equals_the_separate_entries():
