@@ -28,15 +28,25 @@
 // Tile map (sp2p_map_table, tools/gen_sp_map_pair.py): 10 column tiles per pair -- 0-2 local to board A, 3 = top edge, 4 = the same 8
 // positions of both boards, 5 = bottom edge, 6 = left edge, 7-9 local to board B; the corner (8, 0) of each board stays with the
 // board-batched corner phase (12 boards per batch).  A local tile is two whole board rows (columns 1-8), tile 4 one row of both boards, so that
-// a tile's store fills whole write sectors (sp2p_sector_complete below).  A lane's lmap / omap entries carry the second image's LDS offset and the second board's
-// global offset: compile-time constants, the pair is adjacent boards.
+// a tile's store fills whole write sectors (sp2p_sector_complete below).  The rows of a local tile are FOUR apart -- (1, 5), (2, 6), (3, 7), row 4
+// spans -- and tiles 1, 2 are tile 0 one and two board rows lower LANE FOR LANE (sp2p_row_shifts).  A lane's lmap / omap entries carry the second
+// image's LDS offset and the second board's global offset: compile-time constants, the pair is adjacent boards.
 // Units (3, 2, 3, 2 column tiles; accumulator sets 0, 1, 0, 1): U0 = tiles 0-2 (image A only), U1 = tiles 3, 4,
 // U2 = tiles 5-7, U3 = tiles 8, 9 (image B only).  LDS buffer 0 always holds image A, buffer 1 image B: A is free behind U2, the next pair's
 // A arrives as 16 LDS-DMA pieces in U3 and is complete at U3's end barrier; B is free behind U3, this pair's B arrives in U0 and is complete
 // at U0's end barrier.  Barriers per pair: 8 (per unit the hand-over barrier; the end barriers of U0 and
 // U3, which also free the hand-over buffer for the next unit; U2 and U3 open with the barrier that frees it behind a unit without one).
-// The MFMA slots of a unit are a compile-time list (Sp2pSched) of the live (k-step, column tile, cout tile, product) entries; the riders
-// (hand-over, finishing, residual loads, fragment requests, DMA pieces, barriers) are indexed over that list.
+// The MFMA slots of a unit are a compile-time list (Sp2pSched) of the live (step, column tile, weight k-step, cout tile, product) entries; the
+// riders (hand-over, finishing, residual loads, fragment requests, DMA pieces, barriers) are indexed over that list.
+// Shared fragments, the skewed order.  The fragment reads beside the MFMAs cost energy, and time follows energy here.  In U0 and U3
+// the tiles are row shifts of one another: the B fragment of tile j at tap row dy IS the fragment of the unit's first tile at tap row j + dy.
+// These units therefore walk (row set s, tap column, k-half) instead of (tap, k-half): at a step tile j multiplies its tap row s - j if that is
+// -1 .. 1 -- 1, 2, 3, 2, 1 live tiles per row set in U0 (30 steps), 1, 2, 2, 1 in U3 (24 steps) -- and ONE fragment pair (hi, lo), requested in the
+// first two MFMA gaps of the step before, feeds all of them.  252 fragment reads per wave and pair instead of 324; the MFMAs are the same 972,
+// and every accumulator meets its weight k-steps in ascending order as before (sp2p_chains_ascend): the same chains, the same words.  U1 and
+// U2 hold edge tiles and read a fragment per live tile in the plain order.
+// (Measured and left out: the corner phase's two residual loads issued a unit earlier, in U3 of a corner batch's last pair -- the residual
+// layer's launch became 0.4-0.7 % slower; tools/probes/make_sp_abl.py SP2P_EARLY_RES rebuilds it.)
 #pragma once
 #include "az_conv_sp.h"
 
@@ -55,17 +65,17 @@ struct Sp2pMap {
     unsigned char cell[10 * 16];  // board * 81 + position
 };
 constexpr Sp2pMap sp2p_map_table = {{
-    // generated by tools/gen_sp_map_pair.py (seed 9, trial 28; 126 sector-complete stores): board * 81 + position of (column tile, lane & 15)
-     46,  48,  50,  52,  47,  49,  51,  64,  65,  67,  69,  71,  53,  66,  68,  70,
-     10,  12,  14,  16,  11,  13,  15,  28,  29,  31,  33,  35,  17,  30,  32,  34,
-     20,  22,  24,  37,  19,  21,  23,  25,  26,  39,  41,  43,  38,  40,  42,  44,
+    // generated by tools/gen_sp_map_pair.py (seed 66; 126 sector-complete stores): board * 81 + position of (column tile, lane & 15)
+     16,  17,  48,  49,  10,  11,  12,  13,  14,  15,  46,  47,  50,  51,  52,  53,
+     25,  26,  57,  58,  19,  20,  21,  22,  23,  24,  55,  56,  59,  60,  61,  62,
+     34,  35,  66,  67,  28,  29,  30,  31,  32,  33,  64,  65,  68,  69,  70,  71,
       1,   2,   3,   4,  82,  83,  84,  85,  86,  87,  88,  89,   5,   6,   7,   8,
-     55,  56,  57,  58, 136, 137, 138, 139, 140, 141, 142, 143,  59,  60,  61,  62,
+    118, 119, 120, 121,  37,  38,  39,  40,  41,  42,  43,  44, 122, 123, 124, 125,
      73,  74,  75,  76, 154, 155, 156, 157, 158, 159, 160, 161,  77,  78,  79,  80,
       0,   9,  18,  27,  81,  90,  99, 108, 117, 126, 135, 144,  36,  45,  54,  63,
-    127, 129, 131, 133, 128, 130, 132, 145, 146, 148, 150, 152, 134, 147, 149, 151,
-     91,  93,  95,  97,  92,  94,  96, 109, 110, 112, 114, 116,  98, 111, 113, 115,
-    101, 103, 105, 118, 100, 102, 104, 106, 107, 120, 122, 124, 119, 121, 123, 125,
+     97,  98, 129, 130,  91,  92,  93,  94,  95,  96, 127, 128, 131, 132, 133, 134,
+    106, 107, 138, 139, 100, 101, 102, 103, 104, 105, 136, 137, 140, 141, 142, 143,
+    115, 116, 147, 148, 109, 110, 111, 112, 113, 114, 145, 146, 149, 150, 151, 152,
 }};
 constexpr int SP2P_NCT = 10, SP2P_KS = 18;
 // tap (dy, dx) = (tap / 3 - 1, tap % 3 - 1) of position pos lies on the zero padding
@@ -137,56 +147,112 @@ static_assert(sp2p_skips_as_designed(sp2p_map_table) && sp2p_skips(sp2p_map_tabl
 static_assert(sp2p_sector_complete(sp2p_map_table) == 126, "pair map: 9 rows of both boards in one tile each, 7 whole sectors per row");
 static __device__ const Sp2pMap sp2p_map = sp2p_map_table;
 
-// ---- the units of a pair and their live MFMA slots -------------------------------------------------------------------------------
+// ---- the units of a pair, their steps and their live MFMA slots ------------------------------------------------------------------
 constexpr int sp2p_j0(int u) { return u == 0 ? 0 : u == 1 ? 3 : u == 2 ? 5 : 8; }
 constexpr int sp2p_nj(int u) { return (u & 1) ? 2 : 3; }
-constexpr bool sp2p_has_end(int u) { return u == 0 || u == 3; }  // a barrier in front of the unit's last k-step (image complete)
+constexpr bool sp2p_has_end(int u) { return u == 0 || u == 3; }  // a barrier in front of the unit's last step (image complete)
+// The tiles of unit u are ROW SHIFTS of its first tile: tile j0 + j is tile j0 one board row lower per j, lane for lane, and none skips a tap.
+// The B fragment of tile j at tap row dy is then the LDS data of tile j0 at tap row j + dy: one read feeds every tile of the unit.
+constexpr bool sp2p_row_shifts(const Sp2pMap& m, int u) {
+    const int j0 = sp2p_j0(u), nj = sp2p_nj(u);
+    for (int j = 0; j < nj; ++j) {
+        for (int n = 0; n < 16; ++n)
+            if (m.cell[(j0 + j) * 16 + n] != m.cell[j0 * 16 + n] + j * SpGeo9::S) return false;
+        for (int tap = 0; tap < 9; ++tap)
+            if (sp2p_skip(m, j0 + j, tap)) return false;
+    }
+    return true;
+}
+static_assert(sp2p_row_shifts(sp2p_map_table, 0) && sp2p_row_shifts(sp2p_map_table, 3), "pair map: the local tiles of a board are row shifts of one another");
+static_assert(!sp2p_row_shifts(sp2p_map_table, 1) && !sp2p_row_shifts(sp2p_map_table, 2), "pair map: the units with edge tiles read a fragment per tile");
+// A unit is a list of STEPS; a step is one k-half of one fragment position and has 6 MFMAs per live tile.
+//   U1, U2 (a fragment per tile): step t = weight k-step t = (tap, k-half) of every tile that does not skip the tap; tile j reads its own fragment.
+//   U0, U3 (row shifts, the SKEWED order): step (s, dx, k-half), row set s = -1 .. nj outermost; tile j multiplies its tap (dy, dx) = (s - j, dx)
+//   where dy is in -1 .. 1, so 1, 2, 3, 2, 1 (1, 2, 2, 1) tiles are live per s, and all of them read the ONE fragment pair (hi, lo) of the step:
+//   tile j0 at tap row s.  Every accumulator still meets its weight k-steps 0 .. 17 in ascending order: its chain is the one of the plain order.
+constexpr int SP2P_MAXST = 6 * 5;
 struct Sp2pSched {
-    int n;                       // live MFMA slots of the unit
-    int kstart[SP2P_KS + 1];     // first slot of a k-step
-    int live_n[SP2P_KS];         // live column tiles of a k-step ...
-    unsigned char live[SP2P_KS][3];  // ... and which (index inside the unit)
-    unsigned char t[324], jl[324], tt[324], prod[324], first[324];  // per slot; first: the tile's first live k-step (accumulator initialisation)
+    int n, ns;                          // live MFMA slots, steps of the unit
+    bool shared;                        // one fragment pair per step (row shifts) / one per live tile
+    int kstart[SP2P_MAXST + 1];         // first slot of a step
+    int live_n[SP2P_MAXST];             // live column tiles of a step ...
+    unsigned char live[SP2P_MAXST][3];  // ... and which (index inside the unit)
+    // the fragment position of a step: tap row and column (from the (-1, -1) neighbour of tile j0 if shared, of the reading tile if not), k-half
+    unsigned char frow[SP2P_MAXST], fcol[SP2P_MAXST], fkh[SP2P_MAXST];
+    // per slot: step, tile, weight k-step, cout tile, product; first: the tile's first live step (accumulator initialisation)
+    unsigned char st[324], jl[324], wk[324], tt[324], prod[324], first[324];
+    constexpr int nfrag(int step) const { return shared ? 1 : live_n[step]; }  // fragment pairs the step reads
+    constexpr int reads() const {
+        int r = 0;
+        for (int i = 0; i < ns; ++i) r += 2 * nfrag(i);
+        return r;
+    }
 };
 constexpr Sp2pSched sp2p_sched(int u) {
     Sp2pSched s = {};
     const int j0 = sp2p_j0(u), nj = sp2p_nj(u);
-    int first_t[3] = {-1, -1, -1};
+    s.shared = sp2p_row_shifts(sp2p_map_table, u);
+    s.ns = s.shared ? 6 * (nj + 2) : SP2P_KS;
+    int first_st[3] = {-1, -1, -1};
     int n = 0;
-    for (int t = 0; t < SP2P_KS; ++t) {
-        int ln = 0;
-        for (int j = 0; j < nj; ++j)
-            if (!sp2p_skip(sp2p_map_table, j0 + j, t / 2)) {
-                s.live[t][ln++] = (unsigned char)j;
-                if (first_t[j] < 0) first_t[j] = t;
-            }
-        s.live_n[t] = ln;
-        s.kstart[t] = n;
+    for (int i = 0; i < s.ns; ++i) {
+        const int row = i / 6, col = (i / 2) % 3, kh = i % 2;  // shared: row = s + 1
+        int ln = 0, wk[3] = {};
+        for (int j = 0; j < nj; ++j) {
+            const int dy1 = s.shared ? row - j : row;  // tap row + 1 of tile j
+            if (dy1 < 0 || dy1 > 2 || sp2p_skip(sp2p_map_table, j0 + j, dy1 * 3 + col)) continue;
+            wk[ln] = (dy1 * 3 + col) * 2 + kh;
+            s.live[i][ln++] = (unsigned char)j;
+            if (first_st[j] < 0) first_st[j] = i;
+        }
+        s.live_n[i] = ln;
+        s.kstart[i] = n;
+        s.frow[i] = (unsigned char)row, s.fcol[i] = (unsigned char)col, s.fkh[i] = (unsigned char)kh;
         for (int r6 = 0; r6 < 6; ++r6)  // (cout tile, product) outer, column tile inner
             for (int k = 0; k < ln; ++k) {
-                const int j = s.live[t][k];
-                s.t[n] = (unsigned char)t, s.jl[n] = (unsigned char)j, s.tt[n] = (unsigned char)(r6 / 3), s.prod[n] = (unsigned char)(r6 % 3);
-                s.first[n] = first_t[j] == t ? 1 : 0;
+                const int j = s.live[i][k];
+                s.st[n] = (unsigned char)i, s.jl[n] = (unsigned char)j, s.wk[n] = (unsigned char)wk[k], s.tt[n] = (unsigned char)(r6 / 3), s.prod[n] = (unsigned char)(r6 % 3);
+                s.first[n] = first_st[j] == i ? 1 : 0;
                 ++n;
             }
     }
-    s.kstart[SP2P_KS] = n, s.n = n;
+    s.kstart[s.ns] = n, s.n = n;
     return s;
+}
+// every tile of the unit meets each of its live weight k-steps once, in ascending order
+constexpr bool sp2p_chains_ascend(const Sp2pSched& s, int u) {
+    for (int j = 0; j < sp2p_nj(u); ++j)
+        for (int r6 = 0; r6 < 6; ++r6) {
+            int next = 0;
+            for (int sl = 0; sl < s.n; ++sl) {
+                if (s.jl[sl] != j || s.tt[sl] * 3 + s.prod[sl] != r6) continue;
+                while (next < SP2P_KS && sp2p_skip(sp2p_map_table, sp2p_j0(u) + j, next / 2)) ++next;
+                if (s.wk[sl] != next++) return false;
+            }
+            while (next < SP2P_KS && sp2p_skip(sp2p_map_table, sp2p_j0(u) + j, next / 2)) ++next;
+            if (next != SP2P_KS) return false;
+        }
+    return true;
 }
 template <int U> struct Sp2pU {
     static constexpr Sp2pSched S = sp2p_sched(U);
+    static_assert(sp2p_chains_ascend(S, U), "an accumulator's chain: its live weight k-steps, each once, ascending");
+    static_assert(S.ns % 2 == 0, "the fragment ring (2 slots) is in the same phase at every unit's first step");
 };
 static_assert(Sp2pU<0>::S.n + Sp2pU<1>::S.n + Sp2pU<2>::S.n + Sp2pU<3>::S.n == 972, "MFMAs per wave and pair: 1080 less 9 x 12");
 static_assert(Sp2pU<1>::S.n == 180, "the top tile shares its unit with the never-skipped tile");
+static_assert(Sp2pU<0>::S.ns == 30 && Sp2pU<3>::S.ns == 24 && Sp2pU<0>::S.n == 324 && Sp2pU<3>::S.n == 216, "the skewed units: 1, 2, 3, 2, 1 and 1, 2, 2, 1 live tiles per row set");
+static_assert(Sp2pU<0>::S.reads() == 60 && Sp2pU<1>::S.reads() == 60 && Sp2pU<2>::S.reads() == 84 && Sp2pU<3>::S.reads() == 48,
+              "fragment reads per wave and pair: 252 (324 with a fragment per tile in every unit)");
 
 // Constants of unit U's riders (shared by the kernel and by sp2p_vm_younger)
 template <bool RES, int U> struct Sp2pK {
-    static constexpr int KS = SP2P_KS, S0 = 6, NPIECE = 16;
+    static constexpr int NS = Sp2pU<U>::S.ns, S0 = 6, NPIECE = 16;
     static constexpr int E1 = RES ? 4 : 2, PAIR = 2 * E1 + 8, CT_OPS = 2 * PAIR + 2, P2CT = CT_OPS + 1;
     static constexpr int PU = (U + 3) & 3, NU = (U + 1) & 3;
     static constexpr int nj = sp2p_nj(U), j0 = sp2p_j0(U), pnj = sp2p_nj(PU), pj0 = sp2p_j0(PU);
     static constexpr bool END = sp2p_has_end(U), PRE = !sp2p_has_end(PU);
-    static constexpr int N = Sp2pU<U>::S.n, KLAST = Sp2pU<U>::S.kstart[KS - 1];
+    static constexpr int N = Sp2pU<U>::S.n, KLAST = Sp2pU<U>::S.kstart[NS - 1];  // KLAST: first slot of the last step
     static constexpr int P1 = 5 * pnj, SBX = S0 + P1 + 1, P2 = pnj * P2CT;
     static constexpr int AVAIL = (END ? KLAST : N - 4) - (SBX + 1);
     typedef SpSpread<P2, SBX + 1, AVAIL> SP;
@@ -297,11 +363,15 @@ k_conv3x3_sp2p(const unsigned char* __restrict__ x, const _Float16* __restrict__
         return v;
     };
     sp_f16x8 bb[R][2][NJ0];
-    // fragment (plane pl, column tile j of the table) of k-step s into ring slot rs, unit-local tile index jl
-    auto load_frag = [&](int j, int jl, int s, int rs, int pl) __attribute__((always_inline)) {
-        const int tap = s / KSUB;
-        const int off = ((tap / 3) * G::PITCH + (tap % 3)) * 16 + (s % KSUB) * (4 * LBLK);
-        bb[rs][pl][jl] = *(const sp_f16x8*)(lds + lmap[j] + off + pl * LPLANE);
+    // request q of step lt of unit lu: plane q / nfrag of the step's fragment q % nfrag, into ring slot lt % R.  A skewed unit keeps its one
+    // fragment per step in the ring registers of its first tile and addresses it from that tile's lmap entry
+    auto frag_req = [&](auto LU, auto LT, auto QC) __attribute__((always_inline)) {
+        constexpr int lu = decltype(LU)::value, lt = decltype(LT)::value, q = decltype(QC)::value;
+        constexpr int nf = Sp2pU<lu>::S.nfrag(lt), pl = q / nf;
+        constexpr int jr = Sp2pU<lu>::S.shared ? 0 : Sp2pU<lu>::S.live[lt][q % nf];
+        constexpr int off = (Sp2pU<lu>::S.frow[lt] * G::PITCH + Sp2pU<lu>::S.fcol[lt]) * 16 + Sp2pU<lu>::S.fkh[lt] * (4 * LBLK);
+        static_assert(pl < 2, "two planes per fragment");
+        bb[lt % R][pl][jr] = *(const sp_f16x8*)(lds + lmap[sp2p_j0(lu) + jr] + off + pl * LPLANE);
     };
     {
         const unsigned char* src = x + (size_t)slot * (2 * XTILE);  // image A of the first pair; its image B rides in U0
@@ -309,11 +379,9 @@ k_conv3x3_sp2p(const unsigned char* __restrict__ x, const _Float16* __restrict__
         for (int i = 0; i < NPIECE; ++i) dma_piece(src, lds0, true, i);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         CV_BARRIER();
-        static_assert(Sp2pU<0>::S.live_n[0] == NJ0, "the first k-step of a pair has all of U0's tiles");
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl)
-#pragma unroll
-            for (int j = 0; j < NJ0; ++j) load_frag(j, j, 0, 0, pl);
+        static_assert(Sp2pU<0>::S.nfrag(0) == 1, "the first step of a pair reads one fragment");
+        frag_req(CpInt<0>{}, CpInt<0>{}, CpInt<0>{});
+        frag_req(CpInt<0>{}, CpInt<0>{}, CpInt<1>{});
     }
 #pragma unroll
     for (int f = 0; f < NF; ++f) {
@@ -406,13 +474,14 @@ k_conv3x3_sp2p(const unsigned char* __restrict__ x, const _Float16* __restrict__
             constexpr int u = decltype(UC)::value, set = u & 1, pset = set ^ 1;
             typedef Sp2pK<RES, u> K;
             typedef typename K::SP SP;
-            constexpr int nj = K::nj, j0 = K::j0, pj0 = K::pj0, nj0 = sp2p_j0(K::NU);
+            constexpr int nj = K::nj, j0 = K::j0, pj0 = K::pj0;
             unsigned char* pout = u == 0 ? yprev : ybase;
             const sp_gptr pout_lo = u == 0 ? yprev_lo : ybase_lo;
             const bool pstore = u > 0 || have_prev;
             cp_for_each([&](auto SC) __attribute__((always_inline)) {
                 constexpr int sl = decltype(SC)::value;  // MFMA slot of the unit
-                constexpr int t = Sp2pU<u>::S.t[sl], jl = Sp2pU<u>::S.jl[sl], tt = Sp2pU<u>::S.tt[sl], prod = Sp2pU<u>::S.prod[sl];
+                constexpr int t = Sp2pU<u>::S.st[sl], jl = Sp2pU<u>::S.jl[sl], wk = Sp2pU<u>::S.wk[sl], tt = Sp2pU<u>::S.tt[sl], prod = Sp2pU<u>::S.prod[sl];
+                constexpr int jb = Sp2pU<u>::S.shared ? 0 : jl;  // the ring registers of the slot's fragment: of its tile, or the step's one fragment
                 constexpr int qi = sl - Sp2pU<u>::S.kstart[t];
                 constexpr bool first = Sp2pU<u>::S.first[sl] != 0;
                 if constexpr (K::END && sl == K::KLAST) {
@@ -427,30 +496,27 @@ k_conv3x3_sp2p(const unsigned char* __restrict__ x, const _Float16* __restrict__
                 }
                 if constexpr (K::PRE && sl == S0 - 1) CV_BARRIER();  // every wave has finished the previous unit: its reads of the hand-over (and of image A)
                 if constexpr (sl == K::SBX) CV_BARRIER();             // the hand-over writes of all waves are in LDS
-                constexpr int fa = (tt * 2 + (prod == 2 ? 1 : 0)) * KS + t, pl = prod == 1 ? 1 : 0;
+                constexpr int fa = (tt * 2 + (prod == 2 ? 1 : 0)) * KS + wk, pl = prod == 1 ? 1 : 0;
                 static_assert(!first || fa < NF_A, "an accumulator's first MFMA reads its weights from the AGPRs");
                 if constexpr (prod == 0) {
-                    if constexpr (first && tt == 0) sp_mfma_ac(accm[set][jl][tt], wf[fa], bb[t % R][pl][jl], bv);
-                    else if constexpr (first) sp_mfma_a0(accm[set][jl][tt], wf[fa], bb[t % R][pl][jl]);
-                    else if constexpr (fa < NF_A) sp_mfma_a(accm[set][jl][tt], wf[fa], bb[t % R][pl][jl]);
-                    else sp_mfma_v(accm[set][jl][tt], wf[fa], bb[t % R][pl][jl]);
+                    if constexpr (first && tt == 0) sp_mfma_ac(accm[set][jl][tt], wf[fa], bb[t % R][pl][jb], bv);
+                    else if constexpr (first) sp_mfma_a0(accm[set][jl][tt], wf[fa], bb[t % R][pl][jb]);
+                    else if constexpr (fa < NF_A) sp_mfma_a(accm[set][jl][tt], wf[fa], bb[t % R][pl][jb]);
+                    else sp_mfma_v(accm[set][jl][tt], wf[fa], bb[t % R][pl][jb]);
                 } else if constexpr (prod == 1) {
-                    if constexpr (first) sp_mfma_a0(accc[set][jl][tt], wf[fa], bb[t % R][pl][jl]);
-                    else if constexpr (fa < NF_A) sp_mfma_a(accc[set][jl][tt], wf[fa], bb[t % R][pl][jl]);
-                    else sp_mfma_v(accc[set][jl][tt], wf[fa], bb[t % R][pl][jl]);
+                    if constexpr (first) sp_mfma_a0(accc[set][jl][tt], wf[fa], bb[t % R][pl][jb]);
+                    else if constexpr (fa < NF_A) sp_mfma_a(accc[set][jl][tt], wf[fa], bb[t % R][pl][jb]);
+                    else sp_mfma_v(accc[set][jl][tt], wf[fa], bb[t % R][pl][jb]);
                 } else {
-                    if constexpr (fa < NF_A) sp_mfma_a(accc[set][jl][tt], wf[fa], bb[t % R][pl][jl]);
-                    else sp_mfma_v(accc[set][jl][tt], wf[fa], bb[t % R][pl][jl]);
+                    if constexpr (fa < NF_A) sp_mfma_a(accc[set][jl][tt], wf[fa], bb[t % R][pl][jb]);
+                    else sp_mfma_v(accc[set][jl][tt], wf[fa], bb[t % R][pl][jb]);
                 }
-                {   // the fragments of the next k-step (of this unit, or k-step 0 of the next unit), one request per MFMA gap
-                    constexpr bool lsame = t + 1 < KS;
-                    constexpr int lu = lsame ? u : K::NU, lt = lsame ? t + 1 : 0, lj0 = lsame ? j0 : nj0;
-                    constexpr int lnj = Sp2pU<lu>::S.live_n[lt];
-                    static_assert(2 * lnj <= 6 * Sp2pU<u>::S.live_n[t], "a fragment per MFMA gap");
-                    if constexpr (qi < 2 * lnj) {
-                        constexpr int ljl = Sp2pU<lu>::S.live[lt][qi % lnj];
-                        load_frag(lj0 + ljl, ljl, lt, (t + 1) % R, qi / lnj);
-                    }
+                {   // the fragments of the next step (of this unit, or step 0 of the next unit), one request per MFMA gap
+                    constexpr bool lsame = t + 1 < K::NS;
+                    constexpr int lu = lsame ? u : K::NU, lt = lsame ? t + 1 : 0;
+                    constexpr int nreq = 2 * Sp2pU<lu>::S.nfrag(lt);
+                    static_assert(nreq <= 6 * Sp2pU<u>::S.live_n[t], "a fragment per MFMA gap");
+                    if constexpr (qi < nreq) frag_req(CpInt<lu>{}, CpInt<lt>{}, CpInt<qi>{});
                 }
                 if constexpr (sl >= S0 && sl < S0 + K::P1) send_op(pset, (sl - S0) / 5, (sl - S0) % 5);
                 if constexpr (sl > K::SBX) {

@@ -7,18 +7,26 @@ local to board A, tiles 7-9 (the same positions) to board B.
 
 Bank rule of tools/gen_sp_map.py: lanes n in A = {0-3, 12-15} hit bank class cell(n) mod 16, lanes n in B = {4-11} class cell(n) + 8 mod 16,
 and a tile is conflict-free iff the 16 classes are all different.  The second board's image lies a multiple of 256 B behind the first, so
-a spanning tile with board A's 8 positions in the A lanes and the same 8 positions of board B in the B lanes is conflict-free iff the 8
-cells differ mod 8.
+a spanning tile with one board's 8 positions in the A lanes and the same 8 positions of the other board in the B lanes is conflict-free iff
+the 8 cells differ mod 8.
 
-Which of the remaining 56 positions (rows 1-7, columns 1-8) go where is free inside those rules, and decides how a tile's output stores
-meet the memory system.  A lane pair stores the 16 bytes of one position and channel chunk; a chunk plane is 81 x 16 B, so a board row's
-columns 1-8 are 128 contiguous bytes, at every 16-byte alignment over the 16 chunks.  The L2 writes 64-byte granules (4 positions) back,
-32-byte sectors (2 positions) at the least: a granule whose positions sit in ONE tile is filled by one store instruction; one whose
-positions sit in several tiles is filled piecemeal, units apart, and leaves the L2 once per piece if the line is evicted in between.  So
-the table keeps WHOLE ROWS together: a row's 8 cells differ mod 8, hence a row is a valid mixed tile, and two rows form a conflict-free local
-tile iff their first cells differ by an even number mod 16 (per class mod 8 the two cells are either equal mod 16 -- one in the A lanes,
-one in the B lanes -- or a (c, c + 8) couple that shares a lane group, and the couples must split evenly).  Rows 1, 3, 5, 7 pair among
-themselves, as do rows 2, 4, 6, one of which is the mixed tile: 9 choices x the order of the tiles, taken by a seeded shuffle.  Prints
+Which of the remaining 56 positions (rows 1-7, columns 1-8) go where decides two things.
+  Stores.  A lane pair stores the 16 bytes of one position and channel chunk; a chunk plane is 81 x 16 B, so a board row's columns 1-8 are 128
+contiguous bytes, at every 16-byte alignment over the 16 chunks.  The L2 writes 64-byte granules (4 positions) back, 32-byte sectors
+(2 positions) at the least: a granule whose positions sit in ONE tile is filled by one store instruction; one whose positions sit in several
+tiles is filled piecemeal, units apart, and leaves the L2 once per piece if the line is evicted in between.  So the table keeps WHOLE ROWS
+together: a row's 8 cells differ mod 8, hence a row is a valid spanning tile, and two rows form a conflict-free local tile iff their first
+cells differ by an even number mod 16, that is iff the rows are an even number of rows apart (per class mod 8 the two cells are either equal
+mod 16 -- one in the A lanes, one in the B lanes -- or a (c, c + 8) couple that shares a lane group, and the couples must split evenly).
+  Fragment reads.  The B fragment of a local tile at tap row dy is the LDS data of the tile one board row lower at tap row dy - 1 -- if the
+lower tile is the upper one shifted by a board row LANE FOR LANE.  Rows FOUR apart are the choice that lets the three local tiles be
+row shifts of one another: tile 0 = rows (1, 5), tile 1 = tile 0 + 9 = rows (2, 6), tile 2 = tile 0 + 18 = rows (3, 7), and row 4 is the
+spanning tile.  The kernel then reads one fragment per (row set, tap column, k-half) for all the tiles it feeds (the skewed k-step order).
+A shift by a board row moves every cell by the pitch, hence every bank class by the same amount: the shifted tiles are conflict-free
+because tile 0 is.
+
+What stays free is the lane order of tile 0 -- which cell of an equal-class pair sits in the A lanes, which two of the four couples -- and which
+board of the spanning tile has the A lanes: 192 tables that the rules above do not tell apart, one taken by the recorded seed.  Prints
 the table as a C initializer with the number of sector-complete stores -- neighbouring positions (p, p + 1) of a board inside one tile: each
 is one 32-byte sector stored whole in the chunks of one parity --; the header static_asserts the rules and the count again."""
 import random
@@ -26,7 +34,8 @@ import random
 P, C0, S, CORNER = 11, 12, 9, 72
 A = [0, 1, 2, 3, 12, 13, 14, 15]
 B = [4, 5, 6, 7, 8, 9, 10, 11]
-SEED = 9
+SEED = 66
+BASE_ROWS, SPANNING_ROW = (1, 5), 4  # tile 0; tiles 1 and 2 are tile 0 one and two board rows lower
 
 
 def cell(p):
@@ -36,45 +45,26 @@ def cell(p):
 TOP = [x for x in range(1, 9)]
 BOTTOM = [8 * S + x for x in range(1, 9)]
 LEFT = [y * S for y in range(8)]
-for edge in (TOP, BOTTOM, LEFT):
-    assert sorted(cell(p) % 8 for p in edge) == list(range(8)), edge
 ROWS = {y: [y * S + x for x in range(1, 9)] for y in range(1, 8)}
-assert all(sorted(cell(p) % 8 for p in r) == list(range(8)) for r in ROWS.values())
 
 
-def local_tile(ya, yb):
-    """(A lanes' positions, B lanes' positions) of the tile made of rows ya and yb, or None if the couples do not split evenly"""
+def base_tile(rng, ya, yb):
+    """(A lanes' positions, B lanes' positions) of the tile made of rows ya and yb, the free choices drawn from rng"""
     a, b, couples = [], [], []
     for c in range(8):
         p, = [v for v in ROWS[ya] if cell(v) % 8 == c]
         q, = [v for v in ROWS[yb] if cell(v) % 8 == c]
         if cell(p) % 16 == cell(q) % 16:
+            if rng.random() < 0.5:
+                p, q = q, p
             a.append(p), b.append(q)
         else:
             couples.append((p, q))
-    if len(couples) % 2:
-        return None
-    for i, (p, q) in enumerate(couples):  # half of the couples in the A lanes, half in the B lanes
-        (a if i % 2 == 0 else b).extend((p, q))
+    assert len(couples) % 2 == 0, "rows an even number of rows apart"
+    in_a = set(rng.sample(range(len(couples)), len(couples) // 2))  # half of the couples in the A lanes, half in the B lanes
+    for i, pq in enumerate(couples):
+        (a if i in in_a else b).extend(pq)
     return sorted(a), sorted(b)
-
-
-def search(rng):
-    """(mixed tile's row, three local tiles) for one shuffle of the rows: first row alone, then pairs in order; None if a pair is not a tile"""
-    order = list(ROWS)
-    rng.shuffle(order)
-    tiles = [local_tile(order[1 + 2 * t], order[2 + 2 * t]) for t in range(3)]
-    return None if None in tiles else (ROWS[order[0]], tiles)
-
-
-rng = random.Random(SEED)
-found = None
-for trial in range(10000):
-    found = search(rng)
-    if found:
-        break
-assert found, "no map found"
-mixed, local = found
 
 
 def lanes(a, b):
@@ -86,20 +76,35 @@ def lanes(a, b):
     return row
 
 
-def spanning(pos8):
-    return lanes(sorted(pos8), [81 + p for p in sorted(pos8)])
+def spanning(pos8, flip=False):
+    """board A's positions in the A lanes and board B's in the B lanes, or (flip) the other way round"""
+    own, other = sorted(pos8), [81 + p for p in sorted(pos8)]
+    return lanes(other, own) if flip else lanes(own, other)
 
 
-rows = [lanes(a, b) for a, b in local]                                     # 0-2: board A
-rows += [spanning(TOP), spanning(mixed)]                                   # 3, 4
-rows += [spanning(BOTTOM), spanning(LEFT)]                                 # 5, 6
-rows += [lanes([81 + p for p in a], [81 + p for p in b]) for a, b in local]  # 7-9: board B
-for row in rows:
-    banks = sorted((cell(v % 81) + (8 if n in B else 0)) % 16 for n, v in enumerate(row))
-    assert banks == list(range(16)), (row, banks)
-flat = sorted(v for row in rows for v in row)
-assert flat == sorted(b * 81 + p for b in range(2) for p in range(81) if p != CORNER)
-sector_complete = sum(1 for row in rows for v in row if v + 1 in row and v // 81 == (v + 1) // 81)
-print(f"    // generated by tools/gen_sp_map_pair.py (seed {SEED}, trial {trial}; {sector_complete} sector-complete stores): board * 81 + position of (column tile, lane & 15)")
-for row in rows:
-    print("    " + ", ".join(f"{v:3d}" for v in row) + ",")
+def table(seed):
+    for edge in (TOP, BOTTOM, LEFT):
+        assert sorted(cell(p) % 8 for p in edge) == list(range(8)), edge
+    assert all(sorted(cell(p) % 8 for p in r) == list(range(8)) for r in ROWS.values())
+    rng = random.Random(seed)
+    a, b = base_tile(rng, *BASE_ROWS)
+    flip = rng.random() < 0.5
+    local = [([p + S * j for p in a], [p + S * j for p in b]) for j in range(3)]
+    rows = [lanes(a, b) for a, b in local]                                      # 0-2: board A
+    rows += [spanning(TOP), spanning(ROWS[SPANNING_ROW], flip)]                 # 3, 4
+    rows += [spanning(BOTTOM), spanning(LEFT)]                                  # 5, 6
+    rows += [lanes([81 + p for p in a], [81 + p for p in b]) for a, b in local]   # 7-9: board B
+    for row in rows:
+        banks = sorted((cell(v % 81) + (8 if n in B else 0)) % 16 for n, v in enumerate(row))
+        assert banks == list(range(16)), (row, banks)
+    flat = sorted(v for row in rows for v in row)
+    assert flat == sorted(b * 81 + p for b in range(2) for p in range(81) if p != CORNER)
+    return rows
+
+
+if __name__ == "__main__":
+    rows = table(SEED)
+    sector_complete = sum(1 for row in rows for v in row if v + 1 in row and v // 81 == (v + 1) // 81)
+    print(f"    // generated by tools/gen_sp_map_pair.py (seed {SEED}; {sector_complete} sector-complete stores): board * 81 + position of (column tile, lane & 15)")
+    for row in rows:
+        print("    " + ", ".join(f"{v:3d}" for v in row) + ",")

@@ -12,7 +12,11 @@ too), SP2P_NO_RES (the residual loads of the units and of the corner phase read 
 LDS-DMA piece is issued with an empty exec mask: no image is fetched), SP2P_VMCNT0 (NOT an ablation: the counted wait in front of an end
 barrier becomes vmcnt(0); outputs must stay bit-identical), and the cache-policy variants, which keep every output bit: SP2P_NT_RES (the
 residual loads carry nt), SP2P_NT_STORE (the output stores carry nt), SP2P_NT_ALL (both), SP2P_PLAIN_DMA (the global_load_lds_dwordx4 of
-dma_piece WITHOUT the nt the product gives it; profiles/sp2p_ablation.txt measured the three nt items on the header that had none).
+dma_piece WITHOUT the nt the product gives it; profiles/sp2p_ablation.txt measured the three nt items on the header that had none), and the
+builds around the skewed units, bit-identical as well: SP2P_PLAIN_ORDER (no shared fragments: every unit reads a fragment per live tile in
+the plain k-step order, on the product's table), SP2P_EARLY_RES (an item that was measured and left out of the product: the two residual
+loads of a corner batch issued in U3 of the batch's last pair instead of in the corner phase) and SP2P_EARLY_RES_PLAIN_ORDER (both patches: the
+early corner residual alone).  profiles/sp2p_skew_ab.txt: the product is "shared fragments alone".
 tools/split_bench.py times several builds in one process (AZ_BENCH_LIBS), tools/split_pmc.py launches them for a counter pass."""
 import os
 import shutil
@@ -108,10 +112,37 @@ def patch_sp2p(text, variant):
         rep(ST_LO, "} else if (store_ok) __builtin_nontemporal_store((cv_u32x2){lpk[0], lpk[1]}, (__attribute__((address_space(1))) cv_u32x2*)(out_lo + gq));", 1)
         rep(CST_HI, "__builtin_nontemporal_store((cv_u32x2){sp_pack(h[0], h[1]), sp_pack(h[2], h[3])}, (cv_u32x2*)(y + co));", 1)
         rep(CST_LO, "__builtin_nontemporal_store((cv_u32x2){sp_pack(l[0], l[1]), sp_pack(l[2], l[3])}, (cv_u32x2*)(y + co + YPLANE));", 1)
+    if variant in ("SP2P_PLAIN_ORDER", "SP2P_EARLY_RES_PLAIN_ORDER"):
+        rep("s.shared = sp2p_row_shifts(sp2p_map_table, u);", "s.shared = false;", 1)
+        rep("static_assert(Sp2pU<0>::S.ns == 30 && Sp2pU<3>::S.ns == 24 &&", "static_assert(Sp2pU<0>::S.ns == 18 && Sp2pU<3>::S.ns == 18 &&", 1)
+        rep("static_assert(Sp2pU<0>::S.reads() == 60 && Sp2pU<1>::S.reads() == 60 && Sp2pU<2>::S.reads() == 84 && Sp2pU<3>::S.reads() == 48,",
+            "static_assert(Sp2pU<0>::S.reads() == 108 && Sp2pU<1>::S.reads() == 60 && Sp2pU<2>::S.reads() == 84 && Sp2pU<3>::S.reads() == 72,", 1)
+        rep("static_assert(Sp2pU<0>::S.nfrag(0) == 1,", "static_assert(Sp2pU<0>::S.nfrag(0) == 3,", 1)
+        rep("        frag_req(CpInt<0>{}, CpInt<0>{}, CpInt<1>{});\n", "".join("        frag_req(CpInt<0>{}, CpInt<0>{}, CpInt<%d>{});\n" % q for q in range(1, 6)), 1)
+    if variant in ("SP2P_EARLY_RES", "SP2P_EARLY_RES_PLAIN_ORDER"):
+        # the loads move from the corner phase into slots 2 nj, 2 nj + 1 of U3 (behind U3's own residual loads, in front of its first LDS-DMA piece: the
+        # counted wait of U3's end barrier covers them), on the last pair of a corner batch, into set 1's third rr entry, which a two-tile unit leaves free
+        rep("        const bool have_prev = it > 0;\n", """        const bool have_prev = it > 0;
+        const bool corner_next = cb + 2 == SP2P_NB || !has_next;
+        auto corner_off = [&](int n_ok) __attribute__((always_inline)) {
+            const int it0 = it - (n_ok / 2 - 1), nb = l15 < n_ok ? l15 : 0;
+            const size_t board = 2 * ((size_t)slot + (size_t)(it0 + (nb >> 1)) * nslot) + (nb & 1);
+            return board * YTILE + (size_t)(cg * 8 + wa * 4 + wb * 2 + (kg >> 1)) * GBLK + G::CORNER * 16 + (kg & 1) * 8;
+        };
+""", 1)
+        rep("                __builtin_amdgcn_sched_barrier(0);\n                if constexpr (K::DMA &&", """                if constexpr (RES && u == 3 && sl >= 2 * nj && sl < 2 * nj + 2) {
+                    static_assert(2 * nj + 2 <= K::PFIRST && nj < NJ0, "older than the pieces; a free rr entry");
+                    if (corner_next) rr[1][NJ0 - 1][sl - 2 * nj] = *(const cv_u32x2*)(res + corner_off(cb + 2) + (sl - 2 * nj) * YPLANE);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (K::DMA &&""", 1)
+        rep(CLD_HI, "", 1)
+        rep(CLD_LO, "", 1)
+        rep("const cv_u32x2 rh = rr[0][0][0], rl = rr[0][0][1];", "const cv_u32x2 rh = rr[1][NJ0 - 1][0], rl = rr[1][NJ0 - 1][1];", 1)
     return text
 
 
-SP2P_VARIANTS = ("SP2P_NO_STORE", "SP2P_NO_RES", "SP2P_NO_DMA", "SP2P_VMCNT0", "SP2P_NT_RES", "SP2P_NT_STORE", "SP2P_NT_ALL", "SP2P_PLAIN_DMA")
+SP2P_VARIANTS = ("SP2P_NO_STORE", "SP2P_NO_RES", "SP2P_NO_DMA", "SP2P_VMCNT0", "SP2P_NT_RES", "SP2P_NT_STORE", "SP2P_NT_ALL", "SP2P_PLAIN_DMA", "SP2P_PLAIN_ORDER", "SP2P_EARLY_RES", "SP2P_EARLY_RES_PLAIN_ORDER")
 
 
 def build(variant):
