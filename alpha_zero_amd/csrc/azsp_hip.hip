@@ -15,7 +15,6 @@
 #include "az_resblock_sp17.h"
 #include "az_conv_sp2p.h"
 #include "az_conv_spg.h"
-#include "az_stem_spg.h"
 
 static hipError_t g_last = hipSuccess;
 #define AZ_HIP(x) ((g_last = (x)) == hipSuccess ? 0 : -1)
@@ -283,25 +282,35 @@ static int launch_sp17(const void* x, const void* w, const float* bias, const vo
     return launch_k(k_conv3x3_sp17<RES, NCH, XLO0>, grid, CW_THREADS, 0, st, (const unsigned char*)x, (const _Float16*)w, bias, (const unsigned char*)res,
                     (unsigned char*)y, (int)boards, relu, range);
 }
-// k_conv3x3_spg (az_conv_spg.h): the fp32-class convolution with one WAVE per output tile -- any plane size, 64 / 128 / 256 filters.
+// The wave-per-tile kernels of az_conv_spg.h: one WAVE per 16 NT couts x 16 NJ positions of an S x S plane, four waves per workgroup.
+static long long spg_wave_items(long long boards, int S, int C, int NT, int NJ) {
+    const long long nct = ((long long)S * S + 15) / 16;
+    return boards * ((nct + NJ - 1) / NJ) * (C / (16 * NT));
+}
+// the grid of a launch of one wave per item; 0: too many for one launch
+static unsigned spg_wave_grid(long long boards, int S, int C, int NT, int NJ) {
+    const long long grid = (spg_wave_items(boards, S, C, NT, NJ) + 3) / 4;
+    return grid > 0x7fffffffLL ? 0u : (unsigned)grid;
+}
+// k_conv3x3_spg: the fp32-class convolution with one WAVE per output tile -- any plane size, 64 / 128 / 256 filters.
 // `latency`: small tiles (16 couts x 32 positions per wave) so that a handful of boards fill the chip; otherwise k_conv3x3_spgw:
 // 16 NT couts x 48 positions per wave, the B fragments shared by the four waves of a workgroup through LDS.
-// `halves` = 2: k_conv3x3_sp2p's two accumulation chains (bit-identical to it at 9x9 x 128).
+// `halves` = 2 (latency only): k_conv3x3_sp2p's two accumulation chains (bit-identical to it at 9x9 x 128).
 template <bool RES, int KSUB, int NT, int NJ, int HALVES>
 static int launch_spg_t(const void* x, const void* w, const float* bias, const void* res, void* y, long long boards, int S, int C, int relu, void* st,
                         unsigned* range) {
-    const long long nct = ((long long)S * S + 15) / 16, items = boards * ((nct + NJ - 1) / NJ) * (C / (16 * NT)), grid = (items + 3) / 4;
-    if (grid > 0x7fffffffLL) return 1;
-    return launch_k(k_conv3x3_spg<RES, KSUB, NT, NJ, HALVES>, (unsigned)grid, 256, 0, st, (const unsigned char*)x, (const _Float16*)w, bias,
+    const unsigned grid = spg_wave_grid(boards, S, C, NT, NJ);
+    if (!grid) return 1;
+    return launch_k(k_conv3x3_spg<RES, KSUB, NT, NJ, HALVES>, grid, 256, 0, st, (const unsigned char*)x, (const _Float16*)w, bias,
                     (const unsigned char*)(RES ? res : nullptr), (unsigned char*)y, (int)boards, S, C, relu, range);
 }
 // large calls: the four waves of a workgroup share their B fragments through LDS (k_conv3x3_spgw; NT cout tiles per wave, C = 64 NT x groups)
-template <bool RES, int KSUB, int NT, int HALVES>
+template <bool RES, int KSUB, int NT>
 static int launch_spgw_t(const void* x, const void* w, const float* bias, const void* res, void* y, long long boards, int S, int C, int relu, void* st,
                          unsigned* range) {
     const long long nct = ((long long)S * S + 15) / 16, grid = (boards * ((nct + 2) / 3) * (C / (64 * NT)) + 7) / 8 * 8;  // (a multiple of 8: XCD-aware order)
     if (grid > 0x7fffffffLL || C % (64 * NT)) return 1;
-    return launch_k(k_conv3x3_spgw<RES, KSUB, NT, HALVES>, (unsigned)grid, 256, 0, st, (const unsigned char*)x, (const _Float16*)w, bias,
+    return launch_k(k_conv3x3_spgw<RES, KSUB, NT>, (unsigned)grid, 256, 0, st, (const unsigned char*)x, (const _Float16*)w, bias,
                     (const unsigned char*)(RES ? res : nullptr), (unsigned char*)y, (int)boards, S, C, relu, range);
 }
 template <int KSUB, int HALVES>
@@ -309,8 +318,8 @@ static int launch_spg_k(const void* x, const void* w, const float* bias, const v
                         unsigned* range, bool latency) {
     constexpr int NT = KSUB == 2 ? 1 : 2;
     return with_flag(res != nullptr, [&](auto RES) {
-        return latency ? launch_spg_t<RES, KSUB, 1, 2, HALVES>(x, w, bias, res, y, boards, S, C, relu, st, range)
-                       : launch_spgw_t<RES, KSUB, NT, HALVES>(x, w, bias, res, y, boards, S, C, relu, st, range);
+        return latency || HALVES == 2 ? launch_spg_t<RES, KSUB, 1, 2, HALVES>(x, w, bias, res, y, boards, S, C, relu, st, range)
+                                      : launch_spgw_t<RES, KSUB, NT>(x, w, bias, res, y, boards, S, C, relu, st, range);
     });
 }
 static int launch_spg(const void* x, const void* w, const float* bias, const void* res, void* y, long long boards, int S, int C, int relu, void* st,
@@ -337,7 +346,7 @@ static long long& spg_max_waves() {
     }();
     return n;
 }
-static bool small_batch(long long boards, int S, int C) { return boards * ((((long long)S * S + 15) / 16 + 1) / 2) * (C / 16) <= spg_max_waves(); }
+static bool small_batch(long long boards, int S, int C) { return spg_wave_items(boards, S, C, 1, 2) <= spg_max_waves(); }
 long long small_batch_waves(long long n) {
     const long long old = spg_max_waves();
     if (n >= 0) spg_max_waves() = n;
@@ -414,18 +423,17 @@ int launch_split_features(const float* src, void* dst, long long boards, int S, 
     const long long nitems = boards * 4 * S * S;
     return launch_k(k_split_features, (unsigned)((nitems + 255) / 256), 256, 0, st, src, (unsigned char*)dst, nitems, cin, S * S, range);
 }
-// (k_stem_spg repeats k_conv3x3_spg's index, ring and accumulator set-up for the stem's geometry: a fix to one belongs in the other too.)
-// k_stem_spg (az_stem_spg.h): the stem with one WAVE per output tile (16 couts x 32 positions) -- any board, pad 1 or 3, 64 / 128 / 256 filters
+// k_stem_spg (az_conv_spg.h): the stem with one WAVE per output tile (16 couts x 32 positions) -- any board, pad 1 or 3, 64 / 128 / 256 filters
 template <bool XLO0>
 static int launch_stem_spg(const void* x, const void* w, const float* bias, void* y, long long boards, int n, int C, int pad, int relu, void* st,
                            unsigned* range) {
     constexpr int NT = 1, NJ = 2;
     const int off = pad - 1, S = n + 2 * off;
     if ((pad != 1 && pad != 3) || n < 1 || S < 3 || S > 64 || (C != 64 && C != 128 && C != 256) || boards < 1 || boards > 0x7fffffffLL) return 1;
-    const long long nct = ((long long)S * S + 15) / 16, items = boards * ((nct + NJ - 1) / NJ) * (C / (16 * NT)), grid = (items + 3) / 4;
-    if (grid > 0x7fffffffLL) return 1;
-    return launch_k(k_stem_spg<XLO0, NT, NJ>, (unsigned)grid, 256, 0, st, (const unsigned char*)x, (const _Float16*)w, bias, (unsigned char*)y, (int)boards,
-                    n, off, C, relu, range);
+    const unsigned grid = spg_wave_grid(boards, S, C, NT, NJ);
+    if (!grid) return 1;
+    return launch_k(k_stem_spg<XLO0, NT, NJ>, grid, 256, 0, st, (const unsigned char*)x, (const _Float16*)w, bias, (unsigned char*)y, (int)boards, n, off,
+                    C, relu, range);
 }
 // S: the BOARD (the output planes are S + 2 (pad - 1) wide).  The three tailored shapes run their weight-stationary stems unless the call
 // is small (small_batch on the output plane, as the tower: bit-identical results); every other shape runs the wave-per-tile stem.

@@ -429,7 +429,7 @@ int azsp_resblock_split(const void* x_dev, const void* w1_split_dev, const float
  *   board_size), w_split [2 planes][9 taps][C out][32 in] f16 (input channels >= the network's zero), y in the tower's split layout
  *   with planes S = board_size + 2 (pad - 1): pad = 1 for Go, pad = 3 for Gomoku (network.py:101-105).  On the device: tailored
  *   weight-stationary stems for (board 9, C 128 or 64, pad 1) and (board 13, C 64, pad 3); every other board with pad 1 or 3, planes
- *   3 <= S <= 64 and C = 64, 128 or 256 on the wave-per-tile stem k_stem_spg (csrc/az_stem_spg.h; one wave per 16 couts x 32 positions,
+ *   3 <= S <= 64 and C = 64, 128 or 256 on the wave-per-tile stem k_stem_spg (csrc/az_conv_spg.h; one wave per 16 couts x 32 positions,
  *   the embedding margin of pad 3 as zero fragments), AZSP_EINVAL otherwise.  The three tailored shapes run k_stem_spg too -- with
  *   BIT-IDENTICAL results -- when the call is small by azsp_small_batch_waves (counted on the output planes) AND that limit has been
  *   raised above its default of 1024: at the default the tailored stems keep every call (see azsp_small_batch_waves).  The host twin

@@ -1,4 +1,4 @@
-"""The wave-per-tile stem of the fp32-class evaluator (k_stem_spg, csrc/az_stem_spg.h: azsp_stem_split / azsp_stem_split_exact on any
+"""The wave-per-tile stem of the fp32-class evaluator (k_stem_spg, csrc/az_conv_spg.h: azsp_stem_split / azsp_stem_split_exact on any
 board) and the opt-in whole evaluator built on it (InferenceNet.use_split_any_board, SelfPlayActor(split_any_board=True)).
 
 Checker = torch in fp64 on the CPU; the tailored stems for the bit-identity statements.  Inputs, the stem driver and references are those of

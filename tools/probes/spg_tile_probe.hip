@@ -13,11 +13,10 @@
 // (3 - 4 wave-loads per wave instead of 5 - 6) and every wave reads its 2 NT + 6 fragments from LDS: L1 bytes per MFMA 0.31 -> 0.19 KB at NT = 2
 // (k_conv3x3_spgw is L1-bound: one access per CU and cycle, profiles/r06_pmc_spg19.txt).  Ring of three (8 NT + 12) KB LDS slots, one barrier per
 // k-step, as in k_conv3x3_spgw.  Same chains, same epilogue, same bits.
-template <bool RES, int KSUB, int NT, int HALVES> __global__ void __launch_bounds__(512)
+template <bool RES, int KSUB, int NT> __global__ void __launch_bounds__(512)
 k_conv3x3_spgw8(const unsigned char* __restrict__ x, const _Float16* __restrict__ w, const float* __restrict__ bias, const unsigned char* __restrict__ res,
                 unsigned char* __restrict__ y, int nboards, int S, int C, int relu, unsigned* range) {
-    constexpr int NJ = 3, NFA = 8 * NT, NFB = 12, NF = NFA + NFB, NL = (NF + 7) / 8, CIN = 32 * KSUB, NCHI = 4 * KSUB, NST = 9 * KSUB, KH = KSUB / HALVES;
-    static_assert(KSUB % HALVES == 0, "k-steps");
+    constexpr int NJ = 3, NFA = 8 * NT, NFB = 12, NF = NFA + NFB, NL = (NF + 7) / 8, CIN = 32 * KSUB, NCHI = 4 * KSUB, NST = 9 * KSUB;
     __shared__ __attribute__((aligned(1024))) unsigned char lds[3][NF][1024];
     static_assert(sizeof(lds) <= 160 * 1024, "LDS budget");
     const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, kg = lane >> 4;
@@ -30,25 +29,7 @@ k_conv3x3_spgw8(const unsigned char* __restrict__ x, const _Float16* __restrict_
     const int cg = cq * 4 + cgi, jg = jp * 2 + jgi;
     const size_t xplane = (size_t)NCHI * P2 * 16, yplane = (size_t)(C / 8) * P2 * 16;
     const unsigned char* xb = x + (size_t)board * 2 * xplane + (size_t)kg * P2 * 16;
-    auto geometry = [&](int g, int j, int& pp, unsigned& m) __attribute__((always_inline)) {  // position + tap mask of column tile j of position group g
-        const int p = (g * NJ + j) * 16 + l15;
-        pp = p < P2 ? p : P2 - 1;
-        const int r = pp / S, c = pp - r * S;
-        m = 0;
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            const int yy = r + tap / 3 - 1, xx = c + tap % 3 - 1;
-            m |= (yy >= 0 && xx >= 0 && yy < S && xx < S) ? (1u << tap) : 0u;
-        }
-    };
-    int pos[NJ];
-    bool live[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        unsigned m;
-        geometry(jg, j, pos[j], m);
-        live[j] = (jg * NJ + j) * 16 + l15 < P2;
-    }
+    const SpgTile<NJ> g = spg_tile<false, NJ>(jg * NJ, l15, S, S, 0);
     // this wave's share of a k-step's fragments: f = wave + 8 k.  f < NFA: A fragment (cout group f / (2 NT), tile (f / 2) % NT, plane f % 2);
     // otherwise B fragment f - NFA = (position group, plane, column tile) = (fb / 6, (fb % 6) / 3, fb % 3)
     const _Float16* la[NL];
@@ -60,51 +41,37 @@ k_conv3x3_spgw8(const unsigned char* __restrict__ x, const _Float16* __restrict_
         const int f = wave + 8 * k;
         la[k] = w + ((size_t)(f & 1) * 9 * C + (size_t)((cq * 4 + f / (2 * NT)) * NT + (f / 2) % NT) * 16 + l15) * CIN + kg * 8;
         const int fb = f >= NFA && f < NF ? f - NFA : 0;
-        geometry(jp * 2 + fb / 6, fb % 3, lpos[k], lin[k]);
+        const SpgTile<1> gl = spg_tile<false, 1>((jp * 2 + fb / 6) * NJ + fb % 3, l15, S, S, 0);  // position + tap mask of the fragment's column tile
+        lpos[k] = gl.pos[0], lin[k] = gl.inside[0];
         lb[k] = xb + (size_t)((fb % 6) / 3) * xplane;
     }
     sp_f16x8 rg[2][NL];
     auto load_f = [&](int s, int par) __attribute__((always_inline)) {
-        const int tap = s / KSUB, ks = s % KSUB, d = (tap / 3 - 1) * S + (tap % 3 - 1);
+        const int tap = s / KSUB, ks = s % KSUB;
 #pragma unroll
         for (int k = 0; k < NL; ++k) {
             const int f = wave + 8 * k;  // (wave-uniform branches)
             if (f < NFA) rg[par][k] = *(const sp_f16x8*)(la[k] + (size_t)tap * C * CIN + ks * 32);
-            else if (f < NF) rg[par][k] = *(const sp_f16x8*)(lb[k] + ((size_t)ks * 4 * P2 + lpos[k] + (((lin[k] >> tap) & 1u) ? d : 0)) * 16);
+            else if (f < NF) rg[par][k] = *(const sp_f16x8*)(lb[k] + ((size_t)ks * 4 * P2 + spg_tap_cell<false>(lpos[k], lin[k], tap, S)) * 16);
         }
     };
     auto store_f = [&](int s, int par) __attribute__((always_inline)) {
-        const int tap = s / KSUB;
-        const sp_f16x8 zero = (sp_f16x8){0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
         for (int k = 0; k < NL; ++k) {
             const int f = wave + 8 * k;
             if (f < NFA) *(sp_f16x8*)(&lds[s % 3][f][lane * 16]) = rg[par][k];
-            else if (f < NF) *(sp_f16x8*)(&lds[s % 3][f][lane * 16]) = ((lin[k] >> tap) & 1u) ? rg[par][k] : zero;
+            else if (f < NF) *(sp_f16x8*)(&lds[s % 3][f][lane * 16]) = spg_mask(lin[k], s / KSUB, rg[par][k]);
         }
     };
-    c6_f32x4 am[HALVES][NT][NJ], ac[HALVES][NT][NJ];
+    c6_f32x4 am[1][NT][NJ], ac[1][NT][NJ];
     const float lo_clamp = relu ? 0.0f : -SP_F16_MAX;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int own = HALVES == 2 ? ((cg * NT + t) & 1) : 0;
-        c6_f32x4 bv;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) bv[e] = bias[(cg * NT + t) * 16 + 4 * kg + e];
-#pragma unroll
-        for (int h = 0; h < HALVES; ++h)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                am[h][t][j] = h == own ? bv : (c6_f32x4){0.0f, 0.0f, 0.0f, 0.0f};
-                ac[h][t][j] = (c6_f32x4){0.0f, 0.0f, 0.0f, 0.0f};
-            }
-    }
+    spg_init_acc<false>(am, ac, bias, cg, kg, g.live);
     load_f(0, 0);
     load_f(1, 1);
     store_f(0, 0);
     CV_BARRIER();
     cp_for_each([&](auto SC) __attribute__((always_inline)) {
-        constexpr int s = decltype(SC)::value, h = (s % KSUB) / KH;
+        constexpr int s = decltype(SC)::value;
         sp_f16x8 a[2][NT], bh[NJ], bl[NJ];
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
@@ -119,18 +86,11 @@ k_conv3x3_spgw8(const unsigned char* __restrict__ x, const _Float16* __restrict_
         if constexpr (s + 1 < NST) store_f(s + 1, (s + 1) & 1);
         if constexpr (s + 2 < NST) load_f(s + 2, s & 1);
         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                am[h][t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0][t], bh[j], am[h][t][j], 0, 0, 0);
-                ac[h][t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0][t], bl[j], ac[h][t][j], 0, 0, 0);
-                ac[h][t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[1][t], bh[j], ac[h][t][j], 0, 0, 0);
-            }
+        spg_kstep<false>(am[0], ac[0], a, bh, bl);
         if constexpr (s + 1 < NST) CV_BARRIER();
         __builtin_amdgcn_sched_barrier(0);
     }, typename CpMakeSeq<NST>::type{});
-    spg_epilogue<RES, NT, NJ, HALVES>(am, ac, pos, live, res, y, board, yplane, P2, cg, kg, lo_clamp, range);
+    spg_epilogue<RES, NT, NJ, 1>(am, ac, g.pos, g.live, res, y, board, yplane, P2, cg, kg, lo_clamp, range);
 }
 
 
@@ -162,9 +122,9 @@ template <int KSUB, int NT> static void run_w(const char* tag, int boards, int S
     hipEventCreate(&e0);
     hipEventCreate(&e1);
     const int reps = 10;
-    for (int i = 0; i < 3; ++i) hipLaunchKernelGGL((k_conv3x3_spgw<true, KSUB, NT, 1>), dim3((unsigned)grid), dim3(256), 0, 0, x, w, b, x, y, boards, S, C, 1, nullptr);
+    for (int i = 0; i < 3; ++i) hipLaunchKernelGGL((k_conv3x3_spgw<true, KSUB, NT>), dim3((unsigned)grid), dim3(256), 0, 0, x, w, b, x, y, boards, S, C, 1, nullptr);
     hipEventRecord(e0);
-    for (int i = 0; i < reps; ++i) hipLaunchKernelGGL((k_conv3x3_spgw<true, KSUB, NT, 1>), dim3((unsigned)grid), dim3(256), 0, 0, x, w, b, x, y, boards, S, C, 1, nullptr);
+    for (int i = 0; i < reps; ++i) hipLaunchKernelGGL((k_conv3x3_spgw<true, KSUB, NT>), dim3((unsigned)grid), dim3(256), 0, 0, x, w, b, x, y, boards, S, C, 1, nullptr);
     hipEventRecord(e1);
     hipEventSynchronize(e1);
     float ms = 0;
@@ -185,9 +145,9 @@ template <int KSUB, int NT> static void run_w8(const char* tag, int boards, int 
     hipEventCreate(&e1);
     const int reps = 10;
     hipMemset(y, 0, ybytes);
-    for (int i = 0; i < 3; ++i) hipLaunchKernelGGL((k_conv3x3_spgw8<true, KSUB, NT, 1>), dim3((unsigned)grid), dim3(512), 0, 0, x, w, b, x, y, boards, S, C, 1, nullptr);
+    for (int i = 0; i < 3; ++i) hipLaunchKernelGGL((k_conv3x3_spgw8<true, KSUB, NT>), dim3((unsigned)grid), dim3(512), 0, 0, x, w, b, x, y, boards, S, C, 1, nullptr);
     hipEventRecord(e0);
-    for (int i = 0; i < reps; ++i) hipLaunchKernelGGL((k_conv3x3_spgw8<true, KSUB, NT, 1>), dim3((unsigned)grid), dim3(512), 0, 0, x, w, b, x, y, boards, S, C, 1, nullptr);
+    for (int i = 0; i < reps; ++i) hipLaunchKernelGGL((k_conv3x3_spgw8<true, KSUB, NT>), dim3((unsigned)grid), dim3(512), 0, 0, x, w, b, x, y, boards, S, C, 1, nullptr);
     hipEventRecord(e1);
     hipEventSynchronize(e1);
     float ms = 0;

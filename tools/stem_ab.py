@@ -1,4 +1,4 @@
-"""Same-box A/B of the wave-per-tile fp32-class stem k_stem_spg (csrc/az_stem_spg.h) and of the opt-in whole evaluator built on it
+"""Same-box A/B of the wave-per-tile fp32-class stem k_stem_spg (csrc/az_conv_spg.h) and of the opt-in whole evaluator built on it
 (InferenceNet.use_split_any_board), alternating runs:
   (a) the stem alone on the three tailored shapes, tailored kernel (azsp_small_batch_waves(0)) against wave-per-tile (a huge threshold),
       at 1, 8, 16 and 64 boards: decides whether the default threshold moves the tailored shapes (azsp_hip.hip STEM_SPG_DEFAULT_SMALL);
