@@ -51,6 +51,20 @@ def check_num_simulations(num_simulations):
         raise ValueError(f"Expect `num_simulations` to a positive integer, got {num_simulations}")
 
 
+def slot_simulations(num_simulations, n, limit):
+    """int64[n]: `num_simulations` -- an int for all, or a sequence of n ints -- as one number of simulations per active slot of a
+    search whose engine was built for `limit`.  ValueError for a wrong length or a value outside 1..limit (the engine's node pool and
+    pb_c tables are sized from `limit`)."""
+    a = np.asarray(num_simulations)
+    if a.dtype.kind not in "iu" or a.ndim > 1 or (a.ndim == 1 and a.shape[0] != n):
+        raise ValueError(f"`num_simulations` must be an integer or one integer per active slot ({n}), got {num_simulations!r}")
+    a = np.broadcast_to(a.astype(np.int64), (n,))
+    if n and (a.min() < 1 or a.max() > limit):
+        raise ValueError(f"`num_simulations` of a slot must lie in 1..{limit} (what this search's engine was built for), got "
+                         f"{int(a.min())}..{int(a.max())}")
+    return a
+
+
 def check_planes(eval_func, planes, num_stack):
     cin = getattr(eval_func, "in_channels", None)  # known for evaluators that wrap a network (core/evaluate.py DeviceEvaluator)
     if cin is not None and cin != planes:
@@ -153,7 +167,9 @@ def simulate_on_device(eng, evaluator, num_simulations, num_parallel, slots):
     the engine -- nothing pending, status MOVE_DONE -- but each still costs a forward).  ~8 polls per 100-simulation move instead of 100
     round trips.  With several slots the queue is sized by the slot that owes the most: a finished slot ignores rounds.  Every row is
     evaluated, valid or not, like the batched actor does: the engine ignores outputs of rows it did not ask for.  Same searches as the
-    callback loop with the same evaluator (tests/dropin_checks.py)."""
+    callback loop with the same evaluator (tests/dropin_checks.py).  num_simulations: an int, or one per entry of `slots` (per-slot
+    budgets, Engine.set_budgets): what a pending slot still owes is counted against its own number."""
+    sims = np.broadcast_to(np.asarray(num_simulations, dtype=np.int64), (len(slots),))
     per_iter = 1 if num_parallel == 1 else 2 * num_parallel
     into = getattr(evaluator, "device_eval_into", None)
     eng.round()  # nothing to back up yet: selects the first leaves (or asks for the roots' evaluations)
@@ -163,7 +179,7 @@ def simulate_on_device(eng, evaluator, num_simulations, num_parallel, slots):
         pending = rows[:, _abi.STC_STATUS] != _abi.ST_MOVE_DONE
         if not pending.any():
             return
-        left = max(num_simulations - int(rows[pending, _abi.STC_ROOT_N].min()), 1)
+        left = max(int((sims[pending] - rows[pending, _abi.STC_ROOT_N]).max()), 1)
         for _ in range(max(1, (left // 2) // per_iter)):
             if into is not None:
                 into(eng.features, eng.priors, eng.values)
@@ -215,6 +231,7 @@ class BatchSearch:
                                  max_steps, num_to_win, num_stack, binding, device)
         self.slots = np.zeros(0, dtype=np.int64)  # the active slots (a position is loaded, or a sub-tree was kept), ascending
         self._status = np.full(self.capacity, _abi.ST_IDLE, dtype=np.int32)  # host mirror of the slots' status after load / search / commit
+        self._budgets_set = False  # an earlier search left per-slot budgets in the engine (search(num_simulations=...))
 
     @classmethod
     def for_env(cls, env, capacity, num_simulations, num_parallel=1, c_puct_base=19652.0, c_puct_init=1.25, root_noise=False):
@@ -300,9 +317,11 @@ class BatchSearch:
         return self.load(np.stack([x[0] for x in parts]), np.stack([x[1] for x in parts]), np.stack([x[2] for x in parts]), slots, keep)
 
     # -- search ---------------------------------------------------------------------------------------
-    def search(self, eval_func, noise=None, warm_up=False):
+    def search(self, eval_func, noise=None, warm_up=False, num_simulations=None):
         """Run every active slot's search to its end (status MOVE_DONE).  noise: float64[len(slots), A] Dirichlet draws or None; warm_up:
-        a bool, or one bool per active slot (both in `self.slots` order).
+        a bool, or one bool per active slot (both in `self.slots` order).  num_simulations: None = this object's own number for every
+        slot; an int, or one int per active slot in `self.slots` order, in 1..self.num_simulations = that slot's budget for THIS call
+        (a kept sub-tree whose root already has that many visits is done at once, as in the reference's `while root.N < budget`).
 
         An evaluator with `device_eval_into` / `device_eval` that lives on the engine's device runs the resident loop: the leaves of all
         slots stay on the device, the host polls the status rows a few times per search.  Any other `eval_func` is called on the host:
@@ -311,8 +330,14 @@ class BatchSearch:
         root evaluations) is the one contract of uct_search this class does not keep."""
         check_planes(eval_func, self.eng.planes, self.eng.cfg.num_stack)
         eng, G, sl = self.eng, self.capacity, self.slots
+        sims = self.num_simulations if num_simulations is None else slot_simulations(num_simulations, len(sl), self.num_simulations)
         if len(sl) == 0:
             return
+        if num_simulations is not None or self._budgets_set:  # (None also undoes what an earlier call left in the slots)
+            b = np.zeros(G, dtype=np.int32)
+            b[sl] = 0 if num_simulations is None else sims
+            eng.set_budgets(b)
+            self._budgets_set = num_simulations is not None
         warm = np.full(G, _abi.BM_SKIP, dtype=np.int32)
         warm[sl] = np.broadcast_to(np.asarray(warm_up, dtype=bool), (len(sl),)).astype(np.int32)
         full_noise = None
@@ -323,7 +348,7 @@ class BatchSearch:
                 0, torch.from_numpy(sl).to(eng.device), nz)
         eng.begin_moves(full_noise, warm)
         if is_resident(eval_func, eng):
-            simulate_on_device(eng, eval_func, self.num_simulations, self.num_parallel, sl)
+            simulate_on_device(eng, eval_func, sims, self.num_parallel, sl)
         else:
             simulate_with_callback(eng, eval_func, sl)
         self._status[sl] = _abi.ST_MOVE_DONE

@@ -302,10 +302,31 @@ class Engine:
         threshold and the checkpoint's training_steps before each game); games in progress keep theirs."""
         self._ck(self.b.dll.azsp_set_actor_state(self.h, C.c_double(float(resign_threshold)), int(training_steps)), "azsp_set_actor_state")
 
+    def set_budgets(self, budgets):
+        """Per-slot simulations per move (azsp_set_budgets): int[G], each 1..num_simulations, or 0 = the engine's num_simulations -- the
+        node pool and the pb_c tables are sized from it, so it is the upper limit.  A device tensor, or a host array copied once.
+        Sticky until the next call; a slot that is mid-search uses its new value at its next budget check.  Nothing is synchronised."""
+        if not isinstance(budgets, torch.Tensor):
+            budgets = np.asarray(budgets)
+            if budgets.shape != (self.G,) or budgets.dtype.kind not in "iu":
+                raise ValueError(f"set_budgets takes one integer per slot ({self.G}), got shape {budgets.shape} of {budgets.dtype}")
+            if budgets.min() < 0 or budgets.max() > self.cfg.num_simulations:
+                raise ValueError(f"a slot's simulations must lie in 1..{self.cfg.num_simulations} (the engine's num_simulations; 0 = that "
+                                 f"value), got {int(budgets.min())}..{int(budgets.max())}")
+        b = self._dev_tensor(budgets, torch.int32, (self.G,))
+        self._ck(self.b.dll.azsp_set_budgets(self.h, b.data_ptr(), self._stream()), "azsp_set_budgets")
+
+    def set_playout_cap(self, fast_simulations, full_prob=1.0):
+        """Playout-cap randomisation of the batched actor (azsp_set_playout_cap; not in drop-in mode): every move that starts from now
+        on is a full search (the slot's budget, root noise as configured) with probability `full_prob`, else a fast one of
+        `fast_simulations` (1..num_simulations) without root noise.  fast_simulations = 0 turns the cap off."""
+        self._ck(self.b.dll.azsp_set_playout_cap(self.h, int(fast_simulations), C.c_double(float(full_prob))), "azsp_set_playout_cap")
+
     # -- samples ----------------------------------------------------------------------------------------
-    def harvest(self, sample_capacity=None, max_games=None, with_moves=False):
+    def harvest(self, sample_capacity=None, max_games=None, with_moves=False, with_class=False):
         """Returns (states int8[n,2K+1,N,N], pi float32[n,A], z float32[n], games int32[k,GR_COUNT]) -- device tensors + host meta;
-        with_moves=True appends moves int16[n] (the move played from every sample's position, -1 = resigned).
+        with_moves=True appends moves int16[n] (the move played from every sample's position, -1 = resigned); with_class=True then
+        appends full uint8[n] (1 = the sample's move was a full search, 0 = a fast move of the playout cap; all 1 with the cap off).
         The per-game extras of the same call (azsp_harvest_extra) are left in `self.last_extra` int32[k,GX_COUNT].
         ALIASING: the device tensors are views of buffers this engine re-uses -- the NEXT harvest() overwrites them in place.
         Consume (or .clone()) them before harvesting again; SelfPlayActor.harvest_tensors(clone=True) does the latter."""
@@ -315,9 +336,11 @@ class Engine:
             self._harvest_bufs = (torch.empty((cap, self.planes, self.N, self.N), dtype=torch.int8, device=self.device),
                                   torch.empty((cap, self.A), dtype=torch.float32, device=self.device),
                                   torch.empty((cap,), dtype=torch.float32, device=self.device),
-                                  torch.empty((cap,), dtype=torch.int16, device=self.device))
-        st, pi, z, mvbuf = self._harvest_bufs
+                                  torch.empty((cap,), dtype=torch.int16, device=self.device),
+                                  torch.empty((cap,), dtype=torch.uint8, device=self.device))
+        st, pi, z, mvbuf, clbuf = self._harvest_bufs
         self._ck(self.b.dll.azsp_harvest_moves(self.h, mvbuf.data_ptr() if with_moves else None), "azsp_harvest_moves")
+        self._ck(self.b.dll.azsp_harvest_search_class(self.h, clbuf.data_ptr() if with_class else None), "azsp_harvest_search_class")
         games = np.zeros((mg, _abi.GR_COUNT), dtype=np.int32)
         extra = np.zeros((mg, _abi.GX_COUNT), dtype=np.int32)
         self._ck(self.b.dll.azsp_harvest_extra(self.h, extra.ctypes.data), "azsp_harvest_extra")
@@ -327,9 +350,12 @@ class Engine:
         n, k = ns.value, ng.value
         self._ck(self.b.dll.azsp_harvest_extra(self.h, None), "azsp_harvest_extra")  # the host array dies with this call
         self.last_extra = extra[:k]
+        out = (st[:n], pi[:n], z[:n], games[:k])
         if with_moves:
-            return st[:n], pi[:n], z[:n], games[:k], mvbuf[:n]
-        return st[:n], pi[:n], z[:n], games[:k]
+            out += (mvbuf[:n],)
+        if with_class:
+            out += (clbuf[:n],)
+        return out
 
     def counters(self, reset=False):
         out = np.zeros(16, dtype=np.uint64)

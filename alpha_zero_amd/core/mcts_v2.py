@@ -17,7 +17,7 @@ import numpy as np
 
 from .. import _abi
 from .batch_search import (BatchSearch, check_env, check_num_simulations, check_planes, choose_move, dropin_engine, env_key, env_position,
-                           env_settings, is_resident, simulate_on_device, simulate_with_callback)
+                           env_settings, is_resident, simulate_on_device, simulate_with_callback, slot_simulations)
 
 _POOL = {}  # config key -> idle _Searcher objects
 
@@ -155,6 +155,10 @@ def _search_many(envs, eval_func, root_nodes, c_puct_base, c_puct_init, num_simu
     envs = list(envs)
     for env in envs:
         check_env(env)
+    per_env = None  # a sequence: one number of simulations per env; the engine is built at (and the handle remembers) the largest
+    if isinstance(num_simulations, (list, tuple, np.ndarray)):
+        per_env = slot_simulations(list(num_simulations), len(envs), 1 << 30)
+        num_simulations = int(per_env.max()) if len(per_env) else 1
     check_num_simulations(num_simulations)
     if not envs:
         raise ValueError("Expect at least one env")
@@ -215,7 +219,7 @@ def _search_many(envs, eval_func, root_nodes, c_puct_base, c_puct_init, num_simu
         draws = [np.random.dirichlet(np.ones_like(lg) * 0.03) for lg in legals]
         noise = np.stack([draws[i] for i in order])
     warm = np.broadcast_to(np.asarray(warm_up, dtype=bool), (n,))
-    bs.search(eval_func, noise, warm[order])
+    bs.search(eval_func, noise, warm[order], None if per_env is None else per_env[order])
     pis, child_ns, root_qs = bs.results().cpu()
     moves, search_pis = [], []
     for i, env in enumerate(envs):  # the np.random.choice draws of env 0 until its move is acceptable, then env 1, ...
@@ -234,6 +238,8 @@ def uct_search_many(envs, eval_func, root_nodes, c_puct_base, c_puct_init, num_s
     envs (by identity) to slots: envs that no longer appear have their slots idled, new envs take free slots, slots without a
     re-usable sub-tree are loaded again from their env; a slot whose kept tree does not belong to its env's position raises ValueError.
     All envs share game, board size, komi / max_steps / num_to_win and num_stack.  `warm_up` is a bool or one bool per env.
+    `num_simulations` is an int, or one int per env: the batch's engine is built at the largest and every env is searched at its own
+    number (a later call on the same handle must name the same largest value).
 
     `eval_func` is called as eval_func(obs, True) with the leaf rows of ALL envs (a batched search needs a batch-capable eval_func);
     an evaluator with `device_eval` on the engine's device runs resident (core/batch_search.py).

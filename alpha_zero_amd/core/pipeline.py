@@ -106,7 +106,7 @@ class SelfPlayActor:
                  c_puct_base=19652.0, c_puct_init=1.25, warm_up_steps=16, check_resign_after_steps=40, disable_resign_ratio=0.1,
                  resign_threshold=-1.0, komi=7.5, num_to_win=5, seed=1, rank=0, device="cuda", net_dtype=torch.float32,
                  use_graph=True, training_steps=0, binding=None, root_noise=True, deterministic=False, tiled_features=None, engine_kw=None,
-                 use_split_evaluator=True, auto_widen=None, num_stack=8, split_any_board=False):
+                 use_split_evaluator=True, auto_widen=None, num_stack=8, split_any_board=False, playout_cap=None):
         """net_dtype: precision class of the leaf evaluator.  The default is the REFERENCE'S: fp32 (pipeline.py:91-123 evaluates in fp32,
         no autocast anywhere) -- on the hand-written split-precision kernels (hi + lo f16 pairs, three MFMA products, fp32 accumulation:
         include/azsp.h azsp_conv3x3_split) for 9x9 x {128, 64} and 13x13 Gomoku x 64 networks, on library fp32 convolutions (announced
@@ -122,7 +122,11 @@ class SelfPlayActor:
         None = on the GPU whenever the widened network actually reaches hand-written kernels (not for library comparison runs, not when
         the caller disabled the kernels' feature layouts); True / False force it.
         num_stack: history boards per observation (the env's num_stack, 1..8): the engine writes 2 * num_stack + 1 planes, which must be
-        the network's input channels."""
+        the network's input channels.
+        playout_cap: None, or (fast_simulations, full_prob) = playout-cap randomisation (Engine.set_playout_cap; the reference has none):
+        a move is a full search (num_simulations, root noise) with probability full_prob, else a fast one of fast_simulations without
+        noise that only moves the game on.  Every move is recorded; `harvest()` hands the learner the full-search samples only,
+        `harvest_tensors()` leaves the flags in `last_harvest_full`."""
         from .. import _lib
         from .engine import check_num_stack
 
@@ -163,6 +167,14 @@ class SelfPlayActor:
                 raise TypeError(f"unknown engine option {k}")
             setattr(self.cfg, k, v)
         self.engine = Engine(self.binding, self.cfg, device=self.device)
+        self.playout_cap = None
+        if playout_cap is not None:
+            fast, prob = playout_cap
+            if isinstance(fast, bool) or not isinstance(fast, (int, np.integer)) or not 1 <= fast <= num_simulations or not 0.0 <= float(prob) <= 1.0:
+                raise ValueError(f"playout_cap must be (fast_simulations in 1..{num_simulations}, full_prob in [0, 1]), got {playout_cap!r}")
+            self.playout_cap = (int(fast), float(prob))
+            self.engine.set_playout_cap(*self.playout_cap)  # before the first root: the first move of every game draws its class too
+        self.last_harvest_full = torch.zeros(0, dtype=torch.bool, device=self.device)
         self.engine.reset_games()
         self._graph = None
         self.rounds = 0
@@ -263,10 +275,11 @@ class SelfPlayActor:
         """(states, pi, z, games) of the finished games as device tensors.  The tensors are views of buffers the engine re-uses: the
         next harvest overwrites them in place.  clone=True returns private copies (for consumers that keep them across harvests,
         e.g. an asynchronous learner or a replay insert on another stream)."""
-        st, pi, z, games = self.engine.harvest()
+        st, pi, z, games, full = self.engine.harvest(with_class=True)
         self._check_evaluator_range()
         self.last_harvest_clamped = self.clamp_window.mask(games[:, _abi.GR_UID]) if len(games) else np.zeros(0, dtype=bool)
         self.clamped_games += int(self.last_harvest_clamped.sum())
+        self.last_harvest_full = full != 0  # bool per sample (a new tensor): False = a fast move of the playout cap, not for the learner
         return (st.clone(), pi.clone(), z.clone(), games) if clone else (st, pi, z, games)
 
     def poll_evaluator_range(self):
@@ -302,10 +315,13 @@ class SelfPlayActor:
         """Finished games as the reference actor emits them: [(game_seq: list[Transition], stats: dict)]
         (pipeline.py:283, :356-380).  pi_prob is float64 for Go and float32 for Gomoku like the reference.
         with_moves=True yields (game_seq, stats, moves): the game's move list as env.history holds it (flat actions, N*N = pass;
-        a final resignation is not a history move, base.py:224-226) -- what to_sgf() needs (pipeline.py:276-281)."""
-        got = self.engine.harvest(with_moves=with_moves)
+        a final resignation is not a history move, base.py:224-226) -- what to_sgf() needs (pipeline.py:276-281).
+        Under a playout cap game_seq holds the full-search samples only; stats["game_length"] and the moves stay the whole game's and
+        stats["num_full_samples"] (present only then) is len(game_seq)."""
+        got = self.engine.harvest(with_moves=with_moves, with_class=self.playout_cap is not None)
         self._check_evaluator_range()
         states, pi, z, games = got[:4]
+        full = got[-1].cpu().numpy() != 0 if self.playout_cap is not None else None
         extra = self.engine.last_extra
         if len(games) == 0:
             self.last_harvest_clamped = np.zeros(0, dtype=bool)
@@ -330,11 +346,14 @@ class SelfPlayActor:
                 if self.drop_straddling_games:
                     continue
             pis = pi[s0:s0 + ln].astype(np.float64) if self.game == "go" else pi[s0:s0 + ln]
-            seq = [Transition(state=states[s0 + i].copy(), pi_prob=pis[i].copy(), value=float(z[s0 + i])) for i in range(ln)]
+            seq = [Transition(state=states[s0 + i].copy(), pi_prob=pis[i].copy(), value=float(z[s0 + i])) for i in range(ln)
+                   if full is None or full[s0 + i]]
             # the threshold this very game was played with (pipeline.py:241-242, :379), exact double
             thr = float(np.array([ex[_abi.GX_THRESHOLD_LO], ex[_abi.GX_THRESHOLD_HI]], dtype=np.int32).view(np.float64)[0])
             stats = game_stats_from_row(row, self.game, self.komi, thr)
             stats["training_steps"] = int(row[_abi.GR_TRAINING_STEPS])  # weights in use when the game started (pipeline.py:237, :271, :492)
+            if full is not None:
+                stats["num_full_samples"] = len(seq)
             if clamped:
                 stats["evaluator_clamped"] = True  # (only ever present on such a game: the reference's stats keys stay as they are)
             out.append((seq, stats, [int(m) for m in moves[s0:s0 + ln] if m >= 0]) if with_moves else (seq, stats))
@@ -381,11 +400,13 @@ def load_checkpoint_state(path, allow_pickle=None):
 def run_selfplay_actor_loop(seed, rank, network, device, data_queue, env, num_simulations, num_parallel, c_puct_base, c_puct_init,
                             warm_up_steps, check_resign_after_steps, disable_resign_ratio, save_sgf_dir=None, save_sgf_interval=0,
                             logs_dir=None, load_ckpt=None, log_level="INFO", var_ckpt=None, var_resign_threshold=None,
-                            ckpt_event=None, stop_event=None, num_games=4096, net_dtype=torch.float32, harvest_every=64, binding=None):
+                            ckpt_event=None, stop_event=None, num_games=4096, net_dtype=torch.float32, harvest_every=64, binding=None,
+                            playout_cap=None):
     """Same role and argument list as the reference actor entry point (pipeline.py:166-189), extended by
     `num_games`: one call drives `num_games` games on `device` and puts (game_seq, stats) tuples on
     `data_queue` exactly as `num_games` reference actors would.  `net_dtype` defaults to the reference's evaluator precision (fp32,
-    see SelfPlayActor)."""
+    see SelfPlayActor).  `playout_cap`: None or (fast_simulations, full_prob), see SelfPlayActor: the queued game_seq then hold the
+    full-search samples only."""
     import os
 
     game = "go" if env.has_pass_move else "gomoku"
@@ -400,7 +421,7 @@ def run_selfplay_actor_loop(seed, rank, network, device, data_queue, env, num_si
                           check_resign_after_steps=check_resign_after_steps, disable_resign_ratio=disable_resign_ratio,
                           resign_threshold=thr, komi=getattr(env, "komi", 7.5), num_to_win=getattr(env, "num_to_win", 5),
                           seed=seed, rank=rank, device=device, net_dtype=net_dtype, training_steps=training_steps, binding=binding,
-                          num_stack=getattr(env, "num_stack", 8))
+                          num_stack=getattr(env, "num_stack", 8), playout_cap=playout_cap)
     actor.drop_clamped_games = True  # the learner never sees a game that ran on a clamping evaluator (the reference's fp32 has no range)
     writer = None
     if logs_dir:  # per-actor statistics file with the reference's columns (pipeline.py:196, :268-271; logs/go/9x9/actor0.csv)

@@ -66,8 +66,17 @@ class DeviceReplay:
             self.num_samples_added += n
         self.num_games_added += num_games
 
-    def add_harvest(self, states, pi, z, games):
-        """Everything `SelfPlayActor.harvest_tensors()` returned: finished games, concatenated in harvest order."""
+    def add_harvest(self, states, pi, z, games, keep=None):
+        """Everything `SelfPlayActor.harvest_tensors()` returned: finished games, concatenated in harvest order.  keep: an optional
+        bool per sample (e.g. the actor's `last_harvest_full` under a playout cap): only those rows are stored, in order; the games
+        count as before."""
+        if keep is not None:
+            import torch
+
+            k = torch.as_tensor(keep).to(torch.bool).reshape(-1)
+            if k.shape[0] != int(z.shape[0]):
+                raise ValueError(f"`keep` must hold one flag per sample ({int(z.shape[0])}), got {k.shape[0]}")
+            states, pi, z = (torch.as_tensor(t)[k.to(torch.as_tensor(t).device)] for t in (states, pi, z))
         self.add_samples(states, pi, z, num_games=len(games))
 
     def add_game(self, game_seq):

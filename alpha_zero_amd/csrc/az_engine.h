@@ -25,6 +25,12 @@
 #define AZ_PATH_CAP 64    // tree levels handled lane-parallel (one lane per edge); deeper paths walk the parent links
 #endif
 #define AZ_INJ_K 16       // injected sampling uniforms per move
+// GameRec::sim_budget: the low bits hold the slot's simulations per move, AZ_SB_FAST marks a fast move of the playout cap
+#define AZ_SB_SIMS_MASK 0xFFFF
+#define AZ_SB_FAST 0x10000
+// stg_meta: bit 0 = black to move, AZ_META_FAST = the sample's move was a fast search of the playout cap
+#define AZ_META_BLACK 1
+#define AZ_META_FAST 2
 
 enum { AZS_NEED_ROOT = 0, AZS_SEARCH = 1, AZS_MOVE_DONE = 2, AZS_IDLE = 3, AZS_WAIT_BUF = 4 };
 enum { AZ_ERR_NODES = 1, AZ_ERR_SAMPLE = 4, AZ_ERR_STAGE = 8 };  // bit 2 (tree depth) retired: deep paths walk parent links
@@ -52,6 +58,10 @@ struct AzCfg {
     RuleCfg rc;
     u64 seed;
     int rank;
+    // playout cap (azsp_set_playout_cap; actor mode only, 0 = off): a move is a full search with probability cap_full_prob, else a
+    // fast one of cap_fast simulations without root noise
+    int cap_fast;
+    double cap_full_prob;
 };
 
 struct AzMem {
@@ -67,7 +77,7 @@ struct AzMem {
     const double* inj_unif;  // [G][inj_moves][AZ_INJ_K]
     u64* stg_planes;         // [G][2][stage_cap][16][W]
     float* stg_pi;           // [G][2][stage_cap][A]
-    unsigned char* stg_meta; // [G][2][stage_cap]   1 = black to move
+    unsigned char* stg_meta; // [G][2][stage_cap]   AZ_META_*
     int16_t* stg_move;       // [G][2][stage_cap]   the move played from the sample's position (-1 = resigned)
     int* stg_hdr;            // [G][2][16]  see SH_*
     // move log (tests / shim): per game per logged move
@@ -93,7 +103,7 @@ template <int W> struct GameRec {
     // per-game actor state, read when the game starts like the reference actor does before every game (pipeline.py:232-246):
     double resign_thr;   // var_resign_threshold.value at game start (<= -1: no resignation in this game)
     int train_steps;     // training_steps of the weights in use at game start (pipeline.py:237, :271)
-    int pad0;
+    int sim_budget;      // AZ_SB_*: the slot's own simulations per move (azsp_set_budgets, 0 = the engine's) and the class of the move in progress
     int16_t leaf_node[AZ_MAXP];
     uint8_t leaf_depth[AZ_MAXP];
 };
@@ -224,6 +234,33 @@ template <class Wv, int N, int GAME> struct Engine {
         const int ti = n < c.tab_len ? n : c.tab_len - 1;
         pbc = Wv::uni(fresh ? m.pbc_py[ti] : m.pbc_np[ti]);
         sq = Wv::uni(m.sqrt32[ti]);
+    }
+
+    // The root visit count that ends this game's search (mcts_v2.py:378 / :568): its own simulations per move -- the slot's value, the
+    // playout cap's on a fast move, else the engine's, clamped into [1, sims] because pool and tables are sized for `sims` -- plus P in
+    // parallel mode, as azsp_create derives c.budget.
+    AZ_HD int game_budget() const {
+        const int sb = Wv::uni(gr.sim_budget);
+        int s = (sb & AZ_SB_FAST) ? c.cap_fast : (sb & AZ_SB_SIMS_MASK);
+        if (s == 0) s = c.sims;
+        s = s < 1 ? 1 : (s > c.sims ? c.sims : s);
+        return s + (c.parallel_mode ? c.P : 0);
+    }
+    // Playout cap: the class of the move that starts now, from the game's own counter-based stream (a counter word of its own: the
+    // Dirichlet stream uses `| action`, move sampling `| 0xFFF`).  Returns the move's noise_pending.  (first lane only)
+    AZ_HD int begin_move_class() {
+        int sb = gr.sim_budget & ~AZ_SB_FAST;
+        int noise = c.root_noise;
+        if (c.cap_fast > 0 && !c.stop_after_move) {
+            u32 r[4];
+            Philox::gen(c.seed + (u64)c.rank, (u32)g, (u32)gr.uid, ((u32)gr.ply << 12) | 0xFFEu, 0x2000u, r);
+            if (!(Philox::u01(r[0], r[1]) < c.cap_full_prob)) {
+                sb |= AZ_SB_FAST;
+                noise = 0;
+            }
+        }
+        gr.sim_budget = sb;
+        return noise;
     }
 
     AZ_HD Engine(const AzCfg& c_, const AzMem& m_, int g_, SC& sc_)
@@ -759,7 +796,10 @@ template <class Wv, int N, int GAME> struct Engine {
             return;
         }
         int nleaf = 0;
-        if (status == AZS_SEARCH && !Wv::uni(gr.noise_pending)) {
+        // `while root.N < budget` (mcts_v2.py:378 / :568): a kept sub-tree whose root already has its budget's visits owes no simulation;
+        // the next end-of-move phase finishes its move
+        const int budget = game_budget();
+        if (status == AZS_SEARCH && !Wv::uni(gr.noise_pending) && hs_rootN < budget) {
             int attempts = 0;
             {  // the next pops of the free stack, staged once per round
                 const int base = hs_nfree - AZ_FREE_PREFETCH;
@@ -791,8 +831,8 @@ template <class Wv, int N, int GAME> struct Engine {
                     // mcts_v2.py:407-411 / :604-608: back up -reward, node stays unexpanded
                     cnt[AZC_TERMINAL_HITS]++;
                     path_apply(depth, node, (float)(-(int)leaf.reward), true, true);
-                    if (!c.parallel_mode && hs_rootN < c.budget) attempts = 0;  // uct_search keeps looping (:378)
-                    if (!c.parallel_mode && hs_rootN >= c.budget) break;
+                    if (!c.parallel_mode && hs_rootN < budget) attempts = 0;  // uct_search keeps looping (:378)
+                    if (!c.parallel_mode && hs_rootN >= budget) break;
                     continue;
                 }
                 if (c.parallel_mode) path_apply(depth, node, 1.0f, false, false);  // add_virtual_loss :453-467
@@ -848,7 +888,7 @@ template <class Wv, int N, int GAME> struct Engine {
                 gr.root_noisy = 0;
                 gr.root_eval_pending = 0;
                 gr.status = AZS_SEARCH;
-                gr.noise_pending = c.root_noise;
+                gr.noise_pending = begin_move_class();
             }
             Wv::sync();
             return;
@@ -1104,7 +1144,7 @@ template <class Wv, int N, int GAME> struct Engine {
             for (int a = lane; a < A; a += AZ_WAVE) pi[a] = (float)sc.pi[a];
         });
         if (Wv::first()) {
-            m.stg_meta[idx] = me == 0 ? 1 : 0;
+            m.stg_meta[idx] = (unsigned char)((me == 0 ? AZ_META_BLACK : 0) | ((gr.sim_budget & AZ_SB_FAST) ? AZ_META_FAST : 0));
             sh[SH_LEN] = k + 1;
         }
         Wv::sync();
@@ -1180,7 +1220,7 @@ template <class Wv, int N, int GAME> struct Engine {
             gr.root_W = (double)cw;
             gr.root_fresh = 0;
             gr.root_noisy = 0;
-            gr.noise_pending = c.root_noise;
+            gr.noise_pending = begin_move_class();
         }
         Wv::sync();
     }
@@ -1402,7 +1442,7 @@ template <class Wv, int N, int GAME> struct Engine {
             if (Wv::uni(gr.status) != AZS_SEARCH) break;
             if (Wv::uni(gr.noise_pending) && (!c.stop_after_move || Wv::uni(gr.noise_ready))) apply_noise();
             if (Wv::uni(gr.noise_pending)) break;  // drop-in mode: the noise vector arrives with begin_move
-            if (Wv::uni(gr.root_N) < c.budget) break;
+            if (Wv::uni(gr.root_N) < game_budget()) break;
             search_done();
         }
     }

@@ -38,6 +38,16 @@ struct OpReset {
         e.new_game();
     }
 };
+// azsp_set_budgets: every slot's own simulations per move (0 = the engine's); the class bit of a move in progress stays
+struct OpSetBudgets {
+    const int* budgets;  // [G]
+    template <class E> AZ_HD void operator()(E& e) const {
+        int v = E::Wave::uni(budgets[e.g]);
+        v = v < 0 ? 1 : (v > e.c.sims ? e.c.sims : v);  // the pool and the pb_c tables are sized for the engine's num_simulations
+        if (E::Wave::first()) e.gr.sim_budget = (e.gr.sim_budget & ~AZ_SB_SIMS_MASK) | v;
+        E::Wave::sync();
+    }
+};
 // One engine round = three launches over all games (one wave per game each):
 //   OpBackup   expand + backup of the previous leaf batch                       (hot, light)
 //   OpEndMove  policy / move / sample / env step / re-root / noise for the games whose budget is met
@@ -437,6 +447,7 @@ struct OpHarvest {
     const int* ofs;   // [G][2][2] = (first output row, game index) of a staging buffer, -1 = not this time
     int16_t* moves;   // optional: the move played from every sample's position (azsp_harvest_moves)
     int* extra;       // [max_games][AZSP_GX_COUNT]
+    uint8_t* klass;   // optional: 1 = the sample's move was a full search, 0 = a fast one of the playout cap (azsp_harvest_search_class)
     template <class E> AZ_HD void operator()(E& e) const {
         const int NP = E::NP, A = E::A, W = E::W;
         const bool go = E::GAME_ID == AZ_GO;
@@ -458,7 +469,7 @@ struct OpHarvest {
                 const size_t idx = ((size_t)e.g * 2 + b) * e.c.stage_cap + k;
                 const u64* pl = e.m.stg_planes + idx * 16 * W;
                 const float* spi = e.m.stg_pi + idx * A;
-                const int black = e.m.stg_meta[idx];
+                const int meta = e.m.stg_meta[idx], black = meta & AZ_META_BLACK;
                 const int KK = 2 * e.c.K;  // stone planes of the observation; the colour plane follows them
                 int8_t* so = states + (size_t)(start + k) * (KK + 1) * NP;
                 float* po = pi + (size_t)(start + k) * A;
@@ -474,6 +485,7 @@ struct OpHarvest {
                     const int mover = black ? 0 : 1;
                     z[start + k] = reward == 0 ? 0.0f : (mover == last_player ? (float)reward : (float)-reward);
                     if (moves) moves[start + k] = e.m.stg_move[idx];
+                    if (klass) klass[start + k] = (meta & AZ_META_FAST) ? 0 : 1;
                 }
             }
             if (E::Wave::first()) {
@@ -699,6 +711,7 @@ struct AzHandle {
     int* d_games;
     int d_games_cap;
     int16_t* harvest_moves = nullptr;  // optional per-sample move output of azsp_harvest (azsp_harvest_moves)
+    uint8_t* harvest_class = nullptr;  // optional per-sample search class output of azsp_harvest (azsp_harvest_search_class)
     int* d_gextra = nullptr;           // [d_games_cap][4] per-game extras (azsp_harvest_extra)
     int32_t* harvest_extra = nullptr;  // host destination of the extras, optional
     unsigned char* pin = nullptr;      // page-locked staging of azsp_dropin_step (one packed upload + one packed read-back per call)
@@ -1219,7 +1232,7 @@ int azsp_harvest(void* e, int8_t* states, float* pi, float* z, int32_t cap, int3
         h->err = std::string("kernel launch failed: ") + azb::backend_error();
         return AZSP_EDEVICE;
     }
-    OpHarvest op = {states, pi, z, cap, h->d_games, max_games, h->d_hofs, h->harvest_moves, h->d_gextra};
+    OpHarvest op = {states, pi, z, cap, h->d_games, max_games, h->d_hofs, h->harvest_moves, h->d_gextra, h->harvest_class};
     rc = az_run(h, op, stream);
     if (rc) return rc;
     int cnt[4];
@@ -1250,6 +1263,29 @@ int azsp_harvest_moves(void* e, int16_t* moves_dev) {
     AzHandle* h = (AzHandle*)e;
     if (!h) return AZSP_EINVAL;
     h->harvest_moves = moves_dev;
+    return AZSP_OK;
+}
+
+int azsp_harvest_search_class(void* e, uint8_t* class_dev) {
+    AzHandle* h = (AzHandle*)e;
+    if (!h) return AZSP_EINVAL;
+    h->harvest_class = class_dev;
+    return AZSP_OK;
+}
+
+int azsp_set_budgets(void* e, const int32_t* budgets_dev, void* stream) {
+    AzHandle* h = (AzHandle*)e;
+    if (!h || !budgets_dev) return AZSP_EINVAL;
+    OpSetBudgets op = {budgets_dev};
+    return az_run(h, op, stream);
+}
+
+int azsp_set_playout_cap(void* e, int32_t fast_simulations, double full_prob) {
+    AzHandle* h = (AzHandle*)e;
+    if (!h || h->cfg.stop_after_move || fast_simulations < 0 || fast_simulations > h->cfg.sims || !(full_prob >= 0.0 && full_prob <= 1.0))
+        return AZSP_EINVAL;
+    h->cfg.cap_fast = fast_simulations;  // AzCfg travels by value with every launch: the next move that starts draws its class
+    h->cfg.cap_full_prob = full_prob;
     return AZSP_OK;
 }
 

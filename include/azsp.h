@@ -31,6 +31,9 @@
  *                                     (core/mcts_v2.py:378-421, :568-625)
  *   azsp_harvest                      data_queue.put((game_seq, stats))         (core/pipeline.py:283, :349-380)
  *   azsp_set_actor_state              per-game re-read of var_resign_threshold / checkpoint tag (core/pipeline.py:232-246)
+ *   azsp_set_budgets                  no counterpart in the reference: opt-in.  num_simulations per game slot
+ *   azsp_set_playout_cap              no counterpart in the reference: opt-in.  A random fraction of an actor's moves gets the full
+ *                                     search, the others a cheap one; azsp_harvest_search_class tells the samples apart
  *   azsp_replay_gather                UniformReplay.sample + batch tensors + random transformation (core/replay.py:72-83,
  *                                      core/pipeline.py:636-643)
  *   azsp_dihedral                     apply_horizontal_flip / apply_vertical_flip / apply_rotation
@@ -334,6 +337,30 @@ int azsp_harvest_extra(void* engine, int32_t* extra_host);
  * (each game keeps the threshold / tag it started with; resign_disabled is drawn per game only while the threshold is > -1,
  * core/pipeline.py:244-246).  resign_threshold <= -1 disables resignation (the learner's warm-up value, core/pipeline.py:449-459). */
 int azsp_set_actor_state(void* engine, double resign_threshold, int32_t training_steps);
+
+/* Per-game simulation budgets (no counterpart in the reference: opt-in).  budgets_dev int32[G]: the simulations per move of every
+ * slot, 0 = the engine's num_simulations.  The node pool and the pb_c tables are sized from num_simulations, so that is the upper
+ * limit: the kernel clamps a value into [1, num_simulations] (callers refuse out-of-range values before the upload).  A slot's search
+ * ends when its root has budget (+ num_parallel in parallel mode) visits, the rule azsp_create applies to num_simulations
+ * (core/mcts_v2.py:378 / :568).  Values are sticky until the next call; a game that is mid-search uses the new value at its next
+ * budget check.  One launch over all slots, nothing is synchronised. */
+int azsp_set_budgets(void* engine, const int32_t* budgets_dev, void* stream);
+
+/* Playout-cap randomisation for actor mode (no counterpart in the reference: opt-in, off by default).  At the start of every move a
+ * game draws one uniform u from its own Philox stream (key seed + rank; counters slot, game uid, (ply << 12) | 0xFFE, 0x2000 -- a
+ * counter word neither the Dirichlet nor the move-sampling stream uses).  u < full_prob: a FULL move -- the slot's budget, root noise
+ * as configured.  Otherwise a FAST move -- fast_simulations (+ num_parallel), no root noise.  The tree is reused across both kinds as
+ * reuse_tree says; warm-up temperature, resignation and everything else are untouched.  Fast moves are recorded like full ones (game
+ * length, moves and sample rows keep meaning the whole game); the class travels with the sample (azsp_harvest_search_class).
+ * fast_simulations == 0 turns the cap off.  AZSP_EINVAL in drop-in mode (stop_after_move), for fast_simulations outside
+ * 0..num_simulations and for full_prob outside [0, 1].  Takes effect for the moves that start after this call.  (As with
+ * num_simulations = 1, fast_simulations = 1 at num_parallel = 1 leaves a fresh root without a visited child to play.) */
+int azsp_set_playout_cap(void* engine, int32_t fast_simulations, double full_prob);
+
+/* Optional output of azsp_harvest next to azsp_harvest_moves (no counterpart in the reference: opt-in): class_dev
+ * uint8[sample_capacity] receives 1 for every harvested sample whose move was a full search and 0 for a fast move of the playout
+ * cap; with the cap off every byte is 1.  NULL (the default) disables it.  The buffer must stay valid for every later harvest. */
+int azsp_harvest_search_class(void* engine, uint8_t* class_dev);
 
 /* counters_host uint64[16]: simulations, best_child calls, backup edges, leaves, duplicate leaves, terminal hits,
  * moves, games, root evaluations, nodes created, game-rounds, buffer stalls, speculative record prefetches of the select phase and

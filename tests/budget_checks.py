@@ -1,0 +1,409 @@
+"""Shared drivers of the per-game simulation budgets (azsp_set_budgets: BatchSearch.search(num_simulations=...), uct_search_many with a
+list) and of the playout-cap actor (azsp_set_playout_cap / azsp_harvest_search_class: SelfPlayActor(playout_cap=...)).  The same
+functions run on the host twin (CPU tier) and on the device (`-m gpu`).  Every comparison is exact; the yardstick is always the
+uniform-budget engine, which the goldens and the oracle pin."""
+import warnings
+
+import numpy as np
+import pytest
+import torch
+
+import batch_search_checks as bc
+import dropin_checks as dc
+import engine_util as eu
+from alpha_zero_amd import _abi
+from alpha_zero_amd.core.batch_search import BatchSearch
+from alpha_zero_amd.core.network import AlphaZeroNet
+from alpha_zero_amd.core.pipeline import SelfPlayActor
+from arena_checks import SynthDeviceEvaluator
+from synth_eval import eval_batch, make_eval_func
+
+SIMS, BUDGETS, GAMES = 24, (6, 13, 24), 40  # G = 40 crosses a 32-game range boundary; 6 / 13 / 24: below, between and at the engine's number
+FAST = 6
+
+
+# ---------------------------------------------------------------------------------------------------
+# 1. mixed budgets == uniform searches
+# ---------------------------------------------------------------------------------------------------
+def _batch(kind, game, n, P, sims, G=GAMES):
+    b, dev = eu.backend(kind)
+    return BatchSearch(game, n, G, sims, num_parallel=P, binding=b, device=dev)
+
+
+def _evaluator(route, A):
+    return SynthDeviceEvaluator(A, 2.0) if route == "resident" else make_eval_func(A)
+
+
+def _rows(bs):
+    """slot -> (pi bytes, child_N bytes, root_Q bytes) of the finished searches, and slot -> root_N."""
+    pi, cn, rq = bs.results().cpu()
+    st, _ = bs.eng.status()
+    return ({int(s): (pi[r].tobytes(), cn[r].tobytes(), rq[r].tobytes(), int(cn[r].argmax())) for r, s in enumerate(bs.slots)},
+            {int(s): int(st[s, _abi.STC_ROOT_N]) for s in bs.slots})
+
+
+def _commit_most_visited(bs, rows):
+    """Commits every active slot's most visited move; returns slot -> root_N of the sub-tree it kept (slots that kept none are absent)."""
+    bs.commit([rows[int(s)][3] for s in bs.slots])
+    st, _ = bs.eng.status()
+    return {int(s): int(st[s, _abi.STC_ROOT_N]) for s in bs.slots}
+
+
+def check_mixed_budgets_equal_uniform_searches(kind, game="go", n=5, P=1):
+    """One position pool in a BatchSearch built at 24 simulations, searched with per-slot budgets cycling through {6, 13, 24}, by the
+    host-callback loop and by the resident loop: pi, child_N and root_Q of every slot equal, bit for bit, the slot of a BatchSearch
+    built and searched uniformly at that slot's budget.
+
+    Then two more moves with tree reuse and other budgets.  A uniform engine cannot change its budget between moves, so a slot whose
+    budget changes has no uniform twin from then on (its tree is the one of its old budget, its search the one of its new budget).
+    What is compared exactly on those moves: the slots whose budget has NOT changed still equal their uniform twin (which went on with
+    tree reuse) while their neighbours' budgets changed around them, and the two loops agree bit for bit on every slot.  For the slots
+    whose budget did change, the rule itself is checked on the root visit counts: a kept root that already has its new budget's visits
+    is done at once and keeps its count; any other stops in the first round that reaches the budget (P = 1: exactly at the budget).
+
+    Last, the positions are loaded again and search(num_simulations=None) equals the fresh uniform search at 24."""
+    A = n * n + (1 if game == "go" else 0)
+    extra = P if P > 1 else 0  # the reference's parallel search stops at num_simulations + num_parallel root visits (mcts_v2.py:568)
+    boards, hist, pos = bc.positions(game, n, 8, GAMES)
+    # slot s starts at BUDGETS[s % 3]; by (s // 3) % 3 it keeps that budget, changes it at the second and again at the third move, or
+    # changes it at the third move only -- so every (old, new) pair of budgets occurs, upwards and downwards
+    cls = np.array([(s // 3) % 3 for s in range(GAMES)])
+    slot_b = {0: np.array([BUDGETS[s % 3] for s in range(GAMES)])}
+    slot_b[1] = np.array([BUDGETS[(s + (cls[s] == 1)) % 3] for s in range(GAMES)])
+    slot_b[2] = np.array([BUDGETS[(s + (0, 2, 1)[cls[s]]) % 3] for s in range(GAMES)])
+    mixed = {route: _batch(kind, game, n, P, SIMS) for route in ("callback", "resident")}
+    twins = {b: _batch(kind, game, n, P, b) for b in BUDGETS}
+    evs = {route: _evaluator(route, A) for route in mixed}
+    ef = make_eval_func(A)
+    for bs in list(mixed.values()) + list(twins.values()):
+        assert np.all(bs.load(boards, hist, pos) == _abi.SS_OK)
+    fresh24 = None
+    unchanged = set(range(GAMES))
+    for move in range(3):
+        got = {}
+        for route, bs in mixed.items():
+            st = bs.eng.status()[0]
+            before = {int(s): int(st[s, _abi.STC_ROOT_N]) for s in bs.slots} if move else {}
+            bs.search(evs[route], num_simulations=slot_b[move][bs.slots])
+            got[route] = _rows(bs)
+            for s, after in got[route][1].items():
+                budget, had = int(slot_b[move][s]) + extra, before.get(s, 0)
+                if had >= budget:
+                    assert after == had, (move, route, s, had, budget, after)
+                else:
+                    assert budget <= after < budget + max(1, 2 * P if P > 1 else 1), (move, route, s, had, budget, after)
+        assert got["callback"] == got["resident"], move
+        assert evs["resident"].calls > 0
+        rows = got["callback"][0]
+        twin_rows = {}
+        for b, bs in twins.items():
+            bs.search(ef)
+            twin_rows[b] = _rows(bs)[0]
+        if move == 0:
+            fresh24 = twin_rows[24]
+            assert len(rows) == GAMES and len({slot_b[0][s] for s in rows}) == 3
+        unchanged = {s for s in unchanged if s in rows and slot_b[move][s] == slot_b[0][s]}
+        assert len(unchanged) >= (GAMES if move == 0 else 6), (move, sorted(unchanged))  # the comparison below is not empty
+        for s in sorted(unchanged):
+            assert rows[s] == twin_rows[int(slot_b[0][s])][s], (move, s, int(slot_b[0][s]))
+        if move == 0:  # a smaller budget is another search, not a prefix that happens to agree: the comparison can fail
+            assert any(rows[s][1] != twin_rows[24][s][1] for s in rows if slot_b[0][s] != 24)
+        for bs in mixed.values():
+            _commit_most_visited(bs, rows)
+        for b, bs in twins.items():
+            _commit_most_visited(bs, twin_rows[b])
+    bs = mixed["callback"]
+    assert np.all(bs.load(boards, hist, pos) == _abi.SS_OK)
+    bs.search(evs["callback"], num_simulations=None)  # undoes the budgets the calls above left in the slots
+    assert _rows(bs)[0] == fresh24
+    for bs in list(mixed.values()) + list(twins.values()):
+        bs.close()
+
+
+# ---------------------------------------------------------------------------------------------------
+# 2. refusals
+# ---------------------------------------------------------------------------------------------------
+def check_refusals(kind):
+    """Budgets of 0, 25 or negative and a sequence of the wrong length raise ValueError before anything reaches the engine;
+    azsp_set_playout_cap returns AZSP_EINVAL in drop-in mode, for fast_simulations outside 1..num_simulations and for full_prob
+    outside [0, 1]."""
+    from alpha_zero_amd.core.engine import Engine, EngineConfig
+    from alpha_zero_amd.core.mcts_v2 import uct_search_many
+
+    EINVAL = -1
+    boards, hist, pos = bc.positions("go", 5, 8, 4)
+    bs = _batch(kind, "go", 5, 1, SIMS, G=4)
+    assert np.all(bs.load(boards, hist, pos) == _abi.SS_OK)
+    ef = make_eval_func(26)
+
+    def untouched(*a, **k):
+        raise AssertionError("the engine must not be reached")
+
+    real = bs.eng.set_budgets, bs.eng.begin_moves
+    bs.eng.set_budgets = bs.eng.begin_moves = untouched
+    for bad in (0, 25, -3, [6, 6, 0, 6], [6, 25, 6, 6], [6, 6, 6, -1], [6, 6, 6], [6] * 5, 6.5, [[6, 6, 6, 6]]):
+        with pytest.raises(ValueError, match="num_simulations"):
+            bs.search(ef, num_simulations=bad)
+    bs.eng.set_budgets, bs.eng.begin_moves = real
+    with pytest.raises(ValueError):
+        bs.eng.set_budgets([6, 6, 6])
+    with pytest.raises(ValueError):
+        bs.eng.set_budgets([6, 6, 6, 25])
+    bs.search(ef, num_simulations=[6, 13, 24, 2])  # the whole range is accepted
+    assert [int(x) for x in bs.eng.status()[0][:, _abi.STC_ROOT_N]] == [6, 13, 24, 2]
+    assert bs.eng.b.dll.azsp_set_playout_cap(bs.eng.h, 6, 0.5) == EINVAL  # drop-in mode
+    bs.close()
+    envs = [dc.make_env(kind, "go", 5) for _ in range(2)]
+    for bad in ([8, 0], [8], [8, 8, 8], [8.0, 8.0]):
+        with pytest.raises(ValueError):
+            uct_search_many(envs, ef, None, 19652.0, 1.25, bad)
+    b, dev = eu.backend(kind)
+    eng = Engine(b, EngineConfig(game="go", board_size=5, num_games=2, num_parallel=1, num_simulations=SIMS), device=dev)
+    cap = lambda fast, prob: b.dll.azsp_set_playout_cap(eng.h, fast, prob)  # noqa: E731
+    assert [cap(-1, 0.5), cap(SIMS + 1, 0.5), cap(6, -0.01), cap(6, 1.01), cap(6, float("nan"))] == [EINVAL] * 5
+    assert [cap(1, 0.0), cap(SIMS, 1.0), cap(6, 0.25), cap(0, 1.0)] == [0] * 4
+    with pytest.raises(_abi.AzspError):
+        eng.set_playout_cap(SIMS + 1, 0.5)
+    eng.close()
+    net = AlphaZeroNet((17, 5, 5), 26, 1, 8, 8)
+    for bad in ((0, 0.5), (SIMS + 1, 0.5), (6, 1.5), (6.0, 0.5)):
+        with pytest.raises(ValueError, match="playout_cap"):
+            _actor(kind, 1, net=net, G=2, playout_cap=bad)
+
+
+# ---------------------------------------------------------------------------------------------------
+# 3. uct_search_many with a list
+# ---------------------------------------------------------------------------------------------------
+def check_uct_search_many_with_a_list(kind, P=1):
+    """uct_search_many / parallel_uct_search_many with one num_simulations per env equal, env by env, a one-game engine built at that
+    env's number on that env's position alone (the comparison of check_batch_search_object): pi, child_N through the move, root Q and
+    child Q, over two moves with the batch handle."""
+    from alpha_zero_amd.core.mcts_v2 import parallel_uct_search_many, uct_search_many
+
+    n, sims = 5, [6, 24, 13, 24, 6, 13, 2]
+    ef = make_eval_func(26)
+    rng = np.random.Generator(np.random.PCG64(11))
+    envs = [dc.make_env(kind, "go", n) for _ in sims]
+    for k, env in enumerate(envs):
+        for _ in range(k):
+            legal = np.flatnonzero(env.legal_actions[: n * n])
+            env.step(int(legal[rng.integers(len(legal))]))
+    ones = []
+    for env, s in zip(envs, sims):
+        one = bc.make_engine(kind, "go", n, 8, 1, P=P, sims=s)
+        board, hist, row = bc.env_position(env)
+        bc.load_one_by_one(one, board[None], hist[None], row[None])
+        ones.append(one)
+    handle = None
+    for move in range(2):
+        args = (envs, ef, handle, 19652.0, 1.25, sims)
+        moves, pis, rqs, cqs, handle = (uct_search_many(*args, deterministic=True) if P == 1 else
+                                        parallel_uct_search_many(*args, P, deterministic=True))
+        for k, one in enumerate(ones):
+            one.begin_move(None, warm_up=0)
+            bc.run_until_done([one])
+            gpi, gcn, _ = one.get_search(0, 0)
+            assert gpi.tobytes() == pis[k].tobytes() and int(gcn.argmax()) == moves[k], (move, k)
+            one.commit_move(np.array([moves[k]], dtype=np.int32))
+            st, q = one.status()
+            assert q[0, _abi.STQ_ROOT_Q] == rqs[k] and q[0, _abi.STQ_CHILD_Q] == cqs[k], (move, k)
+            assert (st[0, _abi.STC_STATUS] == _abi.ST_SEARCH) == handle.reusable(envs[k]), (move, k)
+            envs[k].step(int(moves[k]))
+    for one in ones:
+        one.close()
+
+
+# ---------------------------------------------------------------------------------------------------
+# 4. / 5. the playout-cap actor
+# ---------------------------------------------------------------------------------------------------
+class SynthActor(SelfPlayActor):
+    """A SelfPlayActor whose forward is the synthetic evaluator on the leaf rows the engine asked for: exact on every backend."""
+
+    def _forward(self):
+        e = self.engine
+        rows = np.flatnonzero(e.valid.cpu().numpy())
+        if len(rows):
+            p, v = eval_batch(eu.decode_features(e)[rows], e.A)
+            idx = torch.from_numpy(rows).to(e.priors.device)
+            e.priors.index_copy_(0, idx, torch.from_numpy(p).to(e.priors.device))
+            e.values.index_copy_(0, idx, torch.from_numpy(v).to(e.values.device))
+
+
+MAX_STEPS = 14  # short games (go.py:176-178 ends a game at max_steps): every slot plays ONE game (stop_at_game_end), <= 14 samples
+
+
+def _actor(kind, P, game="go", n=5, G=GAMES, sims=SIMS, net=None, seed=5, **kw):
+    b, dev = eu.backend(kind)
+    A = n * n + (1 if game == "go" else 0)
+    net = net or AlphaZeroNet((17, n, n), A, 1, 8, 8, gomoku=(game != "go"))
+    ekw = dict(log_moves=True, log_capacity=MAX_STEPS if game == "go" else n * n, stop_at_game_end=True)
+    if game == "go":
+        ekw["max_steps"] = MAX_STEPS
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)  # (the tiny network has no hand-written kernels; its forward is never run)
+        return SynthActor(net, game=game, board_size=n, num_games=G, num_simulations=sims, num_parallel=P, warm_up_steps=4, seed=seed, device=dev,
+                          net_dtype=torch.float32, use_graph=False, binding=b, tiled_features=False, engine_kw=ekw, **kw)
+
+
+def _play_out(actor):
+    """Rounds until every slot's one game is over; returns the engine's counters."""
+    for _ in range(400):
+        actor.run_rounds(8)
+        if np.all(actor.engine.status()[0][:, _abi.STC_STATUS] == _abi.ST_IDLE):
+            return actor.counters()
+    raise AssertionError("the games did not finish")
+
+
+def _drain_tensors(actor):
+    """Every finished game through harvest_tensors(): (states, pi, z, games with START rebased, full flags), concatenated."""
+    parts, base = [], 0
+    while True:
+        st, pi, z, games = actor.harvest_tensors()
+        if len(games) == 0:
+            break
+        full = actor.last_harvest_full
+        assert full.dtype == torch.bool and full.device.type == st.device.type and full.shape == z.shape
+        games = games.copy()
+        games[:, _abi.GR_START] += base
+        base += len(z)
+        parts.append((st.cpu().numpy().copy(), pi.cpu().numpy().copy(), z.cpu().numpy().copy(), games, full.cpu().numpy().copy()))
+    assert parts
+    return tuple(np.concatenate([p[i] for p in parts]) for i in range(5))
+
+
+def _drain_engine(actor):
+    """Every finished game through Engine.harvest: (states, pi, z, games with START rebased, moves, class bytes), concatenated."""
+    parts, base = [], 0
+    while True:
+        got = actor.engine.harvest(with_moves=True, with_class=True)
+        if len(got[3]) == 0:
+            break
+        games = got[3].copy()
+        games[:, _abi.GR_START] += base
+        base += len(got[2])
+        assert got[5].dtype == torch.uint8 and got[5].shape == got[2].shape
+        parts.append(tuple(t.cpu().numpy().copy() for t in got[:3]) + (games, got[4].cpu().numpy().copy(), got[5].cpu().numpy().copy()))
+    assert parts
+    return tuple(np.concatenate([p[i] for p in parts]) for i in range(6))
+
+
+def _drain_games(actor):
+    out = []
+    while True:
+        got = actor.harvest(with_moves=True)
+        if not got:
+            return out
+        out += got
+
+
+def _same_tensors(a, b):
+    return all(x.tobytes() == y.tobytes() and x.shape == y.shape for x, y in zip(a, b))
+
+
+def check_cap_at_the_ends(kind, game="go", n=5, P=1):
+    """full_prob = 1: samples, pi, z, game rows, harvested moves and counters are those of an actor without the cap, and every class
+    byte is 1.  full_prob = 0 with 6 fast simulations: samples, pi, z, game rows and moves are those of an actor built with
+    num_simulations = 6 and root_noise = False, every class byte is 0, and harvest() yields empty sequences with the true
+    game_length."""
+    plain, capped = _actor(kind, P, game, n), _actor(kind, P, game, n, playout_cap=(FAST, 1.0))
+    cp, cc = _play_out(plain), _play_out(capped)
+    assert cp == cc and cp["moves"] >= GAMES
+    tp, tc = _drain_engine(plain), _drain_engine(capped)
+    assert _same_tensors(tp[:5], tc[:5]) and (tc[5] == 1).all() and (tp[5] == 1).all() and len(tc[3]) == GAMES
+    small, fast = _actor(kind, P, game, n, sims=FAST, root_noise=False), _actor(kind, P, game, n, playout_cap=(FAST, 0.0))
+    _play_out(small), _play_out(fast)
+    ts, tf = _drain_engine(small), _drain_engine(fast)
+    assert _same_tensors(ts[:5], tf[:5]) and (tf[5] == 0).all() and (ts[5] == 1).all() and len(tf[3]) == GAMES
+    assert not _same_tensors(ts[:3], tp[:3])  # (6 simulations without noise play other games than 24 with noise)
+    again = _actor(kind, P, game, n, playout_cap=(FAST, 0.0))
+    _play_out(again)
+    got = _drain_games(again)
+    assert len(got) == GAMES
+    for row, (seq, stats, moves) in zip(tf[3][np.argsort(tf[3][:, _abi.GR_START])], got):
+        mv = eu.samples_of(row, tf[4])
+        assert seq == [] and stats["num_full_samples"] == 0 and stats["game_length"] == int(row[_abi.GR_LENGTH]) == len(mv) > 0
+        assert moves == [int(m) for m in mv if m >= 0]
+
+
+# Philox4x32-10 (Salmon et al., SC'11), the engine's counter-based generator, restated independently
+def philox4x32_10(key, c0, c1, c2, c3):
+    M = 0xFFFFFFFF
+    c, k0, k1 = [c0 & M, c1 & M, c2 & M, c3 & M], key & M, (key >> 32) & M
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c[0], 0xCD9E8D57 * c[2]
+        c = [(p1 >> 32) ^ c[1] ^ k0, p1 & M, (p0 >> 32) ^ c[3] ^ k1, p0 & M]
+        k0, k1 = (k0 + 0x9E3779B9) & M, (k1 + 0xBB67AE85) & M
+    return c
+
+
+def class_draw(seed, rank, slot, uid, ply):
+    """The uniform a game draws at the start of the move at `ply`: 53 bits of the first two output words, in [0, 1)."""
+    r = philox4x32_10(seed + rank, slot, uid, (ply << 12) | 0xFFE, 0x2000)
+    return (((r[0] << 32) | r[1]) >> 11) * (1.0 / 9007199254740992.0)
+
+
+def check_cap_in_the_middle(kind, P=1, seed=5, rank=3):
+    """full_prob = 0.5 with logged moves: each sample's class is the draw recomputed here (an independent Philox4x32-10 keyed by seed +
+    rank, with slot, game uid and the sample's ply as counters); the logged root visit count of every move is at least its class's
+    budget; both classes occur; the sequences of harvest() are exactly the class-1 rows of harvest_tensors(); a second actor with the
+    same seed reproduces everything."""
+    prob = 0.5
+    a, b = (_actor(kind, P, seed=seed, rank=rank, playout_cap=(FAST, prob)) for _ in range(2))
+    ca, cb = _play_out(a), _play_out(b)
+    assert ca == cb
+    logged = {}
+    for slot in range(GAMES):
+        for ply in range(MAX_STEPS):
+            logged[(slot, ply)] = a.engine.get_search(slot, ply)[2][_abi.SQ_ROOT_N]
+    states, pi, z, games, full = _drain_tensors(a)
+    assert len(games) == GAMES and len(z) >= 40
+    extra = P if P > 1 else 0
+    for row in games:
+        s0, ln, slot, uid = (int(row[c]) for c in (_abi.GR_START, _abi.GR_LENGTH, _abi.GR_SLOT, _abi.GR_UID))
+        assert 0 < ln <= MAX_STEPS
+        for ply in range(ln):
+            want = class_draw(seed, rank, slot, uid, ply) < prob
+            assert bool(full[s0 + ply]) == want, (slot, uid, ply)
+            assert logged[(slot, ply)] >= (SIMS if want else FAST) + extra, (slot, ply, want, logged[(slot, ply)])
+    assert full.any() and not full.all()
+    got = _drain_games(b)
+    assert len(got) == GAMES
+    by_start = games[np.argsort(games[:, _abi.GR_START])]
+    # both drains hand the games out in the same order: same seed, same call sequence (azsp_harvest is deterministic)
+    for row, (seq, stats, moves) in zip(by_start, got):
+        st, pp, zz, ff = eu.samples_of(row, states, pi, z, full)
+        assert stats["game_length"] == len(ff) and stats["num_full_samples"] == len(seq) == int(ff.sum()) and len(moves) <= len(ff)
+        assert np.array_equal(np.stack([t.state for t in seq]) if seq else st[:0], st[ff])
+        assert np.array_equal(np.stack([t.pi_prob for t in seq]) if seq else pp[:0].astype(np.float64), pp[ff].astype(np.float64))
+        assert [t.value for t in seq] == [float(v) for v in zz[ff]]
+
+
+# ---------------------------------------------------------------------------------------------------
+# 6. replay
+# ---------------------------------------------------------------------------------------------------
+def check_replay_keeps_the_masked_rows(kind):
+    """add_harvest(..., keep=mask) stores the kept rows in order and counts games as before."""
+    from alpha_zero_amd.core.replay import DeviceReplay
+
+    b, dev = eu.backend(kind)
+    rng = np.random.Generator(np.random.PCG64(2))
+    n = 23
+    states = torch.from_numpy(rng.integers(0, 2, size=(n, 17, 5, 5)).astype(np.int8)).to(dev)
+    pi = torch.from_numpy(rng.random((n, 26)).astype(np.float32)).to(dev)
+    z = torch.from_numpy(rng.choice([-1.0, 0.0, 1.0], size=n).astype(np.float32)).to(dev)
+    games = np.zeros((4, _abi.GR_COUNT), dtype=np.int32)
+    keep = torch.from_numpy(rng.random(n) < 0.4).to(dev)
+    k = keep.cpu().numpy()
+    assert 0 < k.sum() < n
+    rep = DeviceReplay(64, np.random.RandomState(1), 5, 26, device=dev, binding=b)
+    rep.add_harvest(states, pi, z, games, keep=keep)
+    m = int(k.sum())
+    assert (rep.num_samples_added, rep.num_games_added, rep.size) == (m, 4, m)
+    assert np.array_equal(rep.states[:m].cpu().numpy(), states.cpu().numpy()[k]) and np.array_equal(rep.pi[:m].cpu().numpy(), pi.cpu().numpy()[k])
+    assert np.array_equal(rep.z[:m].cpu().numpy(), z.cpu().numpy()[k])
+    rep.add_harvest(states, pi, z, games)  # without a mask: everything, as before
+    assert (rep.num_samples_added, rep.num_games_added) == (m + n, 8) and np.array_equal(rep.z[m:m + n].cpu().numpy(), z.cpu().numpy())
+    rep.add_harvest(states, pi, z, games, keep=np.zeros(n, dtype=bool))  # nothing kept: the games still count
+    assert (rep.num_samples_added, rep.num_games_added) == (m + n, 12)
+    with pytest.raises(ValueError, match="keep"):
+        rep.add_harvest(states, pi, z, games, keep=keep[:-1])
