@@ -28,6 +28,7 @@ PS_ACTION, PS_TO_PLAY, PS_STEPS, PS_KO, PS_LAST_PASS, PS_CAPS_BLACK, PS_CAPS_WHI
 PSA_KEEP, PSA_LOAD, PSA_IDLE = 0, 1, 2
 SS_OK, SS_INVALID, SS_GAME_OVER = 0, 1, 2
 BM_SKIP = -2
+SYM_OFF, SYM_RANDOM = -1, -2  # azsp_set_leaf_symmetry modes next to the ops 0..7
 
 SYMBOLS = [
     "azsp_create", "azsp_destroy", "azsp_last_error", "azsp_geometry", "azsp_set_tables", "azsp_set_injection",
@@ -36,6 +37,7 @@ SYMBOLS = [
     "azsp_conv3x3_tiled", "azsp_tile_layout", "azsp_tiled_bytes", "azsp_stem_tiled", "azsp_head_tiled", "azsp_replay_gather", "azsp_rng_probe", "azsp_harvest_moves", "azsp_fc_heads", "azsp_harvest_extra", "azsp_set_actor_state", "azsp_resblock_tiled", "azsp_select_range", "azsp_expand_backup_range", "azsp_split_bytes", "azsp_split_layout", "azsp_conv3x3_split", "azsp_split_features", "azsp_stem_split", "azsp_head_split", "azsp_conv3x3_tiled_f16", "azsp_stem_tiled_f16", "azsp_head_tiled_f16", "azsp_fc_heads_f16", "azsp_split_range_status", "azsp_stem_split_exact", "azsp_split_range_read", "azsp_resblock_split", "azsp_dropin_step", "azsp_small_batch_waves",
     "azsp_set_states", "azsp_begin_moves", "azsp_read_searches",
     "azsp_set_budgets", "azsp_set_playout_cap", "azsp_harvest_search_class",
+    "azsp_set_leaf_symmetry", "azsp_leaf_symmetries",
 ]
 
 COUNTER_NAMES = ["sims", "node_visits", "backup_edges", "leaves", "dup_leaves", "terminal_hits", "moves", "games", "root_evals",
@@ -91,6 +93,7 @@ class Binding:
             "azsp_fc_heads": [V, V, V, V, I, V, V, I, V, C.c_float, V, V, C.c_int64, I, I, V],
             "azsp_replay_gather": [V, V, V, V, I, I, I, I, I, I, V, V, V, V], "azsp_rng_probe": [V, I, I, V, V, V], "azsp_harvest_moves": [V, V], "azsp_harvest_extra": [V, V], "azsp_set_actor_state": [V, C.c_double, I],
             "azsp_set_budgets": [V, V, V], "azsp_set_playout_cap": [V, I, C.c_double], "azsp_harvest_search_class": [V, V],
+            "azsp_set_leaf_symmetry": [V, I], "azsp_leaf_symmetries": [V, V, V],
         }
         for k in ("azsp_conv3x3_tiled", "azsp_stem_tiled", "azsp_head_tiled", "azsp_fc_heads"):  # the f16 variants take the same arguments
             sig[k + "_f16"] = sig[k]

@@ -21,16 +21,18 @@ from .engine import Engine, EngineConfig
 
 
 def dropin_engine(game, board_size, num_games, num_simulations, num_parallel, c_puct_base, c_puct_init, root_noise, komi=7.5, max_steps=0,
-                  num_to_win=5, num_stack=8, binding=None, device=None):
+                  num_to_win=5, num_stack=8, binding=None, device=None, leaf_symmetry=None):
     """The engine of a drop-in search, `uct_search`'s with one game and a BatchSearch's with `capacity`: it stops after every move
-    (`stop_after_move`), hands out int8 observation planes and logs no moves.  Without a `binding` it runs the product library on the GPU."""
+    (`stop_after_move`), hands out int8 observation planes and logs no moves.  Without a `binding` it runs the product library on the GPU.
+    leaf_symmetry: EngineConfig.leaf_symmetry (None = off)."""
     if binding is None:
         from .. import _lib
 
         binding, device = _lib.load(require_gpu=True), device or "cuda"
     cfg = EngineConfig(game=game, board_size=board_size, num_games=num_games, num_parallel=num_parallel, num_simulations=num_simulations,
                        c_puct_base=c_puct_base, c_puct_init=c_puct_init, root_noise=root_noise, komi=komi, max_steps=max_steps or 0,
-                       num_to_win=num_to_win, num_stack=num_stack, stop_after_move=True, feature_dtype=_abi.FEAT_I8, log_moves=False)
+                       num_to_win=num_to_win, num_stack=num_stack, stop_after_move=True, feature_dtype=_abi.FEAT_I8, log_moves=False,
+                       leaf_symmetry=leaf_symmetry)
     return Engine(binding, cfg, device=device)
 
 
@@ -221,14 +223,17 @@ class BatchSearch:
     """
 
     def __init__(self, game, board_size, capacity, num_simulations, num_parallel=1, c_puct_base=19652.0, c_puct_init=1.25, root_noise=False,
-                 komi=7.5, max_steps=0, num_to_win=5, num_stack=8, binding=None, device=None):
+                 komi=7.5, max_steps=0, num_to_win=5, num_stack=8, binding=None, device=None, leaf_symmetry=None):
+        """leaf_symmetry: None, "random" or an op 0..7 (Engine.set_leaf_symmetry; the reference search has none): `eval_func` -- host
+        callback or resident evaluator -- is handed every leaf position under that board symmetry ("random": one drawn per feature row)
+        and the engine maps its priors back; pi, child_N and Q are in the true orientation."""
         if capacity < 1:
             raise ValueError(f"capacity must be at least 1, got {capacity}")
         check_num_simulations(num_simulations)
         self.game, self.capacity, self.num_simulations, self.num_parallel = game, int(capacity), int(num_simulations), int(num_parallel)
         self.key = _key(game, board_size, komi, max_steps, num_to_win, num_stack)
         self.eng = dropin_engine(game, board_size, self.capacity, num_simulations, num_parallel, c_puct_base, c_puct_init, root_noise, komi,
-                                 max_steps, num_to_win, num_stack, binding, device)
+                                 max_steps, num_to_win, num_stack, binding, device, leaf_symmetry)
         self.slots = np.zeros(0, dtype=np.int64)  # the active slots (a position is loaded, or a sub-tree was kept), ascending
         self._status = np.full(self.capacity, _abi.ST_IDLE, dtype=np.int32)  # host mirror of the slots' status after load / search / commit
         self._budgets_set = False  # an earlier search left per-slot budgets in the engine (search(num_simulations=...))

@@ -54,6 +54,19 @@ class EngineConfig:
     seed: int = 1
     rank: int = 0
     device_index: int = 0
+    leaf_symmetry: object = None     # None | "random" | 0..7: the board symmetry leaf positions are evaluated under (Engine.set_leaf_symmetry)
+
+
+def leaf_symmetry_mode(mode):
+    """The azsp_set_leaf_symmetry argument of a `leaf_symmetry` value: None = off, "random" = a fresh op per feature row, an integer
+    0..7 = that dihedral op for every row.  Anything else raises ValueError naming these."""
+    if mode is None:
+        return _abi.SYM_OFF
+    if isinstance(mode, str) and mode == "random":
+        return _abi.SYM_RANDOM
+    if not isinstance(mode, (bool, str)) and isinstance(mode, (int, np.integer)) and 0 <= int(mode) <= 7:
+        return int(mode)
+    raise ValueError(f'leaf_symmetry must be None (off), "random" or an integer op 0..7, got {mode!r}')
 
 
 MAX_NUM_STACK = 8  # the engine's history ring holds 8 boards (include/azsp.h AzspConfig.num_stack)
@@ -83,6 +96,7 @@ class Engine:
         self.b, self.cfg, self.device = binding, cfg, torch.device(device)
         self.on_launch = None
         check_num_stack(cfg.num_stack)
+        sym = leaf_symmetry_mode(cfg.leaf_symmetry)
         c = AzspConfig()
         c.game = _abi.GAME_GO if cfg.game == "go" else _abi.GAME_GOMOKU
         c.board_size, c.num_games, c.num_parallel, c.num_simulations = cfg.board_size, cfg.num_games, cfg.num_parallel, cfg.num_simulations
@@ -123,6 +137,8 @@ class Engine:
         self.values = torch.zeros((self.rows,), dtype=torch.float32, device=self.device)
         self._actions = torch.zeros((self.G,), dtype=torch.int32, device=self.device)
         self._harvest_bufs = None
+        if sym != _abi.SYM_OFF:
+            self.set_leaf_symmetry(cfg.leaf_symmetry)  # before the first select: the first root evaluation is transformed too
 
     # -- plumbing ---------------------------------------------------------------------------------
     def _ck(self, rc, what):
@@ -321,6 +337,20 @@ class Engine:
         on is a full search (the slot's budget, root noise as configured) with probability `full_prob`, else a fast one of
         `fast_simulations` (1..num_simulations) without root noise.  fast_simulations = 0 turns the cap off."""
         self._ck(self.b.dll.azsp_set_playout_cap(self.h, int(fast_simulations), C.c_double(float(full_prob))), "azsp_set_playout_cap")
+
+    def set_leaf_symmetry(self, mode):
+        """Leaf symmetry (azsp_set_leaf_symmetry; the reference search has none): None = off, "random" = every feature row is written
+        under a dihedral op drawn for it, an integer 0..7 = under that op; the row's priors are mapped back when its node is expanded, the
+        value is used as it is.  Holds for the rows selected from now on; rows in flight keep their op.  Samples, logs and env_step
+        observations stay in the true orientation."""
+        self._ck(self.b.dll.azsp_set_leaf_symmetry(self.h, leaf_symmetry_mode(mode)), "azsp_set_leaf_symmetry")
+
+    def leaf_symmetries(self):
+        """uint8[rows] on the engine's device: the op each feature row of the last select was written with (azsp_leaf_symmetries; 0 for
+        rows it did not write and with the mode off).  Nothing is synchronised."""
+        ops = torch.empty((self.rows,), dtype=torch.uint8, device=self.device)
+        self._ck(self.b.dll.azsp_leaf_symmetries(self.h, ops.data_ptr(), self._stream()), "azsp_leaf_symmetries")
+        return ops
 
     # -- samples ----------------------------------------------------------------------------------------
     def harvest(self, sample_capacity=None, max_games=None, with_moves=False, with_class=False):

@@ -18,6 +18,7 @@
 // root), compiled with -ffp-contract=off, so visit counts match the reference exactly.
 #pragma once
 #include "az_rules.h"
+#include "az_dihedral.h"
 #include <math.h>
 
 #define AZ_MAXP 32        // max leaves per game per round (num_parallel)
@@ -31,6 +32,9 @@
 // stg_meta: bit 0 = black to move, AZ_META_FAST = the sample's move was a fast search of the playout cap
 #define AZ_META_BLACK 1
 #define AZ_META_FAST 2
+// AzCfg::leaf_sym (azsp_set_leaf_symmetry): 0..7 = that dihedral op for every row, or one of these two
+#define AZ_SYM_OFF (-1)
+#define AZ_SYM_RANDOM (-2)
 
 enum { AZS_NEED_ROOT = 0, AZS_SEARCH = 1, AZS_MOVE_DONE = 2, AZS_IDLE = 3, AZS_WAIT_BUF = 4 };
 enum { AZ_ERR_NODES = 1, AZ_ERR_SAMPLE = 4, AZ_ERR_STAGE = 8 };  // bit 2 (tree depth) retired: deep paths walk parent links
@@ -62,6 +66,10 @@ struct AzCfg {
     // fast one of cap_fast simulations without root noise
     int cap_fast;
     double cap_full_prob;
+    // leaf symmetry (azsp_set_leaf_symmetry; AZ_SYM_OFF = off): every feature row is written under a board symmetry, its priors are mapped
+    // back when its node is expanded.  sym_live: AzMem::leaf_sym may hold a nonzero op -- the host sets it with the first mode that is
+    // not off and clears it after a select over all games with the mode off again; while it is 0 neither phase touches leaf_sym.
+    int leaf_sym, sym_live;
 };
 
 struct AzMem {
@@ -84,6 +92,8 @@ struct AzMem {
     double* log_pi;          // [G][log_cap][A]
     float* log_childN;       // [G][log_cap][A]
     double* log_q;           // [G][log_cap][4]  root_q, child_q, root_N before search (unused), move
+    uint8_t* leaf_sym;       // [G][P]  the dihedral op the row's features were written under (0 = as they are): select writes, expand reads
+    u32* sym_rows;           // [G]     feature rows this slot has written under a leaf symmetry since azsp_create: a counter word of its op stream
     u64* counters;           // [G][AZC_COUNT]  per-game rows (no atomics: 4096 waves hammering 12 shared words cost ~0.6 ms per launch)
     int* err;                // [1]
 };
@@ -247,7 +257,8 @@ template <class Wv, int N, int GAME> struct Engine {
         return s + (c.parallel_mode ? c.P : 0);
     }
     // Playout cap: the class of the move that starts now, from the game's own counter-based stream (a counter word of its own: the
-    // Dirichlet stream uses `| action`, move sampling `| 0xFFF`).  Returns the move's noise_pending.  (first lane only)
+    // Dirichlet stream uses `| action`, move sampling `| 0xFFF`, the leaf symmetry 0xFFD -- row_symmetry()).  Returns the move's
+    // noise_pending.  (first lane only)
     AZ_HD int begin_move_class() {
         int sb = gr.sim_budget & ~AZ_SB_FAST;
         int noise = c.root_noise;
@@ -262,6 +273,50 @@ template <class Wv, int N, int GAME> struct Engine {
         gr.sim_budget = sb;
         return noise;
     }
+
+    // Leaf symmetry: the op of the feature row this slot writes now into row `slot` of its P, remembered in leaf_sym for the expand phase.
+    // AZ_SYM_RANDOM draws floor(8 u) from a stream of its own: key seed + rank, counters (slot, rows this slot has written under a
+    // symmetry, 0xFFD, 0x3000) -- neither uid nor ply, which stand still in drop-in mode.  Wave-uniform.  (select phase, c.sym_live)
+    AZ_HD int row_symmetry(int slot) {
+        int op = c.leaf_sym;
+        if (op != AZ_SYM_OFF) {
+            const u32 rows = Wv::uni(m.sym_rows[g]);
+            if (op == AZ_SYM_RANDOM) {
+                u32 r[4];
+                Philox::gen(c.seed + (u64)c.rank, (u32)g, rows, 0xFFDu, 0x3000u, r);
+                op = Wv::uni((int)(r[0] >> 29));  // floor(8 u01(r[0], r[1])): the top three bits of the 53-bit uniform
+            }
+            if (Wv::first()) m.sym_rows[g] = rows + 1u;
+        }
+        if (op < 0 || op > 7) op = 0;  // AZ_SYM_OFF while rows of an earlier mode drain
+        if (Wv::first()) m.leaf_sym[(size_t)g * c.P + slot] = (uint8_t)op;
+        Wv::sync();
+        return op;
+    }
+    // The observation planes assembled in LDS become D_op of themselves: bit q of a plane is its old bit src_op(q).  A ballot over 64
+    // positions IS a word of the new plane (the idiom of OpSetStates::plane_word); a plane's words are all read before any is replaced.
+    // The emitters then write the row as they always do -- in the tiled layouts into the row's own sub-tile --, so with the symmetry off
+    // their code is the code it was.  (planes 2K.. are uniform, the colour plane included: no symmetry moves them)
+    AZ_HD void permute_planes(int op) {
+#pragma unroll 1  // (an opt-in path inside the hot select kernel: one group of W ballots in the code, not 2K of them)
+        for (int pl = 0; pl < 2 * c.K; ++pl) {
+            u64 nw[W];
+#pragma unroll
+            for (int k = 0; k < W; ++k)
+                nw[k] = Wv::ballot([&](int lane) -> bool {
+                    const int q = lane + 64 * k;
+                    if (q >= NP) return false;
+                    const int p = az_dihedral_src(op, N, q / N, q % N);
+                    return ((sc.planes[pl][p >> 6] >> (p & 63)) & 1ull) != 0;
+                });
+            Wv::sync();
+            if (Wv::first())
+                for (int k = 0; k < W; ++k) sc.planes[pl][k] = nw[k];
+            Wv::sync();
+        }
+    }
+    // priors entry a of the true orientation <- where position a lies in D_op(observation): src_inv(op)(a)
+    static AZ_HD int sym_image(int op, int p) { return az_dihedral_src(az_dihedral_inv(op), N, p / N, p % N); }
 
     AZ_HD Engine(const AzCfg& c_, const AzMem& m_, int g_, SC& sc_)
         : c(c_), m(m_), g(g_), sc(sc_), gr(*(GR*)(m_.games + (size_t)g_ * GREC)) {
@@ -743,6 +798,10 @@ template <class Wv, int N, int GAME> struct Engine {
     }
     AZ_HD void write_features(void* feat, int slot, int me) {
         stack_planes(me);
+        if (c.sym_live) {  // leaf symmetry (wave-uniform branches): the row's op is drawn and remembered, the planes in LDS are permuted
+            const int op = row_symmetry(slot);
+            if (op) permute_planes(op);
+        }
         if (c.feat_dtype == AZ_FEAT_BF16_TILED || c.feat_dtype == AZ_FEAT_F16_TILED) {
             constexpr int TBF = (256 / NP) > 0 ? 256 / NP : 1;
             emit_tiled_t<TBF, 1>(feat, slot, me, c.feat_dtype == AZ_FEAT_F16_TILED ? 0x3C00u : 0x3F80u);  // 1.0 in f16 / bf16
@@ -759,6 +818,15 @@ template <class Wv, int N, int GAME> struct Engine {
             case AZ_FEAT_BF16: emit_planes<uint16_t>((uint16_t*)feat + row, (uint16_t)0x3F80u, me); break;
             default: emit_planes<uint16_t>((uint16_t*)feat + row, (uint16_t)0x3C00u, me); break;
         }
+    }
+    // Leaf symmetry, end of a select phase: the rows this select did NOT write (from `written` on) get op 0, so leaf_sym always describes
+    // the last select and is all zero once the mode is off again.
+    AZ_HD void sym_end(int written) {
+        if (!c.sym_live) return;
+        uint8_t* srow = m.leaf_sym + (size_t)g * c.P;
+        Wv::lanes([&](int lane) {
+            if (lane >= written && lane < c.P) srow[lane] = 0;
+        });
     }
 
     // ---- select phase -------------------------------------------------------------------------
@@ -792,6 +860,7 @@ template <class Wv, int N, int GAME> struct Engine {
                 gr.n_leaves = 0;
             }
             cnt[AZC_ROOT_EVALS]++;
+            sym_end(1);
             hot_store();
             return;
         }
@@ -855,11 +924,19 @@ template <class Wv, int N, int GAME> struct Engine {
             if (lane < c.P) vrow[lane] = lane < nleaf ? 1 : 0;
         });
         if (Wv::first()) gr.n_leaves = nleaf;
+        sym_end(nleaf);
         hot_store();
     }
 
     // ---- expand + backup phase (mcts_v2.py:188-232, :616-625) -----------------------------------
-    AZ_HD void expand_node(int node, const float* prior) {
+    // op (leaf symmetry, wave-uniform): the row was evaluated on D_op(observation), so the node stores D_inv(op)(prior) -- board entry a
+    // is gathered from where position a lies in the transformed board, the pass column stays.
+    // SYM: an instantiation of its own behind the scalar branch of expand_node, the plain one is the code it was.
+    AZ_HD void expand_node(int node, const float* prior, int op = 0) {
+        if (op) expand_node_t<true>(node, prior, op);
+        else expand_node_t<false>(node, prior, 0);
+    }
+    template <bool SYM> AZ_HD void expand_node_t(int node, const float* prior, int op) {
         float* rn = rowN(node);
         float* rw = rowW(node);
         float* rp = rowP(node);
@@ -867,7 +944,7 @@ template <class Wv, int N, int GAME> struct Engine {
         int16_t* rh = rowH(node);
         Wv::lanes([&](int lane) {
             for (int a = lane; a < AP; a += AZ_WAVE) {
-                rp[a] = a < A ? prior[a] : 0.0f;  // stored unmasked, not renormalised (:209)
+                rp[a] = a < A ? prior[(SYM && a < NP) ? sym_image(op, a) : a] : 0.0f;  // stored unmasked, not renormalised (:209)
                 rn[a] = 0.0f;
                 rw[a] = 0.0f;
                 rc[a] = -1;
@@ -877,10 +954,11 @@ template <class Wv, int N, int GAME> struct Engine {
         if (Wv::first()) hdr(node).expanded = 1;
         Wv::sync();
     }
+    AZ_HD int row_op(int slot) const { return c.sym_live ? Wv::uni((int)m.leaf_sym[(size_t)g * c.P + slot]) : 0; }
     AZ_HD void apply_outputs(const float* priors, const float* values) {
         const size_t row0 = (size_t)g * c.P;
         if (Wv::uni(gr.root_eval_pending)) {
-            expand_node(Wv::uni(gr.root), priors + row0 * A);
+            expand_node(Wv::uni(gr.root), priors + row0 * A, row_op(0));
             if (Wv::first()) {
                 gr.root_N = 1;  // backup(root, value) on DummyNode slots: 0.0 + 1, 0.0 + value
                 gr.root_W = (double)values[row0];
@@ -904,7 +982,7 @@ template <class Wv, int N, int GAME> struct Engine {
                 cnt[AZC_DUP_LEAVES]++;
                 continue;
             }
-            expand_node(node, priors + (row0 + s) * A);
+            expand_node(node, priors + (row0 + s) * A, row_op(s));
             path_update(lp, depth, node, values[row0 + s], true, true);
         }
         if (Wv::first()) gr.n_leaves = 0;

@@ -16,6 +16,7 @@
 // The fixed-width rows of the ABI (include/azsp.h): today's widths, pinned so that the drop-in staging offsets cannot drift.
 static_assert(AZSP_STC_COUNT == 8 && AZSP_STQ_COUNT == 2 && AZSP_ENV_COUNT == 12, "status / env rows are part of the ABI");
 static_assert(AZSP_GR_COUNT == 16 && AZSP_GX_COUNT == 4 && AZSP_SQ_COUNT == 4, "game / search rows are part of the ABI");
+static_assert(AZSP_SYM_OFF == AZ_SYM_OFF && AZSP_SYM_RANDOM == AZ_SYM_RANDOM, "leaf symmetry modes: the engine's values are the ABI's");
 
 #define AZ_FOR_EACH_VARIANT(X) \
     X(5, AZ_GO) X(9, AZ_GO) X(13, AZ_GO) X(19, AZ_GO) X(7, AZ_GOMOKU) X(9, AZ_GOMOKU) X(13, AZ_GOMOKU) X(15, AZ_GOMOKU)
@@ -160,6 +161,17 @@ struct OpDropinStep {
             E::Wave::lanes([&](int lane) {
                 if (b0 + lane < n) feat_out[lo + b0 + lane] = src[b0 + lane];
             });
+    }
+};
+// azsp_leaf_symmetries: the slot's wave copies the ops of its P rows (all zero while no leaf symmetry has been on)
+struct OpLeafSyms {
+    uint8_t* out;  // [G * P]
+    template <class E> AZ_HD void operator()(E& e) const {
+        const int P = e.c.P;
+        const uint8_t* src = e.m.leaf_sym + (size_t)e.g * P;
+        E::Wave::lanes([&](int lane) {
+            if (lane < P) out[(size_t)e.g * P + lane] = src[lane];
+        });
     }
 };
 struct OpRngProbe {
@@ -526,20 +538,7 @@ struct DihedralArgs {
     unsigned char* pout;
     int ses, pes, batch, ch, n, A, op;
 };
-AZ_HD int az_dihedral_src(int op, int n, int i, int j) {
-    int r, c;
-    switch (op) {
-        case 1: r = i; c = n - 1 - j; break;          // hflip: reverse the last dim (:46)
-        case 2: r = n - 1 - i; c = j; break;          // vflip (:71)
-        case 3: r = j; c = n - 1 - i; break;          // rot90 counter-clockwise (transformation_test.py:231-274)
-        case 4: r = n - 1 - i; c = n - 1 - j; break;  // rot180
-        case 5: r = n - 1 - j; c = i; break;          // rot270
-        case 6: r = j; c = i; break;                  // transpose (extra)
-        case 7: r = n - 1 - j; c = n - 1 - i; break;  // anti-transpose (extra)
-        default: r = i; c = j; break;
-    }
-    return r * n + c;
-}
+// (az_dihedral_src: az_dihedral.h, shared with the engine's leaf symmetry)
 AZ_HD void az_copy_elem(unsigned char* d, const unsigned char* s, int es) {
     for (int b = 0; b < es; ++b) d[b] = s[b];
 }
@@ -910,6 +909,7 @@ int azsp_create(const AzspConfig* p, void** out) {
     c.seed = p->seed;
     c.rank = p->rank;
     c.stage_cap = p->stop_after_move ? 1 : (p->game == AZSP_GAME_GO ? c.rc.max_steps : h->NP);
+    c.leaf_sym = AZSP_SYM_OFF;  // azsp_set_leaf_symmetry
 
     const size_t G = (size_t)c.G;
     AzMem& m = h->mem;
@@ -933,6 +933,8 @@ int azsp_create(const AzspConfig* p, void** out) {
     m.log_childN = az_new<float>(h, G * c.log_cap * h->A);
     m.log_q = az_new<double>(h, G * c.log_cap * AZSP_SQ_COUNT);
     m.counters = az_new<u64>(h, G * AZC_COUNT);
+    m.leaf_sym = az_new<uint8_t>(h, G * c.P);
+    m.sym_rows = az_new<u32>(h, G);
     m.err = az_new<int>(h, 4);
     h->d_status = az_new<int>(h, G * AZSP_STC_COUNT);
     h->d_q = az_new<double>(h, G * AZSP_STQ_COUNT);
@@ -945,7 +947,7 @@ int azsp_create(const AzspConfig* p, void** out) {
     h->d_games = az_new<int>(h, (size_t)h->d_games_cap * AZSP_GR_COUNT);
     h->d_gextra = az_new<int>(h, (size_t)h->d_games_cap * AZSP_GX_COUNT);
     if (!m.nodes || !m.games || !m.rootP || !m.free_stack || !m.leaf_path || !m.stg_planes || !m.stg_pi || !m.log_pi ||
-        !h->d_games || !h->d_gextra || !m.err || !h->d_hlen || !h->d_hofs) {
+        !h->d_games || !h->d_gextra || !m.err || !h->d_hlen || !h->d_hofs || !m.leaf_sym || !m.sym_rows) {
         for (void* q : h->allocs) azb::release(q);
         delete h;
         return AZSP_ENOMEM;
@@ -1080,11 +1082,18 @@ int azsp_read_searches(void* e, double* pi, float* cn, double* q, int32_t* statu
     return az_run(h, op, stream);
 }
 
+// A select over the games [g0, g1) has been launched.  With the leaf symmetry off again, a select over ALL games leaves AzMem::leaf_sym
+// all zero (Engine::sym_end), so the launches after it need not look at it any more.
+static int az_select_launched(AzHandle* h, int rc, int g0, int g1) {
+    if (rc == AZSP_OK && h->cfg.leaf_sym == AZSP_SYM_OFF && g0 == 0 && g1 == h->cfg.G) h->cfg.sym_live = 0;
+    return rc;
+}
+
 int azsp_select(void* e, void* feat, uint8_t* valid, void* stream) {
     AzHandle* h = (AzHandle*)e;
     if (!h || !feat || !valid) return AZSP_EINVAL;
     OpSelect op = {feat, valid};
-    return az_run(h, op, stream);
+    return az_select_launched(h, az_run(h, op, stream), 0, h->cfg.G);
 }
 
 int azsp_expand_backup(void* e, const float* priors, const float* values, void* stream) {
@@ -1102,7 +1111,7 @@ int azsp_select_range(void* e, void* feat, uint8_t* valid, int32_t g0, int32_t g
     AzHandle* h = (AzHandle*)e;
     if (!h || !feat || !valid || !az_range_ok(h, g0, g1)) return AZSP_EINVAL;
     OpSelect op = {feat, valid};
-    return az_run(h, op, stream, g0, g1);
+    return az_select_launched(h, az_run(h, op, stream, g0, g1), g0, g1);
 }
 
 int azsp_expand_backup_range(void* e, const float* priors, const float* values, int32_t g0, int32_t g1, void* stream) {
@@ -1164,7 +1173,7 @@ int azsp_dropin_step(void* e, const float* priors_host, const float* values_host
     // (priors_dev / values_dev stay the caller's tensors for the separate entries; this entry reads the staging directly)
     OpDropinStep op = {priors_host ? (const float*)pin : nullptr, priors_host ? (const float*)(pin + o_val) : nullptr, feat_dev, valid_dev,
                        (int*)(pin + o_st), (double*)(pin + o_q), (int*)(pin + o_err), pin + o_valid, pin + o_feat, (long long)feat_bytes, (long long)game_feat};
-    int rc = az_run(h, op, stream);
+    int rc = az_select_launched(h, az_run(h, op, stream), 0, h->cfg.G);
     if (rc) return rc;
     if (azb::sync(stream)) {
         h->err = std::string("synchronisation failed: ") + azb::backend_error();
@@ -1287,6 +1296,21 @@ int azsp_set_playout_cap(void* e, int32_t fast_simulations, double full_prob) {
     h->cfg.cap_fast = fast_simulations;  // AzCfg travels by value with every launch: the next move that starts draws its class
     h->cfg.cap_full_prob = full_prob;
     return AZSP_OK;
+}
+
+int azsp_set_leaf_symmetry(void* e, int32_t mode) {
+    AzHandle* h = (AzHandle*)e;
+    if (!h || mode < AZSP_SYM_RANDOM || mode > 7) return AZSP_EINVAL;
+    h->cfg.leaf_sym = mode;  // AzCfg travels by value with every launch: the rows the next select writes
+    if (mode != AZSP_SYM_OFF) h->cfg.sym_live = 1;  // rows in flight keep the op they were written with (az_select_launched clears it)
+    return AZSP_OK;
+}
+
+int azsp_leaf_symmetries(void* e, uint8_t* ops_dev, void* stream) {
+    AzHandle* h = (AzHandle*)e;
+    if (!h || !ops_dev) return AZSP_EINVAL;
+    OpLeafSyms op = {ops_dev};
+    return az_run(h, op, stream);
 }
 
 int azsp_counters(void* e, uint64_t* out, int32_t reset, void* stream) {

@@ -34,6 +34,10 @@
  *   azsp_set_budgets                  no counterpart in the reference: opt-in.  num_simulations per game slot
  *   azsp_set_playout_cap              no counterpart in the reference: opt-in.  A random fraction of an actor's moves gets the full
  *                                     search, the others a cheap one; azsp_harvest_search_class tells the samples apart
+ *   azsp_set_leaf_symmetry            no counterpart in the reference (it transforms in the learner only, core/pipeline.py:636-643):
+ *                                     opt-in.  Every leaf position reaches the evaluator under a board symmetry, chosen at random or
+ *                                     fixed, and its priors are mapped back before the node is expanded; azsp_leaf_symmetries tells a
+ *                                     caller which one each feature row was written under
  *   azsp_replay_gather                UniformReplay.sample + batch tensors + random transformation (core/replay.py:72-83,
  *                                      core/pipeline.py:636-643)
  *   azsp_dihedral                     apply_horizontal_flip / apply_vertical_flip / apply_rotation
@@ -361,6 +365,26 @@ int azsp_set_playout_cap(void* engine, int32_t fast_simulations, double full_pro
  * uint8[sample_capacity] receives 1 for every harvested sample whose move was a full search and 0 for a fast move of the playout
  * cap; with the cap off every byte is 1.  NULL (the default) disables it.  The buffer must stay valid for every later harvest. */
 int azsp_harvest_search_class(void* engine, uint8_t* class_dev);
+
+/* Leaf symmetry (no counterpart in the reference search: opt-in, off by default).  With op the symmetry of a feature row, D_op the
+ * transform of azsp_dihedral (out[c][i][j] = in[c][src_op(i, j)]; on a policy row the N*N board entries move the same way, the pass
+ * column stays) and inv(op) its inverse (3 <-> 5, every other op is its own):
+ *   - azsp_select / azsp_round / azsp_dropin_step write D_op(observation) into the row, in every feature_dtype layout;
+ *   - when the row's node is expanded it stores D_inv(op)(priors row), from priors_dev and from the priors_host of azsp_dropin_step;
+ *   - the value is used as it is.
+ * Nothing else sees the op: recorded samples, azsp_env_step observations, harvests and logs stay in the true orientation.  A search
+ * with op k around an evaluator E is, bit for bit, the plain search around "transform by k, run E, map the priors back".
+ * mode: AZSP_SYM_OFF (the default), AZSP_SYM_RANDOM, or 0..7 = that op for every row; anything else is AZSP_EINVAL.  It holds for the
+ * rows selected after the call; a row in flight keeps the op it was written with.  AZSP_SYM_RANDOM draws op = floor(8 u) per written
+ * row, the root-evaluation row included, from a Philox stream of its own: key seed + rank; counters slot, the slot's count of rows
+ * written under a mode other than AZSP_SYM_OFF since azsp_create, 0xFFD, 0x3000 -- a counter word no other stream uses.  The count
+ * advances in drop-in mode too, so repeated searches of one slot see fresh ops.  (Plain #defines, not an enum: mode is an argument.) */
+#define AZSP_SYM_OFF (-1)
+#define AZSP_SYM_RANDOM (-2)
+int azsp_set_leaf_symmetry(void* engine, int32_t mode);
+/* ops_dev uint8[G * num_parallel]: the op each feature row of the last select was written with -- 0 for a row that select did not
+ * write, and everywhere with the mode off.  What a host callback needs to undo or account for the transform.  Does not synchronise. */
+int azsp_leaf_symmetries(void* engine, uint8_t* ops_dev, void* stream);
 
 /* counters_host uint64[16]: simulations, best_child calls, backup edges, leaves, duplicate leaves, terminal hits,
  * moves, games, root evaluations, nodes created, game-rounds, buffer stalls, speculative record prefetches of the select phase and
