@@ -17,14 +17,15 @@ import torch
 
 from .. import _abi
 from ..envs.base import BoardGameEnv
-from .engine import Engine, EngineConfig
+from .engine import Engine, EngineConfig, forced_playouts_k
 
 
 def dropin_engine(game, board_size, num_games, num_simulations, num_parallel, c_puct_base, c_puct_init, root_noise, komi=7.5, max_steps=0,
-                  num_to_win=5, num_stack=8, binding=None, device=None, leaf_symmetry=None):
+                  num_to_win=5, num_stack=8, binding=None, device=None, leaf_symmetry=None, forced_playouts=None):
     """The engine of a drop-in search, `uct_search`'s with one game and a BatchSearch's with `capacity`: it stops after every move
     (`stop_after_move`), hands out int8 observation planes and logs no moves.  Without a `binding` it runs the product library on the GPU.
-    leaf_symmetry: EngineConfig.leaf_symmetry (None = off)."""
+    leaf_symmetry: EngineConfig.leaf_symmetry (None = off).  forced_playouts: EngineConfig.forced_playouts (None = off)."""
+    forced_playouts_k(forced_playouts)  # ValueError before anything is built
     if binding is None:
         from .. import _lib
 
@@ -32,7 +33,7 @@ def dropin_engine(game, board_size, num_games, num_simulations, num_parallel, c_
     cfg = EngineConfig(game=game, board_size=board_size, num_games=num_games, num_parallel=num_parallel, num_simulations=num_simulations,
                        c_puct_base=c_puct_base, c_puct_init=c_puct_init, root_noise=root_noise, komi=komi, max_steps=max_steps or 0,
                        num_to_win=num_to_win, num_stack=num_stack, stop_after_move=True, feature_dtype=_abi.FEAT_I8, log_moves=False,
-                       leaf_symmetry=leaf_symmetry)
+                       leaf_symmetry=leaf_symmetry, forced_playouts=forced_playouts)
     return Engine(binding, cfg, device=device)
 
 
@@ -207,10 +208,11 @@ def choose_move(env, search_pi, child_n, root_legal, warm_up, deterministic):
 
 
 class SearchResults:
-    """`BatchSearch.results()`: device tensors, one row per active slot; `.cpu()` returns the same three as NumPy arrays."""
+    """`BatchSearch.results()`: device tensors, one row per active slot; `.cpu()` returns pi, child_N and root_Q as NumPy arrays.
+    target_pi: None, or with forced playouts on float64[n, A], the pruned policy target of every slot's search (pi stays unpruned)."""
 
-    def __init__(self, pi, child_N, root_Q):
-        self.pi, self.child_N, self.root_Q = pi, child_N, root_Q
+    def __init__(self, pi, child_N, root_Q, target_pi=None):
+        self.pi, self.child_N, self.root_Q, self.target_pi = pi, child_N, root_Q, target_pi
 
     def cpu(self):
         return self.pi.cpu().numpy(), self.child_N.cpu().numpy(), self.root_Q.cpu().numpy()
@@ -223,17 +225,20 @@ class BatchSearch:
     """
 
     def __init__(self, game, board_size, capacity, num_simulations, num_parallel=1, c_puct_base=19652.0, c_puct_init=1.25, root_noise=False,
-                 komi=7.5, max_steps=0, num_to_win=5, num_stack=8, binding=None, device=None, leaf_symmetry=None):
-        """leaf_symmetry: None, "random" or an op 0..7 (Engine.set_leaf_symmetry; the reference search has none): `eval_func` -- host
+                 komi=7.5, max_steps=0, num_to_win=5, num_stack=8, binding=None, device=None, leaf_symmetry=None, forced_playouts=None):
+        """forced_playouts: None or k >= 0 (Engine.set_forced_playouts; the reference search has none): forced playouts at the root; the
+        move is still to be chosen from `results().pi`, the sample to record is `results().target_pi` (None when off).
+        leaf_symmetry: None, "random" or an op 0..7 (Engine.set_leaf_symmetry; the reference search has none): `eval_func` -- host
         callback or resident evaluator -- is handed every leaf position under that board symmetry ("random": one drawn per feature row)
         and the engine maps its priors back; pi, child_N and Q are in the true orientation."""
         if capacity < 1:
             raise ValueError(f"capacity must be at least 1, got {capacity}")
         check_num_simulations(num_simulations)
+        self.forced_playouts = forced_playouts_k(forced_playouts) > 0.0
         self.game, self.capacity, self.num_simulations, self.num_parallel = game, int(capacity), int(num_simulations), int(num_parallel)
         self.key = _key(game, board_size, komi, max_steps, num_to_win, num_stack)
         self.eng = dropin_engine(game, board_size, self.capacity, num_simulations, num_parallel, c_puct_base, c_puct_init, root_noise, komi,
-                                 max_steps, num_to_win, num_stack, binding, device, leaf_symmetry)
+                                 max_steps, num_to_win, num_stack, binding, device, leaf_symmetry, forced_playouts)
         self.slots = np.zeros(0, dtype=np.int64)  # the active slots (a position is loaded, or a sub-tree was kept), ascending
         self._status = np.full(self.capacity, _abi.ST_IDLE, dtype=np.int32)  # host mirror of the slots' status after load / search / commit
         self._budgets_set = False  # an earlier search left per-slot budgets in the engine (search(num_simulations=...))
@@ -367,7 +372,8 @@ class BatchSearch:
         pi = pi.index_select(0, idx)
         if self.game != "go":
             pi = pi.to(torch.float32)  # float64 for Go, float32 for Gomoku
-        return SearchResults(pi, cn.index_select(0, idx), q.index_select(0, idx)[:, _abi.STQ_ROOT_Q].contiguous())
+        target = self.eng.target_policies().index_select(0, idx) if self.forced_playouts else None
+        return SearchResults(pi, cn.index_select(0, idx), q.index_select(0, idx)[:, _abi.STQ_ROOT_Q].contiguous(), target)
 
     def commit(self, moves):
         """The chosen move of every active slot (`self.slots` order).  Returns (best_child_Q float64[n], reusable bool[n]): a slot whose

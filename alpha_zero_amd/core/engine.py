@@ -55,6 +55,7 @@ class EngineConfig:
     rank: int = 0
     device_index: int = 0
     leaf_symmetry: object = None     # None | "random" | 0..7: the board symmetry leaf positions are evaluated under (Engine.set_leaf_symmetry)
+    forced_playouts: object = None   # None | k >= 0: forced playouts at the root with policy-target pruning (Engine.set_forced_playouts)
 
 
 def leaf_symmetry_mode(mode):
@@ -67,6 +68,16 @@ def leaf_symmetry_mode(mode):
     if not isinstance(mode, (bool, str)) and isinstance(mode, (int, np.integer)) and 0 <= int(mode) <= 7:
         return int(mode)
     raise ValueError(f'leaf_symmetry must be None (off), "random" or an integer op 0..7, got {mode!r}')
+
+
+def forced_playouts_k(k):
+    """The azsp_set_forced_playouts factor of a `forced_playouts` value: None = off (0.0), else a finite number k >= 0 (KataGo uses 2).
+    Anything else raises ValueError naming these."""
+    if k is None:
+        return 0.0
+    if not isinstance(k, (bool, str)) and isinstance(k, (int, float, np.integer, np.floating)) and math.isfinite(float(k)) and float(k) >= 0.0:
+        return float(k)
+    raise ValueError(f"forced_playouts must be None (off) or a finite number k >= 0, got {k!r}")
 
 
 MAX_NUM_STACK = 8  # the engine's history ring holds 8 boards (include/azsp.h AzspConfig.num_stack)
@@ -97,6 +108,7 @@ class Engine:
         self.on_launch = None
         check_num_stack(cfg.num_stack)
         sym = leaf_symmetry_mode(cfg.leaf_symmetry)
+        forced = forced_playouts_k(cfg.forced_playouts)
         c = AzspConfig()
         c.game = _abi.GAME_GO if cfg.game == "go" else _abi.GAME_GOMOKU
         c.board_size, c.num_games, c.num_parallel, c.num_simulations = cfg.board_size, cfg.num_games, cfg.num_parallel, cfg.num_simulations
@@ -139,6 +151,9 @@ class Engine:
         self._harvest_bufs = None
         if sym != _abi.SYM_OFF:
             self.set_leaf_symmetry(cfg.leaf_symmetry)  # before the first select: the first root evaluation is transformed too
+        self.forced_playouts = False  # forced playouts have been on at least once: the target rows exist (target_policies)
+        if forced > 0.0:
+            self.set_forced_playouts(forced)
 
     # -- plumbing ---------------------------------------------------------------------------------
     def _ck(self, rc, what):
@@ -351,6 +366,23 @@ class Engine:
         ops = torch.empty((self.rows,), dtype=torch.uint8, device=self.device)
         self._ck(self.b.dll.azsp_leaf_symmetries(self.h, ops.data_ptr(), self._stream()), "azsp_leaf_symmetries")
         return ops
+
+    def set_forced_playouts(self, k, prune_target=True):
+        """Forced playouts at the root with policy-target pruning (azsp_set_forced_playouts; KataGo, Wu 2019, 3.2; the reference search
+        has none): None or 0 = off, k > 0 = every root child in play gets at least sqrt(k P(c) sum N) visits in a search that is no fast
+        move of the playout cap.  prune_target: the pi recorded for the sample and `target_policies()` leave out the forced visits the
+        search did not want; False forces without pruning.  The move, the logs and `read_searches` stay those of the unpruned search.
+        Holds for the selections and move ends from now on."""
+        kk = forced_playouts_k(k)
+        self._ck(self.b.dll.azsp_set_forced_playouts(self.h, C.c_double(kk), int(bool(prune_target))), "azsp_set_forced_playouts")
+        self.forced_playouts = self.forced_playouts or kk > 0.0
+
+    def target_policies(self):
+        """float64[G, A] on the engine's device: per slot the policy target of its last search that finished with forced playouts on
+        (azsp_read_target_policies; zero rows before the first).  Only once forced playouts have been enabled.  Nothing is synchronised."""
+        out = torch.empty((self.G, self.A), dtype=torch.float64, device=self.device)
+        self._ck(self.b.dll.azsp_read_target_policies(self.h, out.data_ptr(), self._stream()), "azsp_read_target_policies")
+        return out
 
     # -- samples ----------------------------------------------------------------------------------------
     def harvest(self, sample_capacity=None, max_games=None, with_moves=False, with_class=False):

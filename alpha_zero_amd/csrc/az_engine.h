@@ -70,6 +70,12 @@ struct AzCfg {
     // back when its node is expanded.  sym_live: AzMem::leaf_sym may hold a nonzero op -- the host sets it with the first mode that is
     // not off and clears it after a select over all games with the mode off again; while it is 0 neither phase touches leaf_sym.
     int leaf_sym, sym_live;
+    // forced playouts at the root + policy-target pruning (azsp_set_forced_playouts; forced_k = 0: off).  A root child with n_eff > 0
+    // visits (in-flight descents included) and n_eff^2 < forced_k * P * T_eff is selected before the PUCT arg-max; at the end of the move
+    // the forced visits the search did not want are taken out of the recorded policy target (prune_target), not out of the tree.
+    // A fast move of the playout cap is neither forced nor pruned.
+    int prune_target;
+    double forced_k;
 };
 
 struct AzMem {
@@ -92,6 +98,7 @@ struct AzMem {
     double* log_pi;          // [G][log_cap][A]
     float* log_childN;       // [G][log_cap][A]
     double* log_q;           // [G][log_cap][4]  root_q, child_q, root_N before search (unused), move
+    double* target_pi;       // [G][A]  policy target of the slot's last finished search (forced playouts: pruned); null until they are first enabled
     uint8_t* leaf_sym;       // [G][P]  the dihedral op the row's features were written under (0 = as they are): select writes, expand reads
     u32* sym_rows;           // [G]     feature rows this slot has written under a leaf symmetry since azsp_create: a counter word of its op stream
     u64* counters;           // [G][AZC_COUNT]  per-game rows (no atomics: 4096 waves hammering 12 shared words cost ~0.6 ms per launch)
@@ -166,7 +173,14 @@ template <int W, int AP, int HW> struct Scratch {
             float tmpf[AP];             // float32 policy terms (Gomoku)
             int16_t parent[AZ_LDS_NODES];
         };
-        StagedRec<AP, HW> nxt;  // select: speculatively staged record of the node the descent will probably reach one level further down
+        struct {
+            StagedRec<AP, HW> nxt;  // select: speculatively staged record of the node the descent will probably reach one level further down
+            // select, forced playouts (all of it under `parent`: no LDS added, and in LDS because the select kernel has no register to
+            // spare): leaves of the current batch below root move a; T_eff = the sum of the root's child N + the leaves accepted into the
+            // batch so far, -1 = not on for this search; the forced child of the root for the descent that starts now, -1 = none
+            float fv[AP];  // (float: the lane's address is the one of the N / W / P rows; a byte row cost the kernel two more VGPRs)
+            int teff, fsel;
+        };
     };
     StagedRec<AP, HW> root;     // the root's record: staged ONCE per round, kept current in LDS while the P descents update it
     StagedRec<AP, HW> cur;      // the record of the node the current descent is looking at (levels >= 1)
@@ -573,6 +587,36 @@ template <class Wv, int N, int GAME> struct Engine {
         });
     }
 
+    // Forced playouts (KataGo, Wu 2019, 3.2) at the root: with n_eff(a) = N(a) + v(a) -- v(a) = leaves of the current batch whose path starts
+    // with a (sc.fv): virtual loss touches W only, so the in-flight descents are counted here -- and T_eff = sum N + leaves of the batch,
+    // a legal child is forced when n_eff > 0 and n_eff^2 < (k P(a)) T_eff, in float64 as written (no square root).  P(a) is the prior the
+    // PUCT term uses: rootP at a noisy root, else the float32 prior.  Returns the forced child with the lowest index, -1 = none.
+    // Runs in select() in front of every descent and leaves its result in sc.fsel; descend() reads that word after the root's arg-max.
+    // The 9x9 select kernel sits at 126 of the 128 VGPRs of four waves per SIMD with every SGPR in use: one more wave-uniform value
+    // that lives across the descent (the first versions kept T_eff and the forced child in registers, or branched inside puct_argmax)
+    // tips the scheduler over that line and the kernel comes out at 142 to 186 VGPRs.
+    AZ_HD int forced_child(const SR& r) {
+        const S& s = hdr_of(r).st;
+        u64 lg[W];
+        for (int i = 0; i < W; ++i) lg[i] = Wv::uni(s.legal[i]);
+        const bool pass_ok = GAME == AZ_GO && !(Wv::uni((int)s.flags) & AZF_TERMINAL);
+        const double kk = c.forced_k, teff = (double)Wv::uni(sc.teff);
+        const bool noisy = hs_noisy != 0;
+        for (int j = 0; j < EPL; ++j) {
+            const u64 fm = Wv::ballot([&](int lane) -> bool {
+                const int a = lane + 64 * j;
+                if (a >= A) return false;
+                if (!(a < NP ? (j < W && ((lg[j < W ? j : 0] >> lane) & 1ull) != 0) : pass_ok)) return false;
+                const double ne = (double)r.rN[a] + (double)sc.fv[a];
+                if (!(ne > 0.0)) return false;
+                const double p = noisy ? sc.rP64[a] : (double)r.rP[a];
+                return ne * ne < (kk * p) * teff;
+            });
+            if (fm) return 64 * j + __builtin_ctzll(fm);
+        }
+        return -1;
+    }
+
     // One descent from the root.  Returns 0 = leaf reached (unexpanded, non-terminal), 1 = terminal.
     // On return `leaf_state` holds the leaf's position (used for the observation planes).
     AZ_HD int descend(int& node_out, int& depth_out, S& leaf_state) {
@@ -594,6 +638,10 @@ template <class Wv, int N, int GAME> struct Engine {
         for (;;) {
             const SR& r = depth == 0 ? sc.root : (cur_is_nxt ? sc.nxt : sc.cur);  // the root record lives in LDS for the whole round
             int mv = puct_argmax(r, depth == 0, pbc64, sq32);
+            if (depth == 0) {  // forced playouts (select()): a forced child of the root goes first
+                const int f = Wv::uni(sc.fsel);
+                mv = f >= 0 ? f : mv;
+            }
             int child = Wv::uni((int)r.rC[mv]);
             const int hint = Wv::uni((int)r.rH[mv]);
             n_self = Wv::uni((int)r.rN[mv]);
@@ -832,7 +880,10 @@ template <class Wv, int N, int GAME> struct Engine {
     // ---- select phase -------------------------------------------------------------------------
     AZ_HD void select(void* feat, unsigned char* valid) {
         unsigned char* vrow = valid + (size_t)g * c.P;
-        if (Wv::first()) sc.free_base = -(1 << 30);  // no staged free-stack window yet
+        if (Wv::first()) {
+            sc.free_base = -(1 << 30);  // no staged free-stack window yet
+            sc.teff = sc.fsel = -1;     // forced playouts: not on (yet)
+        }
         Wv::sync();
         const int status = Wv::uni(gr.status);
         hot_load();
@@ -887,6 +938,18 @@ template <class Wv, int N, int GAME> struct Engine {
                 Wv::sync();
                 stage_node(hs_root, sc.root, hs_noisy != 0);
             }
+            if (c.forced_k > 0.0 && !(Wv::uni(gr.sim_budget) & AZ_SB_FAST)) {  // forced playouts: T_eff and v(a) of this select phase
+                const int sum = Wv::sum_i32([&](int lane) -> int {
+                    int part = 0;
+                    for (int a = lane; a < AP; a += AZ_WAVE) {
+                        part += (int)sc.root.rN[a];
+                        sc.fv[a] = 0.0f;
+                    }
+                    return part;
+                });
+                if (Wv::first()) sc.teff = sum;
+                Wv::sync();
+            }
             // mcts_v2.py:572: up to P leaves in at most 2P attempts, one after another (each descent
             // sees the virtual losses of the previous ones); uct_search (:378-418) is the P == 1 case
             const int max_att = c.parallel_mode ? 2 * c.P : 1;
@@ -894,11 +957,17 @@ template <class Wv, int N, int GAME> struct Engine {
                 attempts++;
                 int node, depth;
                 S leaf;
+                if (Wv::uni(sc.teff) >= 0) {  // (wave-uniform) forced playouts
+                    const int f = forced_child(sc.root);
+                    if (Wv::first()) sc.fsel = f;
+                    Wv::sync();
+                }
                 const int term = descend(node, depth, leaf);
                 cnt[AZC_SIMS]++;
                 if (term) {
                     // mcts_v2.py:407-411 / :604-608: back up -reward, node stays unexpanded
                     cnt[AZC_TERMINAL_HITS]++;
+                    if (Wv::first() && sc.teff >= 0) sc.teff += 1;  // (forced playouts) the hit goes through the root: not in flight, counted in N
                     path_apply(depth, node, (float)(-(int)leaf.reward), true, true);
                     if (!c.parallel_mode && hs_rootN < budget) attempts = 0;  // uct_search keeps looping (:378)
                     if (!c.parallel_mode && hs_rootN >= budget) break;
@@ -913,6 +982,11 @@ template <class Wv, int N, int GAME> struct Engine {
                     gr.leaf_node[nleaf] = (int16_t)node;
                     gr.leaf_depth[nleaf] = (uint8_t)(depth < 255 ? depth : 255);
                 }
+                if (Wv::first() && sc.teff >= 0) {  // (forced playouts) this leaf is in flight below its root move
+                    sc.fv[sc.path[0] & 0xffff] += 1.0f;
+                    sc.teff += 1;
+                }
+                Wv::sync();
                 const int me = leaf.to_play;
                 gather_planes(node, depth, me, &leaf);
                 write_features(feat, nleaf, me);
@@ -1108,9 +1182,10 @@ template <class Wv, int N, int GAME> struct Engine {
     }
 
     // generate_search_policy (mcts_v2.py:265-298) into the wave's LDS row sc.pi[A] (and the move log when enabled).
-    AZ_HD void search_policy(bool warm, double* log_pi) {
+    // rn: the visit counts the policy is formed from -- the root's child N, or the pruned counts of prune_counts() (an LDS row).
+    AZ_HD void search_policy(bool warm, double* log_pi, const float* rn = nullptr) {
         const S& s = hdr(gr.root).st;
-        const float* rn = rowN(gr.root);
+        if (!rn) rn = rowN(gr.root);
         if (GAME == AZ_GO) {
             // legal(int64) * child_N(float32) -> float64; n**5 and the sum are exact integers in float64, so the
             // summation order is irrelevant and a wave reduction is bit-identical to np.sum
@@ -1160,6 +1235,89 @@ template <class Wv, int N, int GAME> struct Engine {
                 for (int a = lane; a < A; a += AZ_WAVE) log_pi[a] = sc.pi[a];
             });
         }
+    }
+
+    // Policy-target pruning (forced playouts; end of a search, no virtual loss outstanding) into the LDS row `out` (AP floats).
+    // c* = the first legal action with the largest N, S* = its PUCT score; score(a, m) = the expression puct_argmax evaluates at the root
+    // with N(a) replaced by m (q stays W(a) / N(a); pb_c, sqrt entry, float64 / float32 as at the root's final visit count).  Every other
+    // visited legal child loses up to f(a) = floor(sqrt(k P(a) T)) visits, one at a time while its score stays below S*; a child left
+    // with a single playout is pruned outright.  One lane per action, at most f(a) + 1 scores each.
+    AZ_HD void prune_counts(float* out) {
+        const int root = gr.root;
+        const S& s = hdr(root).st;
+        const float* rn = rowN(root);
+        const float* rw = rowW(root);
+        const float* rp = rowP(root);
+        const double* rp64 = rootP();
+        const bool noisy = Wv::uni(gr.root_noisy) != 0;
+        double pbc64;
+        float sq32;
+        table_entry(Wv::uni(gr.root_N), Wv::uni(gr.root_fresh) != 0, pbc64, sq32);
+        const float pbc32 = (float)pbc64;
+        const double kk = c.forced_k;
+        auto score = [&](int a, float n) -> double {
+            const float n0 = rn[a], w = rw[a];
+            const float q = w / (n0 > 0.0f ? n0 : 1.0f);
+            const float rr = sq32 / (1.0f + n);
+            if (noisy) return (double)(-q) + (pbc64 * rp64[a]) * (double)rr;
+            return (double)(-q + (pbc32 * rp[a]) * rr);
+        };
+        const double T = Wv::sum_f64([&](int lane) -> double {
+            double part = 0.0;
+            for (int a = lane; a < A; a += AZ_WAVE) part += (double)rn[a];
+            return part;
+        });
+        const int cs = Wv::argmax_first([&](int lane, double& best, int& bi) {
+            for (int a = lane; a < A; a += AZ_WAVE)
+                if (action_legal(s, a) && (bi < 0 || (double)rn[a] > best)) {
+                    best = (double)rn[a];
+                    bi = a;
+                }
+        });
+        const bool any = cs >= 0 && cs < A && rn[cs] > 0.0f;
+        const double sstar = any ? score(cs, rn[cs]) : 0.0;
+        Wv::lanes([&](int lane) {
+            for (int a = lane; a < AP; a += AZ_WAVE) {
+                float keep = a < A ? rn[a] : 0.0f;
+                if (any && a < A && a != cs && keep > 0.0f && action_legal(s, a)) {
+                    const int ni = (int)keep;
+                    // only min(f, N(a)) is used, and that is the largest integer with f^2 <= min(x, N(a)^2): the square root is taken of
+                    // a value of at most N(a)^2 < 2^48 (N is a float32 count), whatever k is -- x itself may be huge or inf for a large k
+                    const double nn = (double)ni * (double)ni, xk = (kk * (noisy ? rp64[a] : (double)rp[a])) * T;
+                    const double x = xk < nn ? xk : nn;
+                    int f = 0;  // a truncated square root, corrected with the multiplication; 0 <= f <= N(a)
+                    if (x > 0.0) {
+                        f = (int)sqrt(x);
+                        while (f > 0 && (double)f * (double)f > x) --f;
+                        while (f < ni && (double)(f + 1) * (double)(f + 1) <= x) ++f;
+                    }
+                    const int lo = ni - f;
+                    int last = ni;
+                    for (int mm = ni - 1; mm >= lo; --mm) {
+                        if (score(a, (float)mm) >= sstar) break;
+                        last = mm;
+                    }
+                    if (last < ni && last == 1) last = 0;
+                    keep = (float)last;
+                }
+                out[a] = keep;
+            }
+        });
+        Wv::sync();
+    }
+    // The policy target of the search that just ended (forced playouts on): the pruned policy unless the move was a fast one of the
+    // playout cap or pruning is off -- then the plain one search_policy left in sc.pi.  It replaces sc.pi, which record_sample stages,
+    // and goes to the slot's target_pi row.  (after the move was chosen from the unpruned policy; sc.cur is free at the end of a move)
+    AZ_HD void make_target(bool warm) {
+        if (c.prune_target && !(Wv::uni(gr.sim_budget) & AZ_SB_FAST)) {
+            prune_counts(sc.cur.rN);
+            search_policy(warm, nullptr, sc.cur.rN);
+        }
+        double* tp = m.target_pi + (size_t)g * A;
+        Wv::lanes([&](int lane) {
+            for (int a = lane; a < A; a += AZ_WAVE) tp[a] = sc.pi[a];
+        });
+        Wv::sync();
     }
 
     // np.random.choice(p=pi): cdf = cumsum(p) (sequential, float64), cdf /= cdf[-1], searchsorted(cdf, u, 'right').
@@ -1373,6 +1531,7 @@ template <class Wv, int N, int GAME> struct Engine {
             });
         }
         if (c.stop_after_move) {
+            if (c.forced_k > 0.0) make_target(warm);
             if (Wv::first()) {
                 gr.out_root_q = root_q();
                 gr.status = AZS_MOVE_DONE;
@@ -1392,6 +1551,7 @@ template <class Wv, int N, int GAME> struct Engine {
         } else {
             mv = sample_move(warm);
         }
+        if (c.forced_k > 0.0) make_target(warm);  // the move came from the unpruned policy; the sample records the target
         commit_actor(mv);
     }
 

@@ -174,6 +174,17 @@ struct OpLeafSyms {
         });
     }
 };
+// azsp_read_target_policies: the slot's wave copies its target_pi row (zero before the slot's first finished search)
+struct OpReadTargets {
+    double* out;  // [G][A]
+    template <class E> AZ_HD void operator()(E& e) const {
+        const int A = E::A;
+        const double* src = e.m.target_pi + (size_t)e.g * A;
+        E::Wave::lanes([&](int lane) {
+            for (int a = lane; a < A; a += AZ_WAVE) out[(size_t)e.g * A + a] = src[a];
+        });
+    }
+};
 struct OpRngProbe {
     double* noise;
     double* unif;
@@ -1310,6 +1321,26 @@ int azsp_leaf_symmetries(void* e, uint8_t* ops_dev, void* stream) {
     AzHandle* h = (AzHandle*)e;
     if (!h || !ops_dev) return AZSP_EINVAL;
     OpLeafSyms op = {ops_dev};
+    return az_run(h, op, stream);
+}
+
+int azsp_set_forced_playouts(void* e, double k, int32_t prune_target) {
+    AzHandle* h = (AzHandle*)e;
+    if (!h || !(k >= 0.0) || !(k <= 1.7976931348623157e308)) return AZSP_EINVAL;  // negative, NaN, infinite
+    if (k > 0.0 && !h->mem.target_pi) {  // the first enabling call allocates the target rows: never a launch path
+        if (azb::set_device(h->pub.device) != 0) return AZSP_EDEVICE;  // the engine's device, as azsp_create selects it, whatever the calling thread's is
+        h->mem.target_pi = az_new<double>(h, (size_t)h->cfg.G * h->A);  // (zero-initialised, like every engine allocation)
+        if (!h->mem.target_pi) return AZSP_ENOMEM;
+    }
+    h->cfg.forced_k = k;  // AzCfg travels by value with every launch: the selections and move ends after this call
+    h->cfg.prune_target = prune_target ? 1 : 0;
+    return AZSP_OK;
+}
+
+int azsp_read_target_policies(void* e, double* pi_dev, void* stream) {
+    AzHandle* h = (AzHandle*)e;
+    if (!h || !pi_dev || !h->mem.target_pi) return AZSP_EINVAL;  // no rows before forced playouts were first enabled
+    OpReadTargets op = {pi_dev};
     return az_run(h, op, stream);
 }
 

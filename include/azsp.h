@@ -38,6 +38,8 @@
  *                                     opt-in.  Every leaf position reaches the evaluator under a board symmetry, chosen at random or
  *                                     fixed, and its priors are mapped back before the node is expanded; azsp_leaf_symmetries tells a
  *                                     caller which one each feature row was written under
+ *   azsp_set_forced_playouts          no counterpart in the reference: opt-in.  Forced playouts at the root with policy-target pruning
+ *                                     (KataGo, Wu 2019, 3.2); azsp_read_target_policies hands a drop-in caller the pruned targets
  *   azsp_replay_gather                UniformReplay.sample + batch tensors + random transformation (core/replay.py:72-83,
  *                                      core/pipeline.py:636-643)
  *   azsp_dihedral                     apply_horizontal_flip / apply_vertical_flip / apply_rotation
@@ -385,6 +387,39 @@ int azsp_set_leaf_symmetry(void* engine, int32_t mode);
 /* ops_dev uint8[G * num_parallel]: the op each feature row of the last select was written with -- 0 for a row that select did not
  * write, and everywhere with the mode off.  What a host callback needs to undo or account for the transform.  Does not synchronise. */
 int azsp_leaf_symmetries(void* engine, uint8_t* ops_dev, void* stream);
+
+/* Forced playouts at the root with policy-target pruning (KataGo, Wu 2019, 3.2; no counterpart in the reference search: opt-in, off by
+ * default).  k >= 0, finite (0 = off, KataGo uses 2); anything else is AZSP_EINVAL.  Valid in actor and drop-in mode; holds for the
+ * selections and move ends after the call.  The rule applies at the root only, to every search whose move is not a fast move of the
+ * playout cap, with or without root noise.  N(a), W(a) = the root's child row, P(a) = the prior the root's PUCT term uses (the float64
+ * noisy prior at a noisy root, else the float32 prior converted to double), legal(a) = the mask the selection applies.
+ *   Forcing (select).  Virtual loss touches W only, so the descents in flight are counted: v(a) = the leaves already accepted into the
+ *   current leaf batch whose path starts with root move a (duplicates count; terminal hits are backed up, not in flight),
+ *   n_eff(a) = N(a) + v(a), T_eff = sum_a N(a) + leaves of the batch.  A legal child is forced when n_eff > 0 and
+ *   (double)n_eff * (double)n_eff < (k * (double)P(a)) * (double)T_eff, evaluated as written (no square root).  If any child is forced
+ *   the root's arg-max returns the forced child with the lowest action index, else what it returns without the rule.  Nothing else of
+ *   the descent changes.
+ *   Pruning (end of the move; no virtual loss is outstanding).  T = sum_a N(a); c* = the first legal action with the largest N;
+ *   score(a, m) = the -q + u the root's selection evaluates for child a with N(a) replaced by m in u (q stays W(a) / N(a); pb_c, the
+ *   square-root entry and float64 / float32 as at the root's final visit count); S* = score(c*, N(c*)).  For every legal a != c* with
+ *   N(a) > 0: f(a) = the largest integer with f^2 <= (k * (double)P(a)) * (double)T; m runs from N(a) - 1 down to max(N(a) - f(a), 0)
+ *   and stops at the first m with score(a, m) >= S*; N'(a) = the last m that passed (N(a) if none); a child reduced to a single playout
+ *   is pruned outright (N' = 0).  N'(c*) = N(c*); without a visited child nothing is pruned.  The policy target is the search policy
+ *   (same temperature exponent, float64 for Go, float32 pairwise sum for Gomoku) of N' instead of N.
+ * What uses which: the move is chosen from the unpruned policy, and the move log, azsp_get_search and azsp_read_searches keep
+ * reporting the unpruned search; the pi row staged for the sample -- everything azsp_harvest hands out -- and the slot's target row
+ * are the pruned target.  prune_target = 0 forces without pruning: the target is the plain policy.  A fast move of the playout cap is
+ * neither forced nor pruned.  With k = 0 neither phase evaluates the rule (what stays is a flag per select launch and per descent) and
+ * every output is what it is without this call.
+ * Every finite k is accepted, however large: only min(f(a), N(a)) enters the pruning, so its cost per child is bounded by N(a), and a
+ * k beyond any N^2 / (P T) simply forces every visited child with P > 0 and lets every such child be pruned down to 0.  The first call
+ * with k > 0 allocates the target rows on the engine's device and, like azsp_create, leaves that device selected on the calling thread. */
+int azsp_set_forced_playouts(void* engine, double k, int32_t prune_target);
+/* pi_dev float64[G][A]: per slot the policy target of its most recent search that finished with forced playouts on (k > 0) -- what a
+ * drop-in caller records instead of the pi of azsp_read_searches.  A row is zero before the slot's first such search; with pruning off
+ * it equals the plain policy.  AZSP_EINVAL before forced playouts were enabled for the first time (the rows are allocated by that
+ * call, never by a launch).  Does not synchronise. */
+int azsp_read_target_policies(void* engine, double* pi_dev, void* stream);
 
 /* counters_host uint64[16]: simulations, best_child calls, backup edges, leaves, duplicate leaves, terminal hits,
  * moves, games, root evaluations, nodes created, game-rounds, buffer stalls, speculative record prefetches of the select phase and
