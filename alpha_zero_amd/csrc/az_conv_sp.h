@@ -137,14 +137,6 @@ template <int H> __device__ __forceinline__ float sp_mix_join(unsigned rh, unsig
     else asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,1] op_sel_hi:[1,0,1]" : "=v"(r) : "v"(rl), "s"(SP_INV_SCALE), "v"(rh));
     return r;
 }
-// s - 2^11 * (f16) half `H` of hpk, with s = 2^11 v: the scaled remainder (v - hi) 2^11 of sp_split in one v_fma_mix_f32 (both products
-// are exact in fp32 and so is their difference: bit-identical to the subtract-then-scale of sp_split)
-template <int H> __device__ __forceinline__ float sp_mix_rem(unsigned hpk, float s) {
-    float r;
-    if constexpr (H == 0) asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(hpk), "s"(-SP_SCALE), "v"(s));
-    else asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(hpk), "s"(-SP_SCALE), "v"(s));
-    return r;
-}
 __device__ __forceinline__ unsigned sp_cvt_pk(float a, float b) {  // one v_cvt_pk_f16_f32 (round to nearest even)
     return __builtin_bit_cast(unsigned, (sp_f16x2){(_Float16)a, (_Float16)b});
 }
@@ -165,13 +157,14 @@ __device__ __forceinline__ unsigned sp_scale_cvt_hi(unsigned lo, float d) {
     asm("v_fma_mixhi_f16 %0, %1, %2, 0 op_sel:[0,0,0] op_sel_hi:[0,0,0]" : "+v"(lo) : "v"(d), "s"(SP_SCALE));
     return lo;
 }
-// Micro-ops of a riding epilogue (shared by the kernels and by the compile-time mirrors of their schedules, sp9_vm_younger /
-// sp17_vm_younger): per element E1 = join [, residual join, add]; per pair of elements 8 more: range record of both (one v_max3_f32), 2 x
-// ReLU + clamp (one v_med3_f32 each: the lower bound is 0 with ReLU, -65504 without), packed hi convert, 2 exact remainders v - hi,
-// 2 scale-and-convert v_fma_mixlo/hi_f16; per column tile 2 stores.  (Round 4: 38 / 30 micro-ops per column tile; now 30 / 22.)
-__host__ __device__ constexpr int sp_epi_e1(bool res) { return res ? 3 : 1; }
-__host__ __device__ constexpr int sp_epi_pair(bool res) { return 2 * sp_epi_e1(res) + 8; }
-__host__ __device__ constexpr int sp_epi_ct_ops(bool res) { return 2 * sp_epi_pair(res) + 2; }
+// Micro-ops of a riding epilogue (shared by the kernels, SpEpi below, and by the compile-time mirrors of their schedules, sp9_vm_younger /
+// sp17_vm_younger / Sp2pK): per element E1 = join [, partner add (k_conv3x3_sp2p: the other cin half's partial sum)] [, residual join, add];
+// per pair of elements 8 more: range record of both (one v_max3_f32), 2 x ReLU + clamp (one v_med3_f32 each: the lower bound is 0 with
+// ReLU, -65504 without), packed hi convert, 2 exact remainders v - hi, 2 scale-and-convert v_fma_mixlo/hi_f16; per column tile 2 stores.
+// (Round 4: 38 / 30 micro-ops per column tile; now 30 / 22.)
+__host__ __device__ constexpr int sp_epi_e1(bool res, bool partner = false) { return (res ? 3 : 1) + (partner ? 1 : 0); }
+__host__ __device__ constexpr int sp_epi_pair(bool res, bool partner = false) { return 2 * sp_epi_e1(res, partner) + 8; }
+__host__ __device__ constexpr int sp_epi_ct_ops(bool res, bool partner = false) { return 2 * sp_epi_pair(res, partner) + 2; }
 // mx = max(mx, |a|, |b|) in one v_max3_f32 (the range record of a pair of elements)
 __device__ __forceinline__ float sp_max3_abs(float mx, float a, float b) {
     asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(mx) : "v"(a), "v"(b));
@@ -196,6 +189,121 @@ template <int P_OPS, int S0, int AVAIL> struct SpSpread {
     }
     static_assert(AVAIL > 0 && cum(S0 + AVAIL - 1) == P_OPS, "every micro-op has a slot");
 };
+// Stores of a riding epilogue with schedule SP (pnj column tiles of ct_ops micro-ops; a tile's two stores are its last two micro-ops) that
+// are issued in a k-step behind `step` (nq MFMA slots per k-step): the vector-memory instructions younger than an LDS-DMA piece issued
+// behind all MFMA slots of k-step `step` (step < 0: every store).  The compile-time mirrors behind the counted s_waitcnt vmcnt.
+template <class SP> __host__ __device__ constexpr int sp_epi_stores_behind(int pnj, int ct_ops, int nq, int step) {
+    int n = 0;
+    for (int c = 0; c < pnj; ++c)
+        for (int st = 0; st < 2; ++st)
+            if (SP::slot_of(c * ct_ops + ct_ops - 2 + st) / nq > step) ++n;
+    return n;
+}
+
+// ---- what the weight-stationary kernels share: k_conv3x3_sp (below), k_conv3x3_sp17 (az_conv_sp17.h), k_resblock_sp (az_resblock_sp17.h),
+// k_conv3x3_sp2p (az_conv_sp2p.h).  Their unit schedules differ and stay in the kernels; the pieces the schedules issue are these. ----
+// Base of a board's output (or residual) slots of a wave: the hi plane as a plain pointer, the lo plane as ONE uniform base that is opaque to
+// the compiler (it would otherwise fold base + plane size + lane offset into 64-bit VALU adds per access: a plane exceeds the 13-bit
+// immediate).  Every residual load / y store is then scalar base + 32-bit lane offset, in the global address space (no flat accesses).
+struct SpOut {
+    unsigned char* hi;
+    sp_gptr lo;
+};
+__device__ __forceinline__ SpOut sp_out_base(const unsigned char* p, int plane) {
+    unsigned long long lo = (unsigned long long)p + plane;
+    asm volatile("" : "+s"(lo));
+    return {const_cast<unsigned char*>(p), (sp_gptr)lo};
+}
+// the 8 bytes (4 channels of one plane) of a lane's slot `off`: a unit's residual load
+__device__ __forceinline__ cv_u32x2 sp_load8(const SpOut& b, int plane, unsigned off) {
+    if (plane == 0) return *(const cv_u32x2*)(b.hi + off);
+    return *(const __attribute__((address_space(1))) cv_u32x2*)(b.lo + off);
+}
+// The riding epilogue of one column tile: its registers and its micro-ops, ONE VALU / memory instruction each (counts: sp_epi_* above).
+// op<RES, PARTNER>(o, ...) is arithmetic micro-op o < 2 sp_epi_pair(RES, PARTNER) on the tile's accumulators am (main), ac (correction), the
+// residual words r[plane] and the partner's partial sums xr; store(0 / 1, ...) are the tile's two stores (hi, lo plane).
+struct SpEpi {
+    float evv[2] = {0.0f, 0.0f}, sc[2] = {0.0f, 0.0f}, t0 = 0.0f, mx = 0.0f;  // mx: the largest |value| this lane produced (range record, sp_range_report)
+    unsigned hpk[2] = {0u, 0u}, lpk[2] = {0u, 0u};
+    template <bool RES, bool PARTNER = false>
+    __device__ __forceinline__ void op(int o, const c6_f32x4& am, const c6_f32x4& ac, const cv_u32x2 (&r)[2], float lo_clamp, const c6_f32x4* xr = nullptr) {
+        constexpr int E1 = sp_epi_e1(RES, PARTNER), PAIR = sp_epi_pair(RES, PARTNER), P = PARTNER ? 1 : 0;
+        const int pr = o / PAIR, k = o % PAIR;  // pair pr = elements 2 pr, 2 pr + 1 (one packed dword of each plane)
+        if (k < 2 * E1) {
+            const int ei = k / E1, kk = k % E1, e = 2 * pr + ei;
+            const unsigned rh = pr == 0 ? r[0].x : r[0].y, rl = pr == 0 ? r[1].x : r[1].y;
+            if (kk == 0) evv[ei] = fmaf(ac[e], SP_INV_SCALE, am[e]);
+            else if (PARTNER && kk == 1) evv[ei] = cw_add_f32(evv[ei], (*xr)[e]);
+            else if (RES && kk == P + 1) t0 = ei == 0 ? sp_mix_join<0>(rh, rl) : sp_mix_join<1>(rh, rl);
+            else if (RES && kk == P + 2) evv[ei] = cw_add_f32(evv[ei], t0);
+        } else {
+            const int kk = k - 2 * E1;
+            if (kk == 0) mx = sp_max3_abs(mx, evv[0], evv[1]);                                // what the reference would carry on ...
+            else if (kk == 1) evv[0] = __builtin_amdgcn_fmed3f(evv[0], lo_clamp, SP_F16_MAX);  // ... is clamped here (ReLU in the same median)
+            else if (kk == 2) evv[1] = __builtin_amdgcn_fmed3f(evv[1], lo_clamp, SP_F16_MAX);
+            else if (kk == 3) hpk[pr] = sp_cvt_pk(evv[0], evv[1]);
+            else if (kk == 4) sc[0] = sp_mix_diff<0>(hpk[pr], evv[0]);
+            else if (kk == 5) sc[1] = sp_mix_diff<1>(hpk[pr], evv[1]);
+            else if (kk == 6) lpk[pr] = sp_scale_cvt_lo(sc[0]);
+            else lpk[pr] = sp_scale_cvt_hi(lpk[pr], sc[1]);
+        }
+    }
+    __device__ __forceinline__ void store(int plane, const SpOut& out, unsigned off, bool store_ok) {
+        if (plane == 0) {
+            if (store_ok) *(cv_u32x2*)(out.hi + off) = (cv_u32x2){hpk[0], hpk[1]};
+        } else if (store_ok) *(__attribute__((address_space(1))) cv_u32x2*)(out.lo + off) = (cv_u32x2){lpk[0], lpk[1]};
+    }
+};
+// One LDS-DMA piece: the 64 cells pc of strip c of an image (strips are gblk bytes apart in global memory, lblk in LDS; dst0 = the image's
+// LDS address) in one global_load_lds_dwordx4 under the exec mask `mask`; lane_src = the lane's byte offset inside the strip (sp_dma_plan).
+// NT: streaming lines (k_conv3x3_sp2p: the image is read by the two cout groups of an XCD at about the same time, then never again).
+#define SP_DMA_ASM(POLICY) "s_mov_b64 exec, %0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3" POLICY "\n\ts_mov_b64 exec, -1"
+template <bool NT = false>
+__device__ __forceinline__ void sp_dma_piece(const unsigned char* src, unsigned dst0, int c, int pc, int gblk, int lblk, unsigned long long mask, unsigned lane_src) {
+    const unsigned long long base = (unsigned long long)(src + (size_t)c * gblk);
+    const unsigned dst = dst0 + (unsigned)(c * lblk + pc * 1024);
+    if constexpr (NT) asm volatile(SP_DMA_ASM(" nt") : : "s"(mask), "s"(dst), "v"(lane_src), "s"(base) : "memory");
+    else asm volatile(SP_DMA_ASM("") : : "s"(mask), "s"(dst), "v"(lane_src), "s"(base) : "memory");
+}
+// The lane plan of an image's pieces: src_off(cell) = byte offset of image cell `cell` inside a strip in global memory, or < 0 for a cell
+// the DMA never writes (zero padding; from the geometry's pos_of_cell) -> per piece the lane's source offset and the exec mask
+template <int NP, class F> __device__ __forceinline__ void sp_dma_plan(unsigned (&dsrc)[NP], unsigned long long (&dmask)[NP], int lane, F src_off) {
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        const int o = src_off(64 * i + lane);
+        dsrc[i] = (unsigned)(o < 0 ? 0 : o);
+        dmask[i] = __builtin_amdgcn_ballot_w64(o >= 0);
+    }
+}
+// byte offset of the B fragment of k-step s = (tap, k-sub of 32 channels) from a lane's (-1, -1) neighbour cell: rows are `pitch` cells
+// apart, a k-sub is 4 strips of blk bytes
+__host__ __device__ constexpr int sp_frag_off(int s, int ksub, int pitch, int blk) {
+    const int tap = s / ksub;
+    return ((tap / 3) * pitch + (tap % 3)) * 16 + (s % ksub) * (4 * blk);
+}
+// workgroup -> (cout group, board slot).  Workgroups are dealt to the 8 XCDs round-robin; when the grid allows it the ncg groups of a
+// board are workgroups b and b + 8, ... (same XCD, launched together): the board's second read hits that XCD's L2.
+__device__ __forceinline__ void sp_wg_map(int ncg, int& cg, int& slot, int& nslot) {
+    const int b = (int)blockIdx.x, nb = (int)gridDim.x;
+    nslot = nb / ncg;
+    if (nb % (8 * ncg) == 0) {
+        const int xcd = b & 7, k = b >> 3;
+        cg = k % ncg;
+        slot = xcd + 8 * (k / ncg);
+    } else {
+        cg = b % ncg;
+        slot = b / ncg;
+    }
+}
+// the compiler's wait for the weight loads belongs in front of the board loop (see az_conv.h): the A fragments are pinned here, the first
+// NF_A of them in AGPRs (read by the MFMA in place)
+template <int NF_A, int NF> __device__ __forceinline__ void sp_pin_a(const sp_f16x8 (&wf)[NF]) {
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+        if (f < NF_A) asm volatile("" : : "a"(wf[f]));
+        else asm volatile("" : : "v"(wf[f]));
+    }
+}
 
 // fp32 channels-last rows [boards * P2][C] <-> split layout; one thread per (board, chunk, position), positions fastest
 // (the 16-byte accesses of the split side are contiguous per chunk strip)
@@ -379,33 +487,19 @@ __device__ __forceinline__ void sp_mfma_a0(c6_f32x4& acc, const sp_f16x8& wa, co
 }
 // Vector-memory instructions a wave of k_conv3x3_sp issues between the last LDS-DMA piece of the next board (unit 0, k-step NPIECE) and
 // the board's barrier (unit 1, k-step KS - 2): the stores of the riding epilogues (2 per column tile) and unit 1's residual loads (2 per
-// column tile, first slots of the unit).  Mirrors the kernel's schedule (same constants, same SpSpread arithmetic).
-// Slots of the B-fragment ring (k-steps): a fragment is requested R - 1 k-steps before its MFMAs.  (Round 5 tried 4 slots on the plain
+// column tile, first slots of the unit).  Mirrors the kernel's schedule (same constants, the kernel's SpSpread): unit I's share.
+// (The B-fragment ring has 3 slots = k-steps: a fragment is requested 2 k-steps before its MFMAs.  Round 5 tried 4 slots on the plain
 // 128-filter layer after the PMC wave-cycle breakdown showed 14 - 15 % of the wave time parked at s_waitcnt: no gain on the same box,
 // 1.792 vs 1.794 ms, profiles/r05_split_ablation.txt -- the waits are not fragment latency here; the skip layer has no registers for it.)
-__host__ __device__ constexpr int sp9_ring(int, bool) { return 3; }
+template <bool RES, int NCH, bool XLO0, int I> __host__ __device__ constexpr int sp9_vm_unit() {
+    constexpr int KSUB = NCH / 4, KS = 9 * KSUB, R = 3, S0 = 6, NP = (SpGeo9::CELLS + 63) / 64, NPIECE = NP * ((XLO0 ? 1 : 2) * NCH / 4);
+    constexpr int CT_OPS = sp_epi_ct_ops(RES), nj = I == 0 ? 3 : 2, pnj = I == 0 ? 2 : 3, NQ = (XLO0 ? 2 : 3) * nj, P_OPS = pnj * CT_OPS;
+    constexpr int AVAIL = (I == 1 ? (KS - (R - 1)) * NQ : NQ * KS - 4) - S0;
+    // a DMA piece is issued behind all MFMA slots of its k-step; unit 0 loads its residual in its first slots, before the first piece
+    return sp_epi_stores_behind<SpSpread<P_OPS, S0, AVAIL>>(pnj, CT_OPS, NQ, I > 0 ? -1 : NPIECE) + (RES && I > 0 ? 2 * nj : 0);
+}
 template <bool RES, int NCH, bool XLO0 = false> __host__ __device__ constexpr int sp9_vm_younger() {
-    constexpr int KSUB = NCH / 4, KS = 9 * KSUB, R = sp9_ring(NCH, RES), S0 = 6, NP = (SpGeo9::CELLS + 63) / 64, NPIECE = NP * ((XLO0 ? 1 : 2) * NCH / 4);
-    constexpr int CT_OPS = sp_epi_ct_ops(RES);
-    int n = 0;
-    for (int i = 0; i < 2; ++i) {
-        const int nj = i == 0 ? 3 : 2, pnj = i == 0 ? 2 : 3, NQ = (XLO0 ? 2 : 3) * nj, P_OPS = pnj * CT_OPS;
-        const int AVAIL = (i == 1 ? (KS - (R - 1)) * NQ : NQ * KS - 4) - S0;
-        auto cum = [&](int sl) {
-            if (sl < S0) return 0;
-            const long long c = ((long long)(sl - S0 + 1) * P_OPS + AVAIL - 1) / AVAIL;
-            return c > P_OPS ? P_OPS : (int)c;
-        };
-        for (int c = 0; c < pnj; ++c)
-            for (int st = 0; st < 2; ++st) {  // the two stores of column tile c are its last two micro-ops
-                const int o = c * CT_OPS + CT_OPS - 2 + st;
-                int sl = S0;
-                while (cum(sl) <= o) ++sl;
-                if (i > 0 || sl / NQ > NPIECE) ++n;  // a DMA piece is issued behind all MFMA slots of its k-step
-            }
-        if (RES && i > 0) n += 2 * nj;  // (unit 0 loads its residual in its first slots, before the first piece)
-    }
-    return n;
+    return sp9_vm_unit<RES, NCH, XLO0, 0>() + sp9_vm_unit<RES, NCH, XLO0, 1>();
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -426,7 +520,7 @@ k_conv3x3_sp(const unsigned char* __restrict__ x, const _Float16* __restrict__ w
     typedef SpGeo9 G;
     constexpr int C = 64 * NCG, CIN = 8 * NCH, KSUB = NCH / 4;
     constexpr int KS = 9 * KSUB;                             // k-steps per unit (one tap x 32 input channels)
-    constexpr int NJ0 = 3, NJ1 = 2, R = sp9_ring(NCH, RES);       // column tiles of unit 0 / unit 1, ring slots (k-steps)
+    constexpr int NJ0 = 3, NJ1 = 2, R = 3;                   // column tiles of unit 0 / unit 1, ring slots (k-steps, see sp9_vm_unit)
     constexpr int LBLK = G::CELLS * 16, LPLANE = NCH * LBLK, LBUF = 2 * LPLANE;
     constexpr int GBLK = G::P2 * 16, XPLANE = NCH * GBLK, XTILE = 2 * XPLANE;
     constexpr int YPLANE = (C / 8) * GBLK, YTILE = 2 * YPLANE;
@@ -435,7 +529,7 @@ k_conv3x3_sp(const unsigned char* __restrict__ x, const _Float16* __restrict__ w
     constexpr int NPROD = XLO0 ? 2 : 3;                               // MFMA products per multiply
     static_assert(!XLO0 || (!RES && NCH == 4), "exact-f16 inputs: the stem");
     constexpr int NF = 2 * KS, NF_A = NF < 64 ? NF : 64;
-    constexpr int E1 = sp_epi_e1(RES), PAIR = sp_epi_pair(RES), CT_OPS = sp_epi_ct_ops(RES);  // epilogue micro-ops (see sp_epi_e1)
+    constexpr int PAIR = sp_epi_pair(RES), CT_OPS = sp_epi_ct_ops(RES);  // epilogue micro-ops (see sp_epi_e1)
     constexpr int S0 = 6;                                    // first MFMA slot of a unit that may touch the previous unit's accumulators
     static_assert((2 * KS) % R == 0, "a board's k-steps keep the ring phase");
     static_assert(KS - 1 >= NPIECE, "the next board's pieces ride in unit 0");
@@ -449,21 +543,8 @@ k_conv3x3_sp(const unsigned char* __restrict__ x, const _Float16* __restrict__ w
     const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, kg = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds;
-    // workgroup -> (cout group, board slot).  Workgroups are dealt to the 8 XCDs round-robin; when the grid allows it the NCG groups of a
-    // board are workgroups b and b + 8, ... (same XCD, launched together): the board's second read hits that XCD's L2.
     int cg, slot, nslot;
-    {
-        const int b = (int)blockIdx.x, nb = (int)gridDim.x;
-        nslot = nb / NCG;
-        if (nb % (8 * NCG) == 0) {
-            const int xcd = b & 7, k = b >> 3;
-            cg = k % NCG;
-            slot = xcd + 8 * (k / NCG);
-        } else {
-            cg = b % NCG;
-            slot = b / NCG;
-        }
-    }
+    sp_wg_map(NCG, cg, slot, nslot);
     for (int i = tid; i < (SIDE0 + 16 * SIDE_BOARD) / 16; i += CW_THREADS) *(cv_u32x4*)(lds + i * 16) = (cv_u32x4){0u, 0u, 0u, 0u};
     CV_BARRIER();  // the zero cells are final before any LDS-DMA piece can land
     if (slot >= ntiles) return;  // (uniform per workgroup)
@@ -484,21 +565,9 @@ k_conv3x3_sp(const unsigned char* __restrict__ x, const _Float16* __restrict__ w
     // LDS-DMA plan: a strip is NP pieces of 64 cells; wave q moves strips SPW q .. SPW q + SPW - 1 (strip = plane * NCH + chunk)
     unsigned dsrc[NP];
     unsigned long long dmask[NP];
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-        const int p = 64 * i + lane < G::CELLS ? G::pos_of_cell(64 * i + lane) : -1;
-        dsrc[i] = (unsigned)((p < 0 ? 0 : p) * 16);
-        dmask[i] = __builtin_amdgcn_ballot_w64(p >= 0);
-    }
+    sp_dma_plan(dsrc, dmask, lane, [](int cell) { return cell < G::CELLS ? G::pos_of_cell(cell) * 16 : -1; });
     auto dma_piece = [&](const unsigned char* src, unsigned dstbuf, bool live, int i) {
-        const int c = SPW * wave + i / NP, pc = i % NP;
-        const unsigned long long base = (unsigned long long)(src + (size_t)c * GBLK);
-        const unsigned long long mask = live ? dmask[pc] : 0ull;
-        const unsigned dst = dstbuf + (unsigned)(c * LBLK + pc * 1024);
-        asm volatile("s_mov_b64 exec, %0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b64 exec, -1"
-                     :
-                     : "s"(mask), "s"(dst), "v"(dsrc[pc]), "s"(base)
-                     : "memory");
+        sp_dma_piece(src, dstbuf, SPW * wave + i / NP, i % NP, GBLK, LBLK, live ? dmask[i % NP] : 0ull, dsrc[i % NP]);
     };
     unsigned lmap[G::NCT];
 #pragma unroll
@@ -521,27 +590,18 @@ k_conv3x3_sp(const unsigned char* __restrict__ x, const _Float16* __restrict__ w
         return v;
     };
     sp_f16x8 bb[R][2][NJ0];  // ring of B fragments [k-step slot][plane][column tile of the unit]
-    auto load_step = [&](const unsigned char* img, int j0, int nj, int s, int rs) {
-        const int tap = s / KSUB;
-        const int off = ((tap / 3) * G::PITCH + (tap % 3)) * 16 + (s % KSUB) * (4 * LBLK);
-#pragma unroll
-        for (int j = 0; j < NJ0; ++j)
-            if (j < nj) bb[rs][0][j] = *(const sp_f16x8*)(img + (lmap[j0 + j] & 0xffffu) + off);
-        if constexpr (!XLO0) {
-#pragma unroll
-            for (int j = 0; j < NJ0; ++j)
-                if (j < nj) bb[rs][1][j] = *(const sp_f16x8*)(img + (lmap[j0 + j] & 0xffffu) + off + LPLANE);
-        }
-    };
-
     // fragment f of a k-step (plane f / nj, column tile f % nj): inside the units the requests are SPREAD over the first MFMA gaps of the
     // k-step R - 1 before their use -- one ds_read_b128 per gap instead of a burst of 2 nj reads in front of a k-step, during which no
     // MFMA is issued (measured on k_conv3x3_sp2, same box: -4.0 % plain / -3.5 % residual per launch, bit-identical)
     auto load_frag = [&](const unsigned char* img, int j0, int nj, int s, int rs, int f) __attribute__((always_inline)) {
-        const int tap = s / KSUB;
-        const int off = ((tap / 3) * G::PITCH + (tap % 3)) * 16 + (s % KSUB) * (4 * LBLK);
+        const int off = sp_frag_off(s, KSUB, G::PITCH, LBLK);
         const int pl = f / nj, j = f % nj;
         bb[rs][pl][j] = *(const sp_f16x8*)(img + (lmap[j0 + j] & 0xffffu) + off + pl * LPLANE);
+    };
+    auto load_step = [&](const unsigned char* img, int j0, int nj, int s, int rs) {  // all fragments of a k-step at once (the prologue)
+#pragma unroll
+        for (int f = 0; f < (XLO0 ? 1 : 2) * NJ0; ++f)
+            if (f < (XLO0 ? 1 : 2) * nj) load_frag(img, j0, nj, s, rs, f);
     };
 
     {   // first board: all pieces at once, then the first fragments
@@ -553,51 +613,16 @@ k_conv3x3_sp(const unsigned char* __restrict__ x, const _Float16* __restrict__ w
 #pragma unroll
         for (int s = 0; s < R - 1; ++s) load_step(lds, 0, NJ0, s, s);
     }
-#pragma unroll
-    for (int f = 0; f < NF; ++f) {  // the compiler's wait for the weight loads belongs in front of the loop (see az_conv.h)
-        if (f < NF_A) asm volatile("" : : "a"(wf[f]));
-        else asm volatile("" : : "v"(wf[f]));
-    }
+    sp_pin_a<NF_A>(wf);
     asm volatile("" : : "v"(bv), "v"(lmap[0]), "v"(lmap[G::NCT - 1]), "v"(dsrc[0]), "v"(dsrc[NP - 1]));
 
-    c6_f32x4 accm[2][NJ0], accc[2][NJ0];  // [unit][column tile of the unit]
-    cv_u32x2 rr[2][NJ0][2];             // residual of a unit: [unit][column tile][plane]
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int j = 0; j < NJ0; ++j) {
-            accm[a][j] = (c6_f32x4){0.0f, 0.0f, 0.0f, 0.0f}, accc[a][j] = (c6_f32x4){0.0f, 0.0f, 0.0f, 0.0f};
-            rr[a][j][0] = (cv_u32x2){0u, 0u}, rr[a][j][1] = (cv_u32x2){0u, 0u};
-        }
-    float evv[2] = {0.0f, 0.0f}, sc[2] = {0.0f, 0.0f}, t0 = 0.0f, mx = 0.0f;  // mx: the largest |value| this lane produced (range record, sp_range_report)
-    unsigned hpk[2] = {0u, 0u}, lpk[2] = {0u, 0u};
+    c6_f32x4 accm[2][NJ0] = {}, accc[2][NJ0] = {};  // [unit][column tile of the unit]
+    cv_u32x2 rr[2][NJ0][2] = {};                    // residual of a unit: [unit][column tile][plane]
+    SpEpi ep;
     // micro-op `o` of the epilogue of column tile j (lmap index mj) of the unit with accumulator set `set`: ONE VALU / memory instruction
-    auto epi_op = [&](int set, int j, int mj, unsigned char* out, sp_gptr out_lo, int o, bool store_ok) {
-        if (o < 2 * PAIR) {
-            const int pr = o / PAIR, k = o % PAIR;  // pair pr = elements 2 pr, 2 pr + 1 (one packed dword of each plane)
-            if (k < 2 * E1) {
-                const int ei = k / E1, kk = k % E1, e = 2 * pr + ei;
-                const unsigned rh = pr == 0 ? rr[set][j][0].x : rr[set][j][0].y, rl = pr == 0 ? rr[set][j][1].x : rr[set][j][1].y;
-                if (kk == 0) evv[ei] = fmaf(accc[set][j][e], SP_INV_SCALE, accm[set][j][e]);
-                else if (RES && kk == 1) t0 = ei == 0 ? sp_mix_join<0>(rh, rl) : sp_mix_join<1>(rh, rl);
-                else if (RES && kk == 2) evv[ei] = cw_add_f32(evv[ei], t0);
-            } else {
-                const int kk = k - 2 * E1;
-                if (kk == 0) mx = sp_max3_abs(mx, evv[0], evv[1]);                                            // what the reference would carry on ...
-                else if (kk == 1) evv[0] = __builtin_amdgcn_fmed3f(evv[0], lo_clamp, SP_F16_MAX);                  // ... is clamped here (ReLU in the same median)
-                else if (kk == 2) evv[1] = __builtin_amdgcn_fmed3f(evv[1], lo_clamp, SP_F16_MAX);
-                else if (kk == 3) hpk[pr] = sp_cvt_pk(evv[0], evv[1]);
-                else if (kk == 4) sc[0] = sp_mix_diff<0>(hpk[pr], evv[0]);
-                else if (kk == 5) sc[1] = sp_mix_diff<1>(hpk[pr], evv[1]);
-                else if (kk == 6) lpk[pr] = sp_scale_cvt_lo(sc[0]);
-                else lpk[pr] = sp_scale_cvt_hi(lpk[pr], sc[1]);
-            }
-        } else {
-            const unsigned gq = out_off(mj);
-            if (o == 2 * PAIR) {
-                if (store_ok) *(cv_u32x2*)(out + gq) = (cv_u32x2){hpk[0], hpk[1]};
-            } else if (store_ok) *(__attribute__((address_space(1))) cv_u32x2*)(out_lo + gq) = (cv_u32x2){lpk[0], lpk[1]};
-        }
+    auto epi_op = [&](int set, int j, int mj, const SpOut& out, int o, bool store_ok) {
+        if (o < 2 * PAIR) ep.op<RES>(o, accm[set][j], accc[set][j], rr[set][j], lo_clamp);
+        else ep.store(o - 2 * PAIR, out, out_off(mj), store_ok);
     };
 
     // Corner side buffer.  Thread tid < 8 NCH copies one 16-byte cell per board: cell index c = tid = ((kg * 4 + tap) * 2 + plane) * KSUB + ks
@@ -614,8 +639,7 @@ k_conv3x3_sp(const unsigned char* __restrict__ x, const _Float16* __restrict__ w
     static_assert(KS >= 6, "the side-buffer copy rides in unit 0");
 
     int it = 0;
-    unsigned char* yprev = y;
-    sp_gptr yprev_lo = (sp_gptr)(unsigned long long)y;
+    SpOut yprev = {y, (sp_gptr)(unsigned long long)y};
     for (int tile = slot; tile < ntiles; tile += nslot, ++it) {
         const int buf = it & 1;
         const unsigned char* Xs = lds + buf * LBUF;
@@ -624,14 +648,7 @@ k_conv3x3_sp(const unsigned char* __restrict__ x, const _Float16* __restrict__ w
         const unsigned char* nsrc = x + (size_t)(has_next ? tile + nslot : tile) * XTILE;
         const unsigned ndst = lds0 + (unsigned)((buf ^ 1) * LBUF);
         const size_t yo = (size_t)tile * YTILE + (size_t)(cg * 8 + wave * 2) * GBLK;  // uniform: the lane part is in lmap
-        const unsigned char* rbase = RES ? res + yo : nullptr;
-        unsigned char* ybase = y + yo;
-        // one uniform base per plane, opaque to the compiler (it would otherwise fold base + YPLANE + lane offset into 64-bit VALU adds per
-        // access: YPLANE exceeds the 13-bit immediate): every residual load / y store is scalar base + 32-bit lane offset
-        unsigned long long rlo = (unsigned long long)(RES ? res + yo : y + yo) + YPLANE, ylo = (unsigned long long)(y + yo) + YPLANE;
-        asm volatile("" : "+s"(rlo), "+s"(ylo));
-        const sp_gcptr rbase_lo = (sp_gcptr)rlo;
-        const sp_gptr ybase_lo = (sp_gptr)ylo;
+        const SpOut rbase = sp_out_base(RES ? res + yo : y + yo, YPLANE), ybase = sp_out_base(y + yo, YPLANE);
         const bool have_prev = it > 0;
         auto unit = [&](auto IC) __attribute__((always_inline)) {
             constexpr int i = decltype(IC)::value, set = i, pset = i ^ 1;
@@ -644,8 +661,7 @@ k_conv3x3_sp(const unsigned char* __restrict__ x, const _Float16* __restrict__ w
             constexpr int AVAIL = (i == 1 ? (KS - (R - 1)) * NQ : NQ * KS - 4) - S0;
             typedef SpSpread<P_OPS, S0, AVAIL> SP;
             static_assert(SP::MAXPER <= (NCH >= 16 ? 1 : NCH >= 8 ? 2 : XLO0 ? 6 : 4), "the previous unit's epilogue fits this unit's MFMA gaps");
-            unsigned char* pout = i == 0 ? yprev : ybase;
-            const sp_gptr pout_lo = i == 0 ? yprev_lo : ybase_lo;
+            const SpOut pout = i == 0 ? yprev : ybase;
             const bool pstore = i > 0 || have_prev;
             cp_for_each([&](auto TC) __attribute__((always_inline)) {
                 constexpr int t = decltype(TC)::value;
@@ -687,12 +703,11 @@ k_conv3x3_sp(const unsigned char* __restrict__ x, const _Float16* __restrict__ w
                     constexpr int sl = t * NQ + q;  // MFMA slot of the unit
                     cp_for_each([&](auto KC) __attribute__((always_inline)) {
                         constexpr int o = SP::cum(sl - 1) + decltype(KC)::value;
-                        if constexpr (o < SP::cum(sl)) epi_op(pset, o / CT_OPS, pj0 + o / CT_OPS, pout, pout_lo, o % CT_OPS, pstore);
+                        if constexpr (o < SP::cum(sl)) epi_op(pset, o / CT_OPS, pj0 + o / CT_OPS, pout, o % CT_OPS, pstore);
                     }, typename CpMakeSeq<SP::MAXPER>::type{});
                     if constexpr (RES && sl < 2 * nj) {  // this unit's residual (used by its epilogue inside the next unit)
                         constexpr int rj = sl >> 1, rp = sl & 1;
-                        if constexpr (rp == 0) rr[set][rj][rp] = *(const cv_u32x2*)(rbase + out_off(j0 + rj));
-                        else rr[set][rj][rp] = *(const __attribute__((address_space(1))) cv_u32x2*)(rbase_lo + out_off(j0 + rj));
+                        rr[set][rj][rp] = sp_load8(rbase, rp, out_off(j0 + rj));
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }, typename CpMakeSeq<NQ>::type{});
@@ -708,7 +723,7 @@ k_conv3x3_sp(const unsigned char* __restrict__ x, const _Float16* __restrict__ w
         };
         unit(CpInt<0>{});
         unit(CpInt<1>{});
-        yprev = ybase, yprev_lo = ybase_lo;
+        yprev = ybase;
         if ((it & 15) == 15 || !has_next) {
             // ---- the corner (8, 0) of the last (it & 15) + 1 boards: a [16 couts] x [<= 16 boards] x [4 taps x cin] tile per wave on the resident
             // filter banks.  The side buffer is complete: every wave passed this board's barrier after the copy of its column.
@@ -766,7 +781,7 @@ k_conv3x3_sp(const unsigned char* __restrict__ x, const _Float16* __restrict__ w
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 v[e] = fmaxf(v[e], lo_relu);
-                if (l15 < n_ok) mx = fmaxf(mx, fabsf(v[e]));
+                if (l15 < n_ok) ep.mx = fmaxf(ep.mx, fabsf(v[e]));
                 sp_split(v[e], h[e], l[e]);
             }
             if (l15 < n_ok) {
@@ -781,8 +796,8 @@ k_conv3x3_sp(const unsigned char* __restrict__ x, const _Float16* __restrict__ w
 #pragma unroll
     for (int j = 0; j < NJ1; ++j)
 #pragma unroll
-        for (int o = 0; o < CT_OPS; ++o) epi_op(1, j, NJ0 + j, yprev, yprev_lo, o, true);
-    sp_range_report(mx, range);
+        for (int o = 0; o < CT_OPS; ++o) epi_op(1, j, NJ0 + j, yprev, o, true);
+    sp_range_report(ep.mx, range);
 }
 
 #endif  // __HIPCC__

@@ -26,6 +26,8 @@
 //     halves, packed converts: 38 micro-ops per column tile against 54 MFMAs); the B-fragment ring (3 k-steps) runs on across units, tiles and boards.
 //   * NCH = 4 is the STEM (17 planes padded to 32 channels -> 64): the input is the 13x13 feature board of azsp_split_features, embedded
 //     at (2, 2) of the zero 17x17 plane by the DMA masks -- a pad-3 convolution of the board IS the pad-1 convolution of that plane.
+// The epilogue's registers and micro-ops (SpEpi), the LDS-DMA piece and its lane plan (sp_dma_piece, sp_dma_plan), the fragment offset, the
+// output bases and the A-fragment pinning are the ones of az_conv_sp.h, shared by the four weight-stationary kernels; the unit schedule is this kernel's.
 // Per board and wave: 19 column tiles x 18 k-steps x 3 products = 1026 MFMAs (v_mfma_f32_16x16x32_f16); HBM: each tensor once
 // (the halo rows 8 / 9 are read by both tiles of a board: the second read is an L2 hit).
 #pragma once
@@ -123,31 +125,17 @@ static_assert(sp17_uj0(0, 3) + sp17_unj(0, 3) == Sp17Geo::NCT0 && sp17_uj0(1, 3)
 
 // Vector-memory instructions a wave issues between the last LDS-DMA piece of the next tile (unit 0, k-step NPIECE) and the barrier of
 // the tile (unit 3, k-step KS - 2) of half h: the stores of the riding epilogues (2 per column tile) and the residual loads (2 per
-// column tile, first slots of a unit).  Mirrors the schedule of k_conv3x3_sp17 below (same constants, same SpSpread).
-template <bool RES, int NCH, bool XLO0 = false> __host__ __device__ constexpr int sp17_vm_younger(int h) {
+// column tile, first slots of a unit).  Mirrors the schedule of k_conv3x3_sp17 below (same constants, the kernel's SpSpread): unit U's share.
+template <bool RES, int NCH, bool XLO0, int H, int U> __host__ __device__ constexpr int sp17_vm_unit() {
     constexpr int KSUB = NCH / 4, KS = 9 * KSUB, R = 3, S0 = 6, NP = (Sp17Geo::CELLS + 63) / 64, NPIECE = NP * ((XLO0 ? 1 : 2) * NCH / 4);
-    constexpr int CT_OPS = sp_epi_ct_ops(RES);
-    int n = 0;
-    for (int u = 0; u < 4; ++u) {
-        const int nj = sp17_unj(h, u), NQ = (XLO0 ? 2 : 3) * nj;
-        const int ph = u == 0 ? h ^ 1 : h, pu = (u + 3) & 3, pnj = sp17_unj(ph, pu), P_OPS = pnj * CT_OPS;
-        const int AVAIL = (u == 3 ? (KS - (R - 1)) * NQ : NQ * KS - 4) - S0;
-        // slot -> cumulative micro-ops (SpSpread::cum with run-time arguments)
-        auto cum = [&](int sl) {
-            if (sl < S0) return 0;
-            const long long c = ((long long)(sl - S0 + 1) * P_OPS + AVAIL - 1) / AVAIL;
-            return c > P_OPS ? P_OPS : (int)c;
-        };
-        for (int c = 0; c < pnj; ++c)
-            for (int st = 0; st < 2; ++st) {  // the two stores of column tile c are its last two micro-ops
-                const int o = c * CT_OPS + CT_OPS - 2 + st;
-                int sl = S0;
-                while (cum(sl) <= o) ++sl;
-                if (u > 0 || sl / NQ > NPIECE) ++n;  // a DMA piece is issued behind all MFMA slots of its k-step
-            }
-        if (RES && u > 0) n += 2 * nj;  // (unit 0 loads its residual in its first slots, before the first piece)
-    }
-    return n;
+    constexpr int CT_OPS = sp_epi_ct_ops(RES), nj = sp17_unj(H, U), NQ = (XLO0 ? 2 : 3) * nj;
+    constexpr int pnj = sp17_unj(U == 0 ? H ^ 1 : H, (U + 3) & 3), P_OPS = pnj * CT_OPS;
+    constexpr int AVAIL = (U == 3 ? (KS - (R - 1)) * NQ : NQ * KS - 4) - S0;
+    // a DMA piece is issued behind all MFMA slots of its k-step; unit 0 loads its residual in its first slots, before the first piece
+    return sp_epi_stores_behind<SpSpread<P_OPS, S0, AVAIL>>(pnj, CT_OPS, NQ, U > 0 ? -1 : NPIECE) + (RES && U > 0 ? 2 * nj : 0);
+}
+template <bool RES, int NCH, bool XLO0, int H> __host__ __device__ constexpr int sp17_vm_younger() {
+    return sp17_vm_unit<RES, NCH, XLO0, H, 0>() + sp17_vm_unit<RES, NCH, XLO0, H, 1>() + sp17_vm_unit<RES, NCH, XLO0, H, 2>() + sp17_vm_unit<RES, NCH, XLO0, H, 3>();
 }
 
 // NCH = input-channel chunks of 8: 8 = tower layer (64 -> 64), 4 = stem (17 planes padded to 32 -> 64, 13x13 input board at (2, 2)).
@@ -170,7 +158,7 @@ k_conv3x3_sp17(const unsigned char* __restrict__ x, const _Float16* __restrict__
     constexpr int NPROD = XLO0 ? 2 : 3;
     static_assert(!XLO0 || (!RES && NCH == 4), "exact-f16 inputs: the stem");
     constexpr int NF = 2 * KS;
-    constexpr int E1 = sp_epi_e1(RES), PAIR = sp_epi_pair(RES), CT_OPS = sp_epi_ct_ops(RES);  // epilogue micro-ops (az_conv_sp.h sp_epi_e1)
+    constexpr int PAIR = sp_epi_pair(RES), CT_OPS = sp_epi_ct_ops(RES);  // epilogue micro-ops (az_conv_sp.h sp_epi_e1)
     constexpr int S0 = 6;                                    // first MFMA slot of a unit that may touch the previous unit's accumulators
     static_assert(NF <= 64, "all A fragments live in AGPRs");
     static_assert((4 * KS) % R == 0, "a tile's k-steps keep the ring phase");
@@ -203,22 +191,9 @@ k_conv3x3_sp17(const unsigned char* __restrict__ x, const _Float16* __restrict__
     unsigned dsrc[2][NP];
     unsigned long long dmask[2][NP];
 #pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            const int p = G::pos_of_cell(h, 64 * i + lane, IN_S, IN_OFF);
-            dsrc[h][i] = (unsigned)((p < 0 ? 0 : p) * 16);
-            dmask[h][i] = __builtin_amdgcn_ballot_w64(p >= 0);
-        }
+    for (int h = 0; h < 2; ++h) sp_dma_plan(dsrc[h], dmask[h], lane, [h](int cell) { return G::pos_of_cell(h, cell, IN_S, IN_OFF) * 16; });
     auto dma_piece = [&](const unsigned char* src, unsigned dstbuf, bool live, int h, int i) {
-        const int c = SPW * wave + i / NP, pc = i % NP;
-        const unsigned long long base = (unsigned long long)(src + (size_t)c * GBLK_IN);
-        const unsigned long long mask = live ? dmask[h][pc] : 0ull;
-        const unsigned dst = dstbuf + (unsigned)(c * LBLK + pc * 1024);
-        asm volatile("s_mov_b64 exec, %0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b64 exec, -1"
-                     :
-                     : "s"(mask), "s"(dst), "v"(dsrc[h][pc]), "s"(base)
-                     : "memory");
+        sp_dma_piece(src, dstbuf, SPW * wave + i / NP, i % NP, GBLK_IN, LBLK, live ? dmask[h][i % NP] : 0ull, dsrc[h][i % NP]);
     };
     unsigned lmap[G::NCT];
 #pragma unroll
@@ -231,26 +206,17 @@ k_conv3x3_sp17(const unsigned char* __restrict__ x, const _Float16* __restrict__
     }
     static_assert(G::P2 * 16 + GBLK + 8 < 65536, "output slot offsets fit 16 bits");
     sp_f16x8 bb[R][2][NJM];  // ring of B fragments [k-step slot][plane][column tile of the unit]
-    auto load_step = [&](const unsigned char* img, int j0, int nj, int s, int rs) {
-        const int tap = s / KSUB;
-        const int off = ((tap / 3) * G::PITCH + (tap % 3)) * 16 + (s % KSUB) * (4 * LBLK);
-#pragma unroll
-        for (int j = 0; j < NJM; ++j)
-            if (j < nj) bb[rs][0][j] = *(const sp_f16x8*)(img + (lmap[j0 + j] & 0xffffu) + off);
-        if constexpr (!XLO0) {
-#pragma unroll
-            for (int j = 0; j < NJM; ++j)
-                if (j < nj) bb[rs][1][j] = *(const sp_f16x8*)(img + (lmap[j0 + j] & 0xffffu) + off + LPLANE);
-        }
-    };
-
     // fragment f of a k-step (plane f / nj, column tile f % nj): inside the units the requests are spread over the first MFMA gaps of the
     // k-step R - 1 before their use (one ds_read_b128 per gap instead of a burst in front of a k-step; see k_conv3x3_sp)
     auto load_frag = [&](const unsigned char* img, int j0, int nj, int s, int rs, int f) __attribute__((always_inline)) {
-        const int tap = s / KSUB;
-        const int off = ((tap / 3) * G::PITCH + (tap % 3)) * 16 + (s % KSUB) * (4 * LBLK);
+        const int off = sp_frag_off(s, KSUB, G::PITCH, LBLK);
         const int pl = f / nj, j = f % nj;
         bb[rs][pl][j] = *(const sp_f16x8*)(img + (lmap[j0 + j] & 0xffffu) + off + pl * LPLANE);
+    };
+    auto load_step = [&](const unsigned char* img, int j0, int nj, int s, int rs) {  // all fragments of a k-step at once (the prologue)
+#pragma unroll
+        for (int f = 0; f < (XLO0 ? 1 : 2) * NJM; ++f)
+            if (f < (XLO0 ? 1 : 2) * nj) load_frag(img, j0, nj, s, rs, f);
     };
 
     {   // first tile (upper half of the first board): all pieces at once, then the first fragments
@@ -262,65 +228,26 @@ k_conv3x3_sp17(const unsigned char* __restrict__ x, const _Float16* __restrict__
 #pragma unroll
         for (int s = 0; s < R - 1; ++s) load_step(lds, sp17_uj0(0, 0), sp17_unj(0, 0), s, s);
     }
-#pragma unroll
-    for (int f = 0; f < NF; ++f) asm volatile("" : : "a"(wf[f]));  // the compiler's wait for the weight loads belongs in front of the loop
+    sp_pin_a<NF>(wf);
     asm volatile("" : : "v"(bv), "v"(lmap[0]), "v"(lmap[G::NCT - 1]), "v"(dsrc[0][0]), "v"(dsrc[1][NP - 1]));
 
-    c6_f32x4 accm[2][NJM], accc[2][NJM];  // [unit parity][column tile of the unit]
-    cv_u32x2 rr[2][NJM][2];               // residual of a unit: [unit parity][column tile][plane]
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int j = 0; j < NJM; ++j) {
-            accm[a][j] = (c6_f32x4){0.0f, 0.0f, 0.0f, 0.0f}, accc[a][j] = (c6_f32x4){0.0f, 0.0f, 0.0f, 0.0f};
-            rr[a][j][0] = (cv_u32x2){0u, 0u}, rr[a][j][1] = (cv_u32x2){0u, 0u};
-        }
-    float evv[2] = {0.0f, 0.0f}, sc[2] = {0.0f, 0.0f}, t0 = 0.0f, mx = 0.0f;  // mx: largest |value| this lane produced (range record)
-    unsigned hpk[2] = {0u, 0u}, lpk[2] = {0u, 0u};
+    c6_f32x4 accm[2][NJM] = {}, accc[2][NJM] = {};  // [unit parity][column tile of the unit]
+    cv_u32x2 rr[2][NJM][2] = {};                    // residual of a unit: [unit parity][column tile][plane]
+    SpEpi ep;
     // micro-op `o` of the epilogue of column tile j (lmap index mj) of the unit with accumulator set `set`: ONE VALU / memory instruction
-    auto epi_op = [&](int set, int j, int mj, unsigned char* out, sp_gptr out_lo, int o, bool store_ok) {
-        if (o < 2 * PAIR) {
-            const int pr = o / PAIR, k = o % PAIR;  // pair pr = elements 2 pr, 2 pr + 1 (one packed dword of each plane)
-            if (k < 2 * E1) {
-                const int ei = k / E1, kk = k % E1, e = 2 * pr + ei;
-                const unsigned rh = pr == 0 ? rr[set][j][0].x : rr[set][j][0].y, rl = pr == 0 ? rr[set][j][1].x : rr[set][j][1].y;
-                if (kk == 0) evv[ei] = fmaf(accc[set][j][e], SP_INV_SCALE, accm[set][j][e]);
-                else if (RES && kk == 1) t0 = ei == 0 ? sp_mix_join<0>(rh, rl) : sp_mix_join<1>(rh, rl);
-                else if (RES && kk == 2) evv[ei] = cw_add_f32(evv[ei], t0);
-            } else {
-                const int kk = k - 2 * E1;
-                if (kk == 0) mx = sp_max3_abs(mx, evv[0], evv[1]);                                            // what the reference would carry on ...
-                else if (kk == 1) evv[0] = __builtin_amdgcn_fmed3f(evv[0], lo_clamp, SP_F16_MAX);                  // ... is clamped here (ReLU in the same median)
-                else if (kk == 2) evv[1] = __builtin_amdgcn_fmed3f(evv[1], lo_clamp, SP_F16_MAX);
-                else if (kk == 3) hpk[pr] = sp_cvt_pk(evv[0], evv[1]);
-                else if (kk == 4) sc[0] = sp_mix_diff<0>(hpk[pr], evv[0]);
-                else if (kk == 5) sc[1] = sp_mix_diff<1>(hpk[pr], evv[1]);
-                else if (kk == 6) lpk[pr] = sp_scale_cvt_lo(sc[0]);
-                else lpk[pr] = sp_scale_cvt_hi(lpk[pr], sc[1]);
-            }
-        } else {
-            const unsigned gq = lmap[mj] >> 16;
-            if (o == 2 * PAIR) {
-                if (store_ok) *(cv_u32x2*)(out + gq) = (cv_u32x2){hpk[0], hpk[1]};
-            } else if (store_ok) *(__attribute__((address_space(1))) cv_u32x2*)(out_lo + gq) = (cv_u32x2){lpk[0], lpk[1]};
-        }
+    auto epi_op = [&](int set, int j, int mj, const SpOut& out, int o, bool store_ok) {
+        if (o < 2 * PAIR) ep.op<RES>(o, accm[set][j], accc[set][j], rr[set][j], lo_clamp);
+        else ep.store(o - 2 * PAIR, out, lmap[mj] >> 16, store_ok);
     };
 
     int it = 0;
-    unsigned char* yprev = y;
-    sp_gptr yprev_lo = (sp_gptr)(unsigned long long)y;
+    SpOut yprev = {y, (sp_gptr)(unsigned long long)y};
     for (int board = slot; board < nboards; board += nslot, ++it) {
         const bool has_next = board + nslot < nboards;
         const unsigned char* xb = x + (size_t)board * XTILE;
         const unsigned char* xnb = x + (size_t)(has_next ? board + nslot : board) * XTILE;
         const size_t yo = (size_t)board * YTILE + (size_t)(wave * 2) * GBLK;  // uniform: the lane part is in lmap
-        const unsigned char* rbase = RES ? res + yo : nullptr;
-        unsigned char* ybase = y + yo;
-        // one opaque uniform base per plane: every residual load / y store is scalar base + 32-bit lane offset (see k_conv3x3_sp)
-        unsigned long long rlo = (unsigned long long)(RES ? res + yo : y + yo) + YPLANE, ylo = (unsigned long long)(y + yo) + YPLANE;
-        asm volatile("" : "+s"(rlo), "+s"(ylo));
-        const sp_gcptr rbase_lo = (sp_gcptr)rlo;
-        const sp_gptr ybase_lo = (sp_gptr)ylo;
+        const SpOut rbase = sp_out_base(RES ? res + yo : y + yo, YPLANE), ybase = sp_out_base(y + yo, YPLANE);
         const bool have_prev = it > 0;
         // unit U of half H (tile H of the board lives in LDS buffer H)
         auto unit = [&](auto HC, auto UC) __attribute__((always_inline)) {
@@ -340,8 +267,7 @@ k_conv3x3_sp17(const unsigned char* __restrict__ x, const _Float16* __restrict__
             const unsigned char* Xs = lds + H * LBUF;
             const unsigned char* Xn = lds + (H ^ 1) * LBUF;
             // previous unit's output: the first unit of a board finishes the previous board's lower half
-            unsigned char* pout = (H == 0 && U == 0) ? yprev : ybase;
-            const sp_gptr pout_lo = (H == 0 && U == 0) ? yprev_lo : ybase_lo;
+            const SpOut pout = (H == 0 && U == 0) ? yprev : ybase;
             const bool pstore = (H == 0 && U == 0) ? have_prev : true;
             // the tile after this one: the lower half of this board, or the upper half of this workgroup's next board
             const unsigned char* nsrc = H == 0 ? xb : xnb;
@@ -354,7 +280,7 @@ k_conv3x3_sp17(const unsigned char* __restrict__ x, const _Float16* __restrict__
                     // every read of this buffer has been issued.  This wave's pieces of the next tile (unit 0) are older than the
                     // VM_YOUNGER youngest vector-memory instructions it has issued (residual loads and stores of units 0-3, counted at
                     // compile time: each is issued unconditionally); those may stay in flight
-                    constexpr int VM_YOUNGER = sp17_vm_younger<RES, NCH, XLO0>(H);
+                    constexpr int VM_YOUNGER = sp17_vm_younger<RES, NCH, XLO0, H>();
                     static_assert(VM_YOUNGER < 63, "vmcnt field");
                     if (H == 0 && !have_prev) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // first tile: the stores riding in its unit 0 were skipped
                     else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(VM_YOUNGER) : "memory");
@@ -386,12 +312,11 @@ k_conv3x3_sp17(const unsigned char* __restrict__ x, const _Float16* __restrict__
                     constexpr int sl = t * NQ + q;  // MFMA slot of the unit
                     cp_for_each([&](auto KC) __attribute__((always_inline)) {
                         constexpr int o = SP::cum(sl - 1) + decltype(KC)::value;
-                        if constexpr (o < SP::cum(sl)) epi_op(pset, o / CT_OPS, pj0 + o / CT_OPS, pout, pout_lo, o % CT_OPS, pstore);
+                        if constexpr (o < SP::cum(sl)) epi_op(pset, o / CT_OPS, pj0 + o / CT_OPS, pout, o % CT_OPS, pstore);
                     }, typename CpMakeSeq<SP::MAXPER>::type{});
                     if constexpr (RES && sl < 2 * nj) {  // this unit's residual (used by its epilogue inside the next unit)
                         constexpr int rj = sl >> 1, rp = sl & 1;
-                        if constexpr (rp == 0) rr[set][rj][rp] = *(const cv_u32x2*)(rbase + (lmap[j0 + rj] >> 16));
-                        else rr[set][rj][rp] = *(const __attribute__((address_space(1))) cv_u32x2*)(rbase_lo + (lmap[j0 + rj] >> 16));
+                        rr[set][rj][rp] = sp_load8(rbase, rp, lmap[j0 + rj] >> 16);
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }, typename CpMakeSeq<NQ>::type{});
@@ -407,7 +332,7 @@ k_conv3x3_sp17(const unsigned char* __restrict__ x, const _Float16* __restrict__
         unit(CpInt<1>{}, CpInt<1>{});
         unit(CpInt<1>{}, CpInt<2>{});
         unit(CpInt<1>{}, CpInt<3>{});
-        yprev = ybase, yprev_lo = ybase_lo;
+        yprev = ybase;
     }
     // epilogue of the very last unit (lower half, unit 3: accumulator set 1)
     {
@@ -416,8 +341,8 @@ k_conv3x3_sp17(const unsigned char* __restrict__ x, const _Float16* __restrict__
 #pragma unroll
         for (int j = 0; j < nj; ++j)
 #pragma unroll
-            for (int o = 0; o < CT_OPS; ++o) epi_op(1, j, j0 + j, yprev, yprev_lo, o, true);
+            for (int o = 0; o < CT_OPS; ++o) epi_op(1, j, j0 + j, yprev, o, true);
     }
-    sp_range_report(mx, range);
+    sp_range_report(ep.mx, range);
 }
 #endif  // __HIPCC__

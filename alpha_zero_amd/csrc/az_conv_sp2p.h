@@ -15,7 +15,8 @@
 // the previous hand-over.
 // The riders.  A unit's MFMA stream is never interrupted: the hand-over, the finishing epilogue of the previous unit (join, residual,
 // stores), the residual loads, the B-fragment requests (one ds_read_b128 per MFMA gap), the LDS-DMA pieces of the next image and the
-// barriers ride in the gaps behind its MFMAs (send_op / fin_op / dma_piece below).
+// barriers ride in the gaps behind its MFMAs (send_op / fin_op / dma_piece below).  The finishing epilogue is the shared SpEpi of az_conv_sp.h
+// with the partner add as its one extra per-element micro-op; the LDS-DMA piece is the shared sp_dma_piece with the nt policy.
 // Arithmetic: result = (main_a + 2^-11 corr_a) + (main_b + 2^-11 corr_b) [+ residual]: two fp32 accumulation chains of 64 cin x 9 taps
 // instead of one of 128 x 9, joined once -- fp32 round-off class (tests/test_split_tower.py bounds), not bit-identical to k_conv3x3_sp;
 // k_conv3x3_spg<..., HALVES = 2> (az_conv_spg.h) repeats these chains bit for bit and runs the odd last board of a call.
@@ -248,7 +249,8 @@ static_assert(Sp2pU<0>::S.reads() == 60 && Sp2pU<1>::S.reads() == 60 && Sp2pU<2>
 // Constants of unit U's riders (shared by the kernel and by sp2p_vm_younger)
 template <bool RES, int U> struct Sp2pK {
     static constexpr int NS = Sp2pU<U>::S.ns, S0 = 6, NPIECE = 16;
-    static constexpr int E1 = RES ? 4 : 2, PAIR = 2 * E1 + 8, CT_OPS = 2 * PAIR + 2, P2CT = CT_OPS + 1;
+    // finishing micro-ops of a column tile: the partner's partial (1 read), then the epilogue with the partner add (sp_epi_* of az_conv_sp.h)
+    static constexpr int PAIR = sp_epi_pair(RES, true), CT_OPS = sp_epi_ct_ops(RES, true), P2CT = CT_OPS + 1;
     static constexpr int PU = (U + 3) & 3, NU = (U + 1) & 3;
     static constexpr int nj = sp2p_nj(U), j0 = sp2p_j0(U), pnj = sp2p_nj(PU), pj0 = sp2p_j0(PU);
     static constexpr bool END = sp2p_has_end(U), PRE = !sp2p_has_end(PU);
@@ -268,11 +270,7 @@ template <bool RES, int U> struct Sp2pK {
 // riders behind the last piece (2 per column tile are the last two micro-ops of a tile); the residual loads are older than the first piece.
 template <bool RES, int U> __host__ __device__ constexpr int sp2p_vm_younger() {
     typedef Sp2pK<RES, U> K;
-    int n = 0;
-    for (int c = 0; c < K::pnj; ++c)
-        for (int st = 0; st < 2; ++st)
-            if (K::SP::slot_of(c * K::P2CT + K::P2CT - 2 + st) > K::PLAST) ++n;
-    return n;
+    return sp_epi_stores_behind<typename K::SP>(K::pnj, K::P2CT, 1, K::PLAST);
 }
 
 template <bool RES> __global__ void __launch_bounds__(CW_THREADS, 1)
@@ -289,7 +287,7 @@ k_conv3x3_sp2p(const unsigned char* __restrict__ x, const _Float16* __restrict__
     constexpr int NP = (G::CELLS + 63) / 64, SPW = 2 * NCH / 4, NPIECE = NP * SPW;
     constexpr int NF = NT * 2 * KS;
     constexpr int NF_A = 64;
-    constexpr int P2CT = Sp2pK<RES, 0>::P2CT, PAIR = Sp2pK<RES, 0>::PAIR, E1 = Sp2pK<RES, 0>::E1, S0 = Sp2pK<RES, 0>::S0;
+    constexpr int P2CT = Sp2pK<RES, 0>::P2CT, PAIR = Sp2pK<RES, 0>::PAIR, S0 = Sp2pK<RES, 0>::S0;
     static_assert(NPIECE == Sp2pK<RES, 0>::NPIECE && KS % R == 0, "pieces per image; ring phase");
     constexpr int SIDE_BOARD = 8 * NCH * 16 + 16, SIDE0 = 2 * LBUF + 16, XB0 = SIDE0 + SP2P_NB * SIDE_BOARD, XBCT = 4 * 1024;
     __shared__ __attribute__((aligned(1024))) unsigned char lds[XB0 + NJ0 * XBCT];
@@ -299,18 +297,7 @@ k_conv3x3_sp2p(const unsigned char* __restrict__ x, const _Float16* __restrict__
     const int wa = wave >> 1, wb = wave & 1;
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds;
     int cg, slot, nslot;
-    {
-        const int b = (int)blockIdx.x, nb = (int)gridDim.x;
-        nslot = nb / NCG;
-        if (nb % (8 * NCG) == 0) {
-            const int xcd = b & 7, k = b >> 3;
-            cg = k % NCG;
-            slot = xcd + 8 * (k / NCG);
-        } else {
-            cg = b % NCG;
-            slot = b / NCG;
-        }
-    }
+    sp_wg_map(NCG, cg, slot, nslot);
     for (int i = tid; i < (XB0 + NJ0 * XBCT) / 16; i += CW_THREADS) *(cv_u32x4*)(lds + i * 16) = (cv_u32x4){0u, 0u, 0u, 0u};
     CV_BARRIER();
     if (slot >= npairs) return;
@@ -330,23 +317,11 @@ k_conv3x3_sp2p(const unsigned char* __restrict__ x, const _Float16* __restrict__
 
     unsigned dsrc[NP];
     unsigned long long dmask[NP];
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-        const int p = 64 * i + lane < G::CELLS ? G::pos_of_cell(64 * i + lane) : -1;
-        dsrc[i] = (unsigned)((p < 0 ? 0 : p) * 16);
-        dmask[i] = __builtin_amdgcn_ballot_w64(p >= 0);
-    }
+    sp_dma_plan(dsrc, dmask, lane, [](int cell) { return cell < G::CELLS ? G::pos_of_cell(cell) * 16 : -1; });
     auto dma_piece = [&](const unsigned char* src, unsigned dstbuf, bool live, int i) {
-        const int c = SPW * wave + i / NP, pc = i % NP;
-        const unsigned long long base = (unsigned long long)(src + (size_t)c * GBLK);
-        const unsigned long long mask = live ? dmask[pc] : 0ull;
-        const unsigned dst = dstbuf + (unsigned)(c * LBLK + pc * 1024);
         // nt: the image is read by this workgroup and by the one of the other cout group on the same XCD at about the same time, then never again;
         // as streaming lines it stops pushing the half-written output lines out of the L2 (fewer bytes written, the same bytes fetched: DESIGN 3.1)
-        asm volatile("s_mov_b64 exec, %0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3 nt\n\ts_mov_b64 exec, -1"
-                     :
-                     : "s"(mask), "s"(dst), "v"(dsrc[pc]), "s"(base)
-                     : "memory");
+        sp_dma_piece<true>(src, dstbuf, SPW * wave + i / NP, i % NP, GBLK, LBLK, live ? dmask[i % NP] : 0ull, dsrc[i % NP]);
     };
     // per lane and column tile: LDS offset of the (-1, -1) neighbour in the image of the position's board (image B = + LBUF), this lane's group
     // of the wave's cin half; offset of the lane's 8-byte output slot from the pair's base (board B = + YTILE)
@@ -383,25 +358,12 @@ k_conv3x3_sp2p(const unsigned char* __restrict__ x, const _Float16* __restrict__
         frag_req(CpInt<0>{}, CpInt<0>{}, CpInt<0>{});
         frag_req(CpInt<0>{}, CpInt<0>{}, CpInt<1>{});
     }
-#pragma unroll
-    for (int f = 0; f < NF; ++f) {
-        if (f < NF_A) asm volatile("" : : "a"(wf[f]));
-        else asm volatile("" : : "v"(wf[f]));
-    }
+    sp_pin_a<NF_A>(wf);
     asm volatile("" : : "v"(bv), "v"(lmap[0]), "v"(lmap[SP2P_NCT - 1]), "v"(dsrc[0]), "v"(dsrc[NP - 1]));
 
-    c6_f32x4 accm[2][NJ0][NT], accc[2][NJ0][NT];  // [accumulator set][column tile of the unit][cout tile]
-    cv_u32x2 rr[2][NJ0][2];                       // residual of the own tile: [set][column tile][plane]
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int j = 0; j < NJ0; ++j) {
-#pragma unroll
-            for (int t = 0; t < NT; ++t) accm[a][j][t] = (c6_f32x4){0.0f, 0.0f, 0.0f, 0.0f}, accc[a][j][t] = (c6_f32x4){0.0f, 0.0f, 0.0f, 0.0f};
-            rr[a][j][0] = (cv_u32x2){0u, 0u}, rr[a][j][1] = (cv_u32x2){0u, 0u};
-        }
-    float evv[2] = {0.0f, 0.0f}, sc[2] = {0.0f, 0.0f}, t0 = 0.0f, mx = 0.0f;
-    unsigned hpk[2] = {0u, 0u}, lpk[2] = {0u, 0u};
+    c6_f32x4 accm[2][NJ0][NT] = {}, accc[2][NJ0][NT] = {};  // [accumulator set][column tile of the unit][cout tile]
+    cv_u32x2 rr[2][NJ0][2] = {};                            // residual of the own tile: [set][column tile][plane]
+    SpEpi ep;
     c6_f32x4 xs = (c6_f32x4){0.0f, 0.0f, 0.0f, 0.0f}, xr = (c6_f32x4){0.0f, 0.0f, 0.0f, 0.0f};
     unsigned char* const xb_mine = lds + XB0 + wave * 1024 + lane * 16;
     const unsigned char* const xb_partner = lds + XB0 + (wave ^ 1) * 1024 + lane * 16;
@@ -411,38 +373,10 @@ k_conv3x3_sp2p(const unsigned char* __restrict__ x, const _Float16* __restrict__
         else *(c6_f32x4*)(xb_mine + c * XBCT) = xs;
     };
     // micro-op o of the finishing of column tile c (table index mj): the partner's partial (1 read), then the epilogue of the own tile
-    auto fin_op = [&](int set, int c, int mj, unsigned char* out, sp_gptr out_lo, int o, bool store_ok) {
-        if (o == 0) {
-            xr = *(const c6_f32x4*)(xb_partner + c * XBCT);
-            return;
-        }
-        o -= 1;
-        if (o < 2 * PAIR) {
-            const int pr = o / PAIR, k = o % PAIR;
-            if (k < 2 * E1) {
-                const int ei = k / E1, kk = k % E1, e = 2 * pr + ei;
-                const unsigned rh = pr == 0 ? rr[set][c][0].x : rr[set][c][0].y, rl = pr == 0 ? rr[set][c][1].x : rr[set][c][1].y;
-                if (kk == 0) evv[ei] = fmaf(accc[set][c][0][e], SP_INV_SCALE, accm[set][c][0][e]);
-                else if (kk == 1) evv[ei] = cw_add_f32(evv[ei], xr[e]);
-                else if (RES && kk == 2) t0 = ei == 0 ? sp_mix_join<0>(rh, rl) : sp_mix_join<1>(rh, rl);
-                else if (RES && kk == 3) evv[ei] = cw_add_f32(evv[ei], t0);
-            } else {
-                const int kk = k - 2 * E1;
-                if (kk == 0) mx = sp_max3_abs(mx, evv[0], evv[1]);
-                else if (kk == 1) evv[0] = __builtin_amdgcn_fmed3f(evv[0], lo_clamp, SP_F16_MAX);
-                else if (kk == 2) evv[1] = __builtin_amdgcn_fmed3f(evv[1], lo_clamp, SP_F16_MAX);
-                else if (kk == 3) hpk[pr] = sp_cvt_pk(evv[0], evv[1]);
-                else if (kk == 4) sc[0] = sp_mix_diff<0>(hpk[pr], evv[0]);
-                else if (kk == 5) sc[1] = sp_mix_diff<1>(hpk[pr], evv[1]);
-                else if (kk == 6) lpk[pr] = sp_scale_cvt_lo(sc[0]);
-                else lpk[pr] = sp_scale_cvt_hi(lpk[pr], sc[1]);
-            }
-        } else {
-            const unsigned gq = out_off(mj);
-            if (o == 2 * PAIR) {
-                if (store_ok) *(cv_u32x2*)(out + gq) = (cv_u32x2){hpk[0], hpk[1]};
-            } else if (store_ok) *(__attribute__((address_space(1))) cv_u32x2*)(out_lo + gq) = (cv_u32x2){lpk[0], lpk[1]};
-        }
+    auto fin_op = [&](int set, int c, int mj, const SpOut& out, int o, bool store_ok) {
+        if (o == 0) xr = *(const c6_f32x4*)(xb_partner + c * XBCT);
+        else if (o - 1 < 2 * PAIR) ep.op<RES, true>(o - 1, accm[set][c][0], accc[set][c][0], rr[set][c], lo_clamp, &xr);
+        else ep.store(o - 1 - 2 * PAIR, out, out_off(mj), store_ok);
     };
 
     const bool copier = tid < 8 * NCH;
@@ -456,27 +390,20 @@ k_conv3x3_sp2p(const unsigned char* __restrict__ x, const _Float16* __restrict__
     cv_u32x4 ctmp = (cv_u32x4){0u, 0u, 0u, 0u};
 
     int it = 0, cb = 0;  // cb: boards in the corner side buffer
-    unsigned char* yprev = y;
-    sp_gptr yprev_lo = (sp_gptr)(unsigned long long)y;
+    SpOut yprev = {y, (sp_gptr)(unsigned long long)y};
     for (int pair = slot; pair < npairs; pair += nslot, ++it) {
         const bool has_next = pair + nslot < npairs;
         const unsigned char* bsrc = x + (size_t)pair * (2 * XTILE) + XTILE;                                  // this pair's image B
         const unsigned char* nsrc = x + (size_t)(has_next ? pair + nslot : pair) * (2 * XTILE);              // the next pair's image A
         const size_t yo = (size_t)pair * (2 * YTILE) + (size_t)(cg * 8 + wa * 4 + wb * 2) * GBLK;  // the own tile's two chunk strips, board A
-        const unsigned char* rbase = RES ? res + yo : nullptr;
-        unsigned char* ybase = y + yo;
-        unsigned long long rlo = (unsigned long long)(RES ? res + yo : y + yo) + YPLANE, ylo = (unsigned long long)(y + yo) + YPLANE;
-        asm volatile("" : "+s"(rlo), "+s"(ylo));
-        const sp_gcptr rbase_lo = (sp_gcptr)rlo;
-        const sp_gptr ybase_lo = (sp_gptr)ylo;
+        const SpOut rbase = sp_out_base(RES ? res + yo : y + yo, YPLANE), ybase = sp_out_base(y + yo, YPLANE);
         const bool have_prev = it > 0;
         auto unit = [&](auto UC) __attribute__((always_inline)) {
             constexpr int u = decltype(UC)::value, set = u & 1, pset = set ^ 1;
             typedef Sp2pK<RES, u> K;
             typedef typename K::SP SP;
             constexpr int nj = K::nj, j0 = K::j0, pj0 = K::pj0;
-            unsigned char* pout = u == 0 ? yprev : ybase;
-            const sp_gptr pout_lo = u == 0 ? yprev_lo : ybase_lo;
+            const SpOut pout = u == 0 ? yprev : ybase;
             const bool pstore = u > 0 || have_prev;
             cp_for_each([&](auto SC) __attribute__((always_inline)) {
                 constexpr int sl = decltype(SC)::value;  // MFMA slot of the unit
@@ -521,12 +448,11 @@ k_conv3x3_sp2p(const unsigned char* __restrict__ x, const _Float16* __restrict__
                 if constexpr (sl >= S0 && sl < S0 + K::P1) send_op(pset, (sl - S0) / 5, (sl - S0) % 5);
                 if constexpr (sl > K::SBX) {
                     constexpr int o = SP::cum(sl - 1);
-                    if constexpr (o < SP::cum(sl)) fin_op(pset, o / P2CT, pj0 + o / P2CT, pout, pout_lo, o % P2CT, pstore);
+                    if constexpr (o < SP::cum(sl)) fin_op(pset, o / P2CT, pj0 + o / P2CT, pout, o % P2CT, pstore);
                 }
                 if constexpr (RES && sl < 2 * nj) {  // this unit's residual of the own tile (used by its finishing inside the next unit)
                     constexpr int rj = sl >> 1, rp = sl & 1;
-                    if constexpr (rp == 0) rr[set][rj][rp] = *(const cv_u32x2*)(rbase + out_off(j0 + rj));
-                    else rr[set][rj][rp] = *(const __attribute__((address_space(1))) cv_u32x2*)(rbase_lo + out_off(j0 + rj));
+                    rr[set][rj][rp] = sp_load8(rbase, rp, out_off(j0 + rj));
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (K::DMA && sl >= K::PFIRST && sl <= K::PLAST && (sl - K::PFIRST) % K::PSTRIDE == 0) {
@@ -549,7 +475,7 @@ k_conv3x3_sp2p(const unsigned char* __restrict__ x, const _Float16* __restrict__
         unit(CpInt<1>{});
         unit(CpInt<2>{});
         unit(CpInt<3>{});
-        yprev = ybase, yprev_lo = ybase_lo;
+        yprev = ybase;
         cb += 2;
         if (cb == SP2P_NB || !has_next) {
             // ---- the corner (8, 0) of the last cb boards: [2 x 16 couts] x [<= 12 boards] x [4 taps x this wave's 64 cin] per wave, then the hand-over
@@ -604,7 +530,7 @@ k_conv3x3_sp2p(const unsigned char* __restrict__ x, const _Float16* __restrict__
             _Float16 h[4], l[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                if (l15 < n_ok) mx = fmaxf(mx, fabsf(v[e]));
+                if (l15 < n_ok) ep.mx = fmaxf(ep.mx, fabsf(v[e]));
                 v[e] = fmaxf(v[e], lo_relu);
                 sp_split(v[e], h[e], l[e]);
             }
@@ -627,7 +553,7 @@ k_conv3x3_sp2p(const unsigned char* __restrict__ x, const _Float16* __restrict__
 #pragma unroll
     for (int c = 0; c < NJ1; ++c)
 #pragma unroll
-        for (int o = 0; o < P2CT; ++o) fin_op(1, c, sp2p_j0(3) + c, yprev, yprev_lo, o, true);
-    sp_range_report(mx, range);
+        for (int o = 0; o < P2CT; ++o) fin_op(1, c, sp2p_j0(3) + c, yprev, o, true);
+    sp_range_report(ep.mx, range);
 }
 #endif  // __HIPCC__

@@ -30,6 +30,8 @@
 //     one-instruction micro-ops (SpSpread); only the last unit of phase A finishes exposed (its m values must be in LDS before the barrier).
 //     Per-(column tile, lane) offsets (B-fragment base, output slot) live in an LDS table and are fetched one unit ahead into a rotating
 //     set of 3 x 2 register pairs: the kernel carries 6 such registers instead of 40 (the 288 weight registers leave ~220 for everything else).
+// The epilogue arithmetic and the global stores (SpEpi; the lower clamp passed in is 0: both layers have a ReLU), the LDS-DMA piece and its lane
+// plan, the fragment offset and the output base are the shared ones of az_conv_sp.h; only phase A's store into the m image is written here.
 // Results are BIT-IDENTICAL to two azsp_conv3x3_split launches (same MFMA order per output, same roundings): tests/test_split_tower.py.
 // y must not alias x (the lower half re-reads x rows 7-8 after the upper half has written y rows 0-8).
 #pragma once
@@ -226,26 +228,6 @@ static_assert(SbSkip<Sb17>::dma_unit(0, 3) == 0 && SbSkip<Sb17>::dma_t0(0, 3) ==
               SbSkip<Sb17>::dma_unit(0, 1) == 3 && SbSkip<Sb17>::dma_t0(0, 1) == 8 && SbSkip<Sb17>::dma_unit(0, 2) == 3 && SbSkip<Sb17>::dma_t0(0, 2) == 13 &&
               SbSkip<Sb17>::dma_unit(1, 0) == 0 && SbSkip<Sb17>::dma_unit(1, 1) == 1 && SbSkip<Sb17>::dma_unit(1, 2) == 3 && SbSkip<Sb17>::dma_t0(1, 2) == 8 &&
               SbSkip<Sb17>::dma_unit(1, 3) == 3 && SbSkip<Sb17>::dma_t0(1, 3) == 13, "Sb17: the derived DMA schedule");
-typedef __attribute__((address_space(1))) unsigned char* sb17_gptr;         // pointers into global memory whose value the compiler must take
-typedef const __attribute__((address_space(1))) unsigned char* sb17_gcptr;  // as given (an opaque scalar base per plane, see the board loop)
-
-// f32 v minus the f16 half H of hpk: the remainder v - hi of the split, exact in fp32, one v_fma_mix_f32
-template <int H> __device__ __forceinline__ float sb17_mix_diff(unsigned hpk, float v) {
-    float r;
-    if constexpr (H == 0) asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(hpk), "v"(v));
-    else asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(hpk), "v"(v));
-    return r;
-}
-// f16(d * 2^11) (the product is exact in fp32: one rounding, to nearest even) into the low / high half of a packed pair
-__device__ __forceinline__ unsigned sb17_scale_cvt_lo(float d) {
-    unsigned r;
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0 op_sel:[0,0,0] op_sel_hi:[0,0,0]" : "=v"(r) : "v"(d), "s"(SP_SCALE));
-    return r;
-}
-__device__ __forceinline__ unsigned sb17_scale_cvt_hi(unsigned lo, float d) {
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0 op_sel:[0,0,0] op_sel_hi:[0,0,0]" : "+v"(lo) : "v"(d), "s"(SP_SCALE));
-    return lo;
-}
 
 // w1, w2: [plane: hi, lo][9 taps][64 couts][64 cin] f16 with lo = (w - hi) * 2^11 (the packing of azsp_conv3x3_split); b1, b2 fp32 [64].
 // R = slots of the B-fragment ring (k-steps): a fragment is requested R - 1 k-steps before its MFMAs.
@@ -269,8 +251,8 @@ k_resblock_sp(const unsigned char* __restrict__ x, const _Float16* __restrict__ 
     // (range record of both in one v_max3_f32, 2 x ReLU + clamp in one v_med3_f32, packed hi convert, 2 exact remainders v - hi, 2
     // scale-and-convert v_fma_mixlo/hi_f16), 2 LDS stores: 22.  TO GLOBAL MEMORY (phase B): per element 3 (join, skip join, add), per pair 8, 2
     // stores: 30.  (k_conv3x3_sp17 of round 4 spent 30 / 38 on the same arithmetic; the results are bit-identical.)
-    constexpr int E1M = sp_epi_e1(false), PAIRM = sp_epi_pair(false), CTM = sp_epi_ct_ops(false);
-    constexpr int E1G = sp_epi_e1(true), PAIRG = sp_epi_pair(true), CTG = sp_epi_ct_ops(true);
+    constexpr int PAIRM = sp_epi_pair(false), CTM = sp_epi_ct_ops(false);
+    constexpr int PAIRG = sp_epi_pair(true), CTG = sp_epi_ct_ops(true);
     constexpr int S0 = 6;                                    // first MFMA slot of a unit that may touch the previous unit's accumulators
     static_assert(KS % R == 0, "every unit starts at ring phase 0");
     static_assert(SPW == 4 && NP == 4 && KS >= 15, "four strips per wave, four pieces per strip: a piece = 4 DMA instructions = 2 k-steps");
@@ -323,21 +305,13 @@ k_resblock_sp(const unsigned char* __restrict__ x, const _Float16* __restrict__ 
     unsigned long long dmask[G::NH][NP];
 #pragma unroll
     for (int h = 0; h < G::NH; ++h)
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            const int p = G::x_pos_of_cell(h, 64 * i + lane);
-            dsrc[h][i] = (unsigned)(p < 0 ? 0 : G::gpos_off(p));
-            dmask[h][i] = __builtin_amdgcn_ballot_w64(p >= 0);
-        }
+        sp_dma_plan(dsrc[h], dmask[h], lane, [h](int cell) {
+            const int p = G::x_pos_of_cell(h, cell);
+            return p < 0 ? -1 : G::gpos_off(p);
+        });
     auto dma_piece = [&](const unsigned char* src, bool live, int h, int i) __attribute__((always_inline)) {
-        const int sx = i / NP, c = (sx >> 1) * NCH + 2 * wave + (sx & 1), pc = i % NP;
-        const unsigned long long base = (unsigned long long)(src + (size_t)c * GBLK);
-        const unsigned long long mask = live ? dmask[h][pc] : 0ull;
-        const unsigned dst = lds0 + (unsigned)(c * XBLK + pc * 1024);
-        asm volatile("s_mov_b64 exec, %0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b64 exec, -1"
-                     :
-                     : "s"(mask), "s"(dst), "v"(dsrc[h][pc]), "s"(base)
-                     : "memory");
+        const int sx = i / NP;
+        sp_dma_piece(src, lds0, (sx >> 1) * NCH + 2 * wave + (sx & 1), i % NP, GBLK, XBLK, live ? dmask[h][i % NP] : 0ull, dsrc[h][i % NP]);
     };
     const unsigned char* Xs = lds;
     const unsigned char* Ms = lds;                           // (phase B's lane-table offsets carry the m image's offset XBUF)
@@ -357,27 +331,19 @@ k_resblock_sp(const unsigned char* __restrict__ x, const _Float16* __restrict__ 
             if (j < nj) lm[rot][j] = *(const cv_u32x2*)(tbl + (tile0 + j) * 512);
     };
     sp_f16x8 bb[R][2][NJM];  // ring of B fragments [k-step slot][plane][column tile of the unit]
-    // fragments of k-step s of a unit whose lane-table registers are lm[rot] from image `img` (PH = 0: x image, 1: m image)
-    auto load_step = [&](auto PHC, const unsigned char* img, int rot, int nj, int s, int rs) __attribute__((always_inline)) {
-        constexpr int PH = decltype(PHC)::value, BLK = PH ? MBLK : XBLK, PLANE = PH ? MPLANE : XPLANE;
-        const int tap = s / KSUB;
-        const int off = ((tap / 3) * G::PITCH + (tap % 3)) * 16 + (s % KSUB) * (4 * BLK);
-#pragma unroll
-        for (int j = 0; j < NJM; ++j)
-            if (j < nj) bb[rs][0][j] = *(const sp_f16x8*)(img + lm[rot][j].x + off);
-#pragma unroll
-        for (int j = 0; j < NJM; ++j)
-            if (j < nj) bb[rs][1][j] = *(const sp_f16x8*)(img + lm[rot][j].x + off + PLANE);
-    };
-
-    // fragment f of a k-step's 2 nj (plane f / nj, column tile f % nj): inside the units the requests are spread over the first MFMA gaps of
-    // the k-step R - 1 before their use (one ds_read_b128 per gap instead of a burst of 2 nj in front of a k-step; az_conv_sp2.h)
+    // fragment f of the 2 nj of k-step s (plane f / nj, column tile f % nj) of a unit whose lane-table registers are lm[rot], from image `img`
+    // (PH = 0: x image, 1: m image): inside the units the requests are spread over the first MFMA gaps of the k-step R - 1 before their use
+    // (one ds_read_b128 per gap instead of a burst of 2 nj in front of a k-step; see k_conv3x3_sp)
     auto load_frag = [&](auto PHC, const unsigned char* img, int rot, int nj, int s, int rs, int f) __attribute__((always_inline)) {
         constexpr int PH = decltype(PHC)::value, BLK = PH ? MBLK : XBLK, PLANE = PH ? MPLANE : XPLANE;
-        const int tap = s / KSUB;
-        const int off = ((tap / 3) * G::PITCH + (tap % 3)) * 16 + (s % KSUB) * (4 * BLK);
+        const int off = sp_frag_off(s, KSUB, G::PITCH, BLK);
         const int pl = f / nj, j = f % nj;
         bb[rs][pl][j] = *(const sp_f16x8*)(img + lm[rot][j].x + off + pl * PLANE);
+    };
+    auto load_step = [&](auto PHC, const unsigned char* img, int rot, int nj, int s, int rs) __attribute__((always_inline)) {  // all of a k-step's at once
+#pragma unroll
+        for (int f = 0; f < 2 * NJM; ++f)
+            if (f < 2 * nj) load_frag(PHC, img, rot, nj, s, rs, f);
     };
 
     {   // first tile (upper half of the first board): all pieces at once, then the first lane-table registers and fragments
@@ -390,75 +356,32 @@ k_resblock_sp(const unsigned char* __restrict__ x, const _Float16* __restrict__ 
 #pragma unroll
         for (int s = 0; s < R - 1; ++s) load_step(CpInt<0>{}, Xs, 0, G::unit_nj(0, 0), s, s);
     }
-#pragma unroll
-    for (int f = 0; f < NF; ++f) {  // the compiler's wait for the weight loads belongs in front of the loop (see az_conv.h)
-        if (f < 64) asm volatile("" : : "a"(wf[f]));
-        else asm volatile("" : : "v"(wf[f]));
-    }
+    sp_pin_a<64>(wf);
     asm volatile("" : : "v"(bv[0]), "v"(bv[1]), "v"(dsrc[0][0]), "v"(dsrc[G::NH - 1][NP - 1]));
 
-    c6_f32x4 accm[2][NJM], accc[2][NJM];  // [accumulator set][column tile of the unit]
-    cv_u32x2 rr[2][NJM][2];               // skip values of a phase-B unit: [accumulator set][column tile][plane]
-    cv_u32x2 rrx[NJM][2];                 // skip values of the LAST unit of a phase B, fetched one unit early (see SbSkip)
-#pragma unroll
-    for (int j = 0; j < NJM; ++j) rrx[j][0] = (cv_u32x2){0u, 0u}, rrx[j][1] = (cv_u32x2){0u, 0u};
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int j = 0; j < NJM; ++j) {
-            accm[a][j] = (c6_f32x4){0.0f, 0.0f, 0.0f, 0.0f}, accc[a][j] = (c6_f32x4){0.0f, 0.0f, 0.0f, 0.0f};
-            rr[a][j][0] = (cv_u32x2){0u, 0u}, rr[a][j][1] = (cv_u32x2){0u, 0u};
-        }
-    float evv[2] = {0.0f, 0.0f}, sc[2] = {0.0f, 0.0f}, t0 = 0.0f, mx = 0.0f;  // mx: largest |value| this lane produced (range record)
-    unsigned hpk[2] = {0u, 0u}, lpk[2] = {0u, 0u};
+    c6_f32x4 accm[2][NJM] = {}, accc[2][NJM] = {};  // [accumulator set][column tile of the unit]
+    cv_u32x2 rr[2][NJM][2] = {};                    // skip values of a phase-B unit: [accumulator set][column tile][plane]
+    cv_u32x2 rrx[NJM][2] = {};                      // skip values of the LAST unit of a phase B, fetched one unit early (see SbSkip)
+    SpEpi ep;
     // micro-op `o` of the epilogue of column tile j of the unit with accumulator set `set`: ONE VALU / memory instruction.
     // GLOBAL = false: phase A (bias + ReLU -> m image at Mw + ooff); true: phase B (bias + skip + ReLU -> global memory at out + ooff)
-    auto epi_op = [&](auto GC, int set, int j, unsigned ooff, unsigned char* out, sb17_gptr out_lo, int o, bool store_ok) __attribute__((always_inline)) {
+    auto epi_op = [&](auto GC, int set, int j, unsigned ooff, const SpOut& out, int o, bool store_ok) __attribute__((always_inline)) {
         constexpr bool GLOBAL = decltype(GC)::value != 0;
-        constexpr int E1 = GLOBAL ? E1G : E1M, PAIR = GLOBAL ? PAIRG : PAIRM;
-        if (o < 2 * PAIR) {
-            const int pr = o / PAIR, k = o % PAIR;  // pair pr = elements 2 pr, 2 pr + 1 (one packed dword of each plane)
-            if (k < 2 * E1) {
-                const int ei = k / E1, kk = k % E1, e = 2 * pr + ei;
-                const unsigned rh = pr == 0 ? rr[set][j][0].x : rr[set][j][0].y, rl = pr == 0 ? rr[set][j][1].x : rr[set][j][1].y;
-                if (kk == 0) evv[ei] = fmaf(accc[set][j][e], SP_INV_SCALE, accm[set][j][e]);
-                else if (GLOBAL && kk == 1) t0 = ei == 0 ? sp_mix_join<0>(rh, rl) : sp_mix_join<1>(rh, rl);
-                else if (GLOBAL && kk == 2) evv[ei] = cw_add_f32(evv[ei], t0);
-            } else {
-                const int kk = k - 2 * E1;
-                if (kk == 0) mx = sp_max3_abs(mx, evv[0], evv[1]);                                            // what the reference would carry on ...
-                else if (kk == 1) evv[0] = __builtin_amdgcn_fmed3f(evv[0], 0.0f, SP_F16_MAX);                  // ... is clamped here (ReLU in the same median)
-                else if (kk == 2) evv[1] = __builtin_amdgcn_fmed3f(evv[1], 0.0f, SP_F16_MAX);
-                else if (kk == 3) hpk[pr] = sp_cvt_pk(evv[0], evv[1]);
-                else if (kk == 4) sc[0] = sb17_mix_diff<0>(hpk[pr], evv[0]);
-                else if (kk == 5) sc[1] = sb17_mix_diff<1>(hpk[pr], evv[1]);
-                else if (kk == 6) lpk[pr] = sb17_scale_cvt_lo(sc[0]);
-                else lpk[pr] = sb17_scale_cvt_hi(lpk[pr], sc[1]);
-            }
-        } else if constexpr (GLOBAL) {
-            if (o == 2 * PAIR) {
-                if (store_ok) *(cv_u32x2*)(out + ooff) = (cv_u32x2){hpk[0], hpk[1]};
-            } else if (store_ok) *(__attribute__((address_space(1))) cv_u32x2*)(out_lo + ooff) = (cv_u32x2){lpk[0], lpk[1]};
-        } else {
-            if (o == 2 * PAIR) *(cv_u32x2*)(Mw + ooff) = (cv_u32x2){hpk[0], hpk[1]};
-            else *(cv_u32x2*)(Mw + MPLANE + ooff) = (cv_u32x2){lpk[0], lpk[1]};
-        }
+        constexpr int PAIR = GLOBAL ? PAIRG : PAIRM;
+        if (o < 2 * PAIR) ep.op<GLOBAL>(o, accm[set][j], accc[set][j], rr[set][j], 0.0f);  // (a block's layers all have a ReLU: the lower clamp is 0)
+        else if constexpr (GLOBAL) ep.store(o - 2 * PAIR, out, ooff, store_ok);
+        else if (o == 2 * PAIR) *(cv_u32x2*)(Mw + ooff) = (cv_u32x2){ep.hpk[0], ep.hpk[1]};
+        else *(cv_u32x2*)(Mw + MPLANE + ooff) = (cv_u32x2){ep.lpk[0], ep.lpk[1]};
     };
 
     int it = 0;
-    unsigned char* yprev = y;
-    sb17_gptr yprev_lo = (sb17_gptr)(unsigned long long)y;
+    SpOut yprev = {y, (sp_gptr)(unsigned long long)y};
     for (int board = slot; board < nblocks; board += nslot, ++it) {
         const bool has_next = board + nslot < nblocks;
         const unsigned char* xb = x + (size_t)board * GBLOCK;
         const unsigned char* xnb = x + (size_t)(has_next ? board + nslot : board) * GBLOCK;
         const size_t yo = (size_t)board * GBLOCK + (size_t)(wave * 2) * GBLK;  // uniform: the lane part comes from the lane table
-        // one uniform base per plane, opaque to the compiler (it would otherwise fold base + GPLANE + lane offset into 64-bit VALU adds
-        // per access: GPLANE exceeds the 13-bit immediate): every y store is scalar base + lane offset
-        unsigned long long ylo = (unsigned long long)(y + yo) + GPLANE;
-        asm volatile("" : "+s"(ylo));  // (an opaque scalar, cast back to a GLOBAL-address-space pointer: no flat accesses)
-        unsigned char* ybase = y + yo;
-        const sb17_gptr ybase_lo = (sb17_gptr)ylo;
+        const SpOut ybase = sp_out_base(y + yo, GPLANE);
         const bool have_prev = it > 0;
         // unit U of segment SG
         auto unit = [&](auto GC, auto UC) __attribute__((always_inline)) {
@@ -486,8 +409,7 @@ k_resblock_sp(const unsigned char* __restrict__ x, const _Float16* __restrict__ 
             static_assert(SP::MAXPER <= 2, "the previous unit's epilogue fits this unit's MFMA gaps");
             const unsigned char* img = PH ? Ms : Xs;
             // where the riding epilogue stores: phase B units of the previous board (first unit of a board) or of this board
-            unsigned char* pout = SG == 0 ? yprev : ybase;
-            const sb17_gptr pout_lo = SG == 0 ? yprev_lo : ybase_lo;
+            const SpOut pout = SG == 0 ? yprev : ybase;
             const bool pstore = SG == 0 && FIRST ? have_prev : true;
             cp_for_each([&](auto TC) __attribute__((always_inline)) {
                 constexpr int t = decltype(TC)::value;
@@ -526,7 +448,7 @@ k_resblock_sp(const unsigned char* __restrict__ x, const _Float16* __restrict__ 
                     if constexpr (RIDE) {
                         cp_for_each([&](auto KC) __attribute__((always_inline)) {
                             constexpr int o = SP::cum(sl - 1) + decltype(KC)::value;
-                            if constexpr (o < SP::cum(sl)) epi_op(CpInt<RGLOBAL ? 1 : 0>{}, pset, o / CT_OPS, lm[PROT][o / CT_OPS].y, pout, pout_lo, o % CT_OPS, pstore);
+                            if constexpr (o < SP::cum(sl)) epi_op(CpInt<RGLOBAL ? 1 : 0>{}, pset, o / CT_OPS, lm[PROT][o / CT_OPS].y, pout, o % CT_OPS, pstore);
                         }, typename CpMakeSeq<SP::MAXPER>::type{});
                     }
                     if constexpr (PH == 1 && sl < 2 * nj) {  // this unit's skip values (used by its epilogue inside the next unit): from the x image
@@ -562,7 +484,7 @@ k_resblock_sp(const unsigned char* __restrict__ x, const _Float16* __restrict__ 
 #pragma unroll
                 for (int j = 0; j < nj; ++j)
 #pragma unroll
-                    for (int o = 0; o < CTM; ++o) epi_op(CpInt<0>{}, set, j, lm[ROT][j].y, nullptr, (sb17_gptr)0, o, true);
+                    for (int o = 0; o < CTM; ++o) epi_op(CpInt<0>{}, set, j, lm[ROT][j].y, yprev, o, true);  // (phase A stores to the m image: no output base)
                 CV_BARRIER();
 #pragma unroll
                 for (int s = 0; s < R - 1; ++s) load_step(CpInt<1>{}, Ms, NROT, nnj, s, s);
@@ -574,7 +496,7 @@ k_resblock_sp(const unsigned char* __restrict__ x, const _Float16* __restrict__ 
             cp_for_each([&](auto UC) __attribute__((always_inline)) { unit(CpInt<SG>{}, UC); }, typename CpMakeSeq<G::seg_nu(SG)>::type{});
         };
         cp_for_each([&](auto GC) __attribute__((always_inline)) { segment(GC); }, typename CpMakeSeq<G::NSEG>::type{});
-        yprev = ybase, yprev_lo = ybase_lo;
+        yprev = ybase;
     }
     // epilogue of the very last unit (the last phase B's last unit: accumulator set 1, lane-table registers of the last sequence number)
     {
@@ -584,8 +506,8 @@ k_resblock_sp(const unsigned char* __restrict__ x, const _Float16* __restrict__ 
 #pragma unroll
         for (int j = 0; j < nj; ++j)
 #pragma unroll
-            for (int o = 0; o < CTG; ++o) epi_op(CpInt<1>{}, 1, j, lm[ROT][j].y, yprev, yprev_lo, o, true);
+            for (int o = 0; o < CTG; ++o) epi_op(CpInt<1>{}, 1, j, lm[ROT][j].y, yprev, o, true);
     }
-    sp_range_report(mx, range);
+    sp_range_report(ep.mx, range);
 }
 #endif  // __HIPCC__

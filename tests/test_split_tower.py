@@ -520,11 +520,15 @@ def test_gpu_wave_per_tile_conv_is_bit_identical_to_the_weight_stationary_kernel
     same shape -- k_conv3x3_sp2p (two accumulation chains; board pairs, so an odd last board is itself a wave-per-tile launch on offset
     pointers, compared here with the whole call's), k_conv3x3_sp<.., 8, 1>, k_conv3x3_sp17 -- on the same inputs: the raw hi / lo
     f16 words of the output are equal, with and without residual and ReLU.  The evaluator's result for a position therefore does not
-    depend on whether it arrives in a batch of 1 (drop-in uct_search) or of 32 768 (the self-play actor)."""
+    depend on whether it arrives in a batch of 1 (drop-in uct_search) or of 32 768 (the self-play actor).
+    With 1, 3 and 19 boards no persistent workgroup takes a second board; the last count gives every workgroup several (n = CUs): the riding
+    epilogue of the previous board, the counted s_waitcnt vmcnt and -- (9, 64): 17 n + 5 boards, the smallest count at which a workgroup runs
+    a full corner batch of 16 boards and then a partial one; (9, 128): 4 n + 3 boards = pairs and an odd last board -- the corner batches."""
     from alpha_zero_amd import _lib
 
     bnd = _lib.load()
-    for boards in (1, 3, 19):
+    n = torch.cuda.get_device_properties(0).multi_processor_count
+    for boards in (1, 3, 19, {(9, 64): 17 * n + 5, (17, 64): 2 * n + 3, (9, 128): 4 * n + 3}[(S, C)]):
         for res, relu in CASES:
             x, r, w, b = _case_inputs(boards, C, S, 300 + boards, res, relu)
             with su.small_batch_waves(bnd.dll, 0):

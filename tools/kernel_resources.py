@@ -25,24 +25,28 @@ def code_object(lib):
     raise SystemExit("no gfx950 code object in " + lib)
 
 
+def resources(co_path):
+    """{demangled kernel name: (vgpr+agpr, agpr, sgpr, lds bytes, scratch bytes)} of a code object file"""
+    notes = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--notes", co_path], capture_output=True, text=True, check=True).stdout
+    names = subprocess.run(["c++filt"], input="\n".join(re.findall(r"\.name:\s+(\S+)", notes)), capture_output=True,
+                           text=True).stdout.split("\n")
+    out = {}
+    for k, blk in enumerate(notes.split("- .agpr_count:")[1:]):
+        g = lambda key: int(re.search(r"\." + key + r":\s+(\d+)", blk).group(1))
+        out[names[k] if k < len(names) else "?"] = (g("vgpr_count"), int(blk.split()[0]), g("sgpr_count"), g("group_segment_fixed_size"),
+                                                    g("private_segment_fixed_size"))
+    return out
+
+
 def main():
     pat = sys.argv[1] if len(sys.argv) > 1 else ""
     with tempfile.NamedTemporaryFile(suffix=".co") as f:
         f.write(code_object(os.path.join(ROOT, "alpha_zero_amd", "libazsp.so")))
         f.flush()
-        notes = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--notes", f.name], capture_output=True, text=True, check=True).stdout
-        names = subprocess.run(["c++filt"], input="\n".join(re.findall(r"\.name:\s+(\S+)", notes)), capture_output=True,
-                               text=True).stdout.split("\n")
-    k = 0
-    for blk in notes.split("- .agpr_count:")[1:]:
-        name = names[k] if k < len(names) else "?"
-        k += 1
-        if pat not in name:
-            continue
-        g = lambda key: int(re.search(r"\." + key + r":\s+(\d+)", blk).group(1))
-        agpr = int(blk.split()[0])
-        print(f"{name[:110]:110s} vgpr+agpr {g('vgpr_count'):3d} (agpr {agpr:3d}) sgpr {g('sgpr_count'):3d} "
-              f"lds {g('group_segment_fixed_size'):6d} scratch {g('private_segment_fixed_size')}")
+        res = resources(f.name)
+    for name, (vgpr, agpr, sgpr, lds, scratch) in res.items():
+        if pat in name:
+            print(f"{name[:110]:110s} vgpr+agpr {vgpr:3d} (agpr {agpr:3d}) sgpr {sgpr:3d} lds {lds:6d} scratch {scratch}")
 
 
 if __name__ == "__main__":

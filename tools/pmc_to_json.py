@@ -123,7 +123,7 @@ def main():
     if "note" in js:
         js.setdefault("earlier_rounds", {})["note"] = js.pop("note")
     js["kernel"] = " / ".join(sorted({short_name(n) for n in kernels})) + " (round 6 pass on this round's sources; both instantiations where templated on the residual add)"
-    js["note"] = ("separate rocprofv3 runs per counter group (tools/profile_r06.sh over tools/pmc_launches.py, post-ReLU-like data); FETCH_SIZE counts 64 B per "
+    js["note"] = ("separate rocprofv3 runs per counter group (tools/pmc_launches.py under rocprofv3 --pmc, post-ReLU-like data); FETCH_SIZE counts 64 B per "
                   "128-B request (x2, profiles/r01_pmc_calibration.txt); cycles = GRBM_GUI_ACTIVE / 8 XCDs; effective clock = cycles / the launch time of the "
                   "kernel-trace pass of the same script (6 cold launches: lower than inside a long run -- bench.py divides the cycles by ITS launch time)")
     js["source_round6"] = ["profiles/" + os.path.basename(src), "profiles/r01_pmc_calibration.txt (FETCH_SIZE x 2)"]
