@@ -17,8 +17,9 @@
 //   * LDS-DMA double buffering of the next tile under the MFMAs, one barrier per tile, epilogue (residual, one bf16 rounding, ReLU)
 //     straight from the accumulators: the D layout hands a lane 4 consecutive couts of its position = an 8-byte slot.
 // k_resblock64 (below) fuses the two convolutions of a ResNetBlock on the same geometry and keeps the intermediate activation in LDS.
+// The LDS-DMA piece and its lane plan, the set-up pieces and the epilogue arithmetic are the shared lp_* pieces of az_conv_lp.h.
 #pragma once
-#include "az_conv.h"
+#include "az_conv_lp.h"
 
 #if defined(__HIPCC__)
 #define C6_C 64
@@ -59,7 +60,7 @@ template <> struct C6Geo<9> {
     }
 };
 
-typedef __attribute__((ext_vector_type(4))) float c6_f32x4;
+typedef lp_f32x4 c6_f32x4;
 
 // (column tile, lane & 15) -> position / cell: column tile k takes the k-th position cell of every residue class mod 16 (no class
 // has more than NCT of the tile's cells); the unfilled slots repeat the first position of a residue the tile still lacks.
@@ -85,28 +86,13 @@ template <class G> constexpr Cw64Map<G> cw64_make_map() {
         used[k][r] = true;
         if (k + 1 > m.real_tiles) m.real_tiles = k + 1;
     }
-    for (int k = 0; k < G::NCT; ++k)
-        for (int r = 0; r < 16 && fill[k] < 16; ++r) {
-            if (used[k][r]) continue;
-            for (int p = 0; p < G::P2; ++p) {
-                const int cell = G::cell_of(p);
-                if ((cell & 15) == r) {
-                    m.cell[k * 16 + fill[k]] = (unsigned short)cell;
-                    m.pos[k * 16 + fill[k]] = (unsigned short)p;
-                    fill[k]++;
-                    used[k][r] = true;
-                    break;
-                }
-            }
-        }
-    for (int k = 0; k < G::NCT; ++k) {  // every column tile: 16 slots, 16 distinct residues (= conflict-free ds_read_b128 lane groups)
-        bool seen[16] = {};
-        if (fill[k] != 16) ok = false;
-        for (int s = 0; s < 16; ++s) {
-            const int r = m.cell[k * 16 + s] & 15;
-            if (seen[r]) ok = false;
-            seen[r] = true;
-        }
+    for (int k = 0; k < G::NCT; ++k) {
+        lp_map_fill(fill[k], used[k], G::P2, [](int p) { return G::cell_of(p); }, [&](int i, int p) {
+            m.cell[k * 16 + i] = (unsigned short)G::cell_of(p);
+            m.pos[k * 16 + i] = (unsigned short)p;
+        });
+        // every column tile: 16 slots, 16 distinct residues (= conflict-free ds_read_b128 lane groups)
+        if (!lp_group_ok(fill[k], [&](int i) { return (int)m.cell[k * 16 + i]; })) ok = false;
     }
     m.ok = ok;
     return m;
@@ -164,8 +150,7 @@ k_conv3x3_t64(const unsigned char* __restrict__ x, const unsigned short* __restr
     const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, kg = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds;
-    for (int i = tid; i < 2 * LBUF / 16; i += CW_THREADS) *(cv_u32x4*)(lds + i * 16) = (cv_u32x4){0u, 0u, 0u, 0u};
-    CV_BARRIER();  // the zero cells are final before any LDS-DMA piece can land
+    lp_zero_lds<2 * LBUF>(lds, tid);
 
     // A fragments: step s = (tap, input half), cout tile q: lane (cout = 16 q + l15, cin = 32 half + 8 kg .. + 8)
     cv_bf16x8 wf[NSTEP * 4];
@@ -184,21 +169,9 @@ k_conv3x3_t64(const unsigned char* __restrict__ x, const unsigned short* __restr
     // LDS-DMA plan: a strip is NP pieces of 64 cells; wave q moves strips SPW q .. SPW q + SPW - 1
     unsigned dsrc[NP];
     unsigned long long dmask[NP];
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-        const int p = G::pos_of_cell(64 * i + lane, IN_S, IN_OFF);
-        dsrc[i] = (unsigned)((p < 0 ? 0 : p) * 16);
-        dmask[i] = __builtin_amdgcn_ballot_w64(p >= 0);
-    }
+    lp_dma_plan(dsrc, dmask, lane, [](int cell) { return G::pos_of_cell(cell, IN_S, IN_OFF) * 16; });
     auto dma_piece = [&](const unsigned char* src, unsigned dstbuf, bool live, int i) {  // i in [0, NPIECE): strip SPW wave + i / NP, piece i % NP
-        const int c = SPW * wave + i / NP, pc = i % NP;
-        const unsigned long long base = (unsigned long long)(src + (size_t)c * IN_GBLK);
-        const unsigned long long mask = live ? dmask[pc] : 0ull;
-        const unsigned dst = dstbuf + (unsigned)(c * LBLK + pc * 1024);
-        asm volatile("s_mov_b64 exec, %0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b64 exec, -1"
-                     :
-                     : "s"(mask), "s"(dst), "v"(dsrc[pc]), "s"(base)
-                     : "memory");
+        lp_dma_piece(src, dstbuf, SPW * wave + i / NP, i % NP, IN_GBLK, LBLK, live ? dmask[i % NP] : 0ull, dsrc[i % NP]);
     };
 
     // this lane's NJ column tiles (wave's tiles: 4 j + wave): LDS byte offset of the (-1, -1) neighbour in its own 8-channel group
@@ -207,7 +180,7 @@ k_conv3x3_t64(const unsigned char* __restrict__ x, const unsigned short* __restr
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         const int idx = (4 * j + wave) * 16 + l15;
-        lmap[j] = (unsigned)((cw64_map<G>().cell[idx] - G::CELL0) * 16 + kg * LBLK) | ((unsigned)cw64_map<G>().pos[idx] << 16);
+        lmap[j] = lp_lmap(cw64_map<G>().cell[idx], G::CELL0, kg * LBLK, cw64_map<G>().pos[idx]);
     }
     cv_bf16x8 bb[2][NJ];  // B fragments: k-step s lives in slot s & 1
     auto load_step = [&](const unsigned char* const (&bp)[NJ], int s) {  // tap s / HALVES = constant cell offset, input half = 4 strips on
@@ -230,11 +203,7 @@ k_conv3x3_t64(const unsigned char* __restrict__ x, const unsigned short* __restr
         for (int j = 0; j < NJ; ++j) bp0[j] = lds + (lmap[j] & 0xffffu);
         load_step(bp0, 0);
     }
-#pragma unroll
-    for (int t = 0; t < NSTEP * 4; ++t) {  // the compiler's wait for the weight loads belongs in front of the loop (see az_conv.h)
-        if (t < 64) asm volatile("" : : "a"(wf[t]));
-        else asm volatile("" : : "v"(wf[t]));
-    }
+    lp_pin_a<64>(wf);
     asm volatile("" : : "v"(bv[0]), "v"(bv[3]), "v"(lmap[0]), "v"(lmap[NJ - 1]), "v"(dsrc[0]), "v"(dsrc[NP - 1]));
 
     int it = 0;
@@ -293,18 +262,7 @@ k_conv3x3_t64(const unsigned char* __restrict__ x, const unsigned short* __restr
             // cout tile q, lane group kg: couts 16 q + 4 kg .. + 4 = chunk 2 q + kg / 2, half kg % 2
             const unsigned gq = (lmap[j] >> 16) * 16u + (unsigned)((kg >> 1) * GBLK + (kg & 1) * 8);
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float v0 = acc[j][q][0], v1 = acc[j][q][1], v2 = acc[j][q][2], v3 = acc[j][q][3];
-                if (RES) {
-                    const cv_u32x2 r2 = rr[j][q];
-                    v0 += cv_bf16_lo(r2.x);
-                    v1 += cv_bf16_hi(r2.x);
-                    v2 += cv_bf16_lo(r2.y);
-                    v3 += cv_bf16_hi(r2.y);
-                }
-                *(cv_u32x2*)(ybase + (2 * q) * GBLK + gq) =
-                    (cv_u32x2){cw_pk_max_i16(cw_pk_bf16(v0, v1), lo16), cw_pk_max_i16(cw_pk_bf16(v2, v3), lo16)};
-            }
+            for (int q = 0; q < 4; ++q) *(cv_u32x2*)(ybase + (2 * q) * GBLK + gq) = lp_epi_quad<RES>(acc[j][q], rr[j][q], lo16);
         }
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -355,8 +313,7 @@ k_resblock64(const unsigned char* __restrict__ x, const unsigned short* __restri
     const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, kg = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), h = wave & 1, ph = wave >> 1;
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds;
-    for (int i = tid; i < 3 * LBUF / 16; i += CW_THREADS) *(cv_u32x4*)(lds + i * 16) = (cv_u32x4){0u, 0u, 0u, 0u};
-    CV_BARRIER();  // the zero cells are final before any LDS-DMA piece can land
+    lp_zero_lds<3 * LBUF>(lds, tid);
     unsigned char* const MID = lds + 2 * LBUF;
 
     // A fragments: f = 36 conv + 2 s + slot, k-step s = (tap, input half): lane (cout = 16 (2 h + (slot ^ ph)) + l15, cin = 32 half + 8 kg .. + 8)
@@ -377,21 +334,9 @@ k_resblock64(const unsigned char* __restrict__ x, const unsigned short* __restri
 
     unsigned dsrc[NP];
     unsigned long long dmask[NP];
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-        const int p = G::pos_of_cell(64 * i + lane, G::S, 0);
-        dsrc[i] = (unsigned)((p < 0 ? 0 : p) * 16);
-        dmask[i] = __builtin_amdgcn_ballot_w64(p >= 0);
-    }
+    lp_dma_plan(dsrc, dmask, lane, [](int cell) { return G::pos_of_cell(cell, G::S, 0) * 16; });
     auto dma_piece = [&](const unsigned char* src, unsigned dstbuf, bool live, int i) {  // strip 2 wave + i / NP, piece i % NP
-        const int c = 2 * wave + i / NP, pc = i % NP;
-        const unsigned long long base = (unsigned long long)(src + (size_t)c * GBLK);
-        const unsigned long long mask = live ? dmask[pc] : 0ull;
-        const unsigned dst = dstbuf + (unsigned)(c * LBLK + pc * 1024);
-        asm volatile("s_mov_b64 exec, %0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b64 exec, -1"
-                     :
-                     : "s"(mask), "s"(dst), "v"(dsrc[pc]), "s"(base)
-                     : "memory");
+        lp_dma_piece(src, dstbuf, 2 * wave + i / NP, i % NP, GBLK, LBLK, live ? dmask[i % NP] : 0ull, dsrc[i % NP]);
     };
 
     // this lane's column tiles, local tile m = 2 u + j: own tiles m < NOWN = column tile 2 m + ph, then (17x17) the shared tile:
@@ -400,7 +345,7 @@ k_resblock64(const unsigned char* __restrict__ x, const unsigned short* __restri
 #pragma unroll
     for (int m = 0; m < NUNIT; ++m) {
         const int idx = (m < NOWN ? 2 * m + ph : G::NCT_REAL - 1) * 16 + l15;
-        lmap[m] = (unsigned)((cw64_map<G>().cell[idx] - G::CELL0) * 16 + kg * LBLK) | ((unsigned)cw64_map<G>().pos[idx] << 16);
+        lmap[m] = lp_lmap(cw64_map<G>().cell[idx], G::CELL0, kg * LBLK, cw64_map<G>().pos[idx]);
     }
     // the 8-byte slot of (position, couts 16 ct + 4 kg .. + 4), ct = 2 h + (slot ^ ph): chunk 2 ct + kg / 2, half kg % 2
     int wconst[2];       // + (lmap & 0xffff) = offset inside an LDS image
@@ -429,11 +374,7 @@ k_resblock64(const unsigned char* __restrict__ x, const unsigned short* __restri
 #pragma unroll
         for (int s = 0; s < R - 1; ++s) load_step(lds + (lmap[0] & 0xffffu), lds + (lmap[1] & 0xffffu), s, s);
     }
-#pragma unroll
-    for (int f = 0; f < 72; ++f) {  // the compiler's wait for the weight loads belongs in front of the loop (see az_conv.h)
-        if (f < 64) asm volatile("" : : "a"(wf[f]));
-        else asm volatile("" : : "v"(wf[f]));
-    }
+    lp_pin_a<64>(wf);
     asm volatile("" : : "v"(bv[0][0]), "v"(bv[1][1]), "v"(lmap[0]), "v"(lmap[NUNIT - 1]), "v"(dsrc[0]), "v"(dsrc[NP - 1]));
 
     c6_f32x4 acc[2][2][2];  // [unit parity][column tile j][slot]
@@ -445,39 +386,24 @@ k_resblock64(const unsigned char* __restrict__ x, const unsigned short* __restri
             acc[a][q >> 1][q & 1] = (c6_f32x4){0.0f, 0.0f, 0.0f, 0.0f};
             rr[a][q] = (cv_u32x2){0u, 0u};
         }
-    float ev[4];  // one epilogue quad between its phases
 
-    // Epilogues as MICRO-OPS: one or two instructions each, issued one per MFMA gap.  Measured with the ablation harness
-    // (tools/probes/block64_abl_probe.hip, profiles/r03_block64_ablation.txt): with the epilogue of a quad issued as one block of 8-16
-    // VALU instructions behind a k-step's four 16-cycle MFMAs the riders cost 18.6 % of the launch's cycles (matrix pipe busy 66 % ->
-    // 81 % without them) -- a 16x16x32 MFMA leaves room for about one VALU instruction in its shadow, not for a burst.
-    unsigned epa = 0, epb = 0;  // packed halves of the quad in flight
-    // first-convolution unit, quad q = 2 j + slot: ReLU, one bf16 rounding, 8 bytes into the intermediate image.  6 micro-ops.
+    // Epilogues as MICRO-OPS (LpEpi), issued one per MFMA gap.  Measured with the ablation harness (tools/probes/block64_abl_probe.hip,
+    // profiles/r03_block64_ablation.txt): with the epilogue of a quad issued as one block of 8-16 VALU instructions behind a k-step's four
+    // 16-cycle MFMAs the riders cost 18.6 % of the launch's cycles (matrix pipe busy 66 % -> 81 % without them).
+    LpEpi epi;
+    constexpr int MID_OPS = LpEpi::ops(false), OUT_OPS = LpEpi::ops(true);
+    // first-convolution unit, quad q = 2 j + slot: one bf16 rounding, ReLU, 8 bytes into the intermediate image
     auto epi_mid_op = [&](int set, int m0, int q, int op) {
         const int j = q >> 1, sl = q & 1;
-        if (op == 0) epa = cw_pk_bf16(acc[set][j][sl][0], acc[set][j][sl][1]);
-        else if (op == 1) epb = cw_pk_bf16(acc[set][j][sl][2], acc[set][j][sl][3]);
-        else if (op == 2) epa = cw_pk_max_i16(epa, 0u);
-        else if (op == 3) epb = cw_pk_max_i16(epb, 0u);
-        else if (op == 4) *(cv_u32x2*)(MID + ((int)(lmap[m0 + j] & 0xffffu) + wconst[sl])) = (cv_u32x2){epa, epb};
+        if (op < MID_OPS - 1) epi.op<false>(op, acc[set][j][sl], rr[set][q], 0u);
+        else *(cv_u32x2*)(MID + ((int)(lmap[m0 + j] & 0xffffu) + wconst[sl])) = (cv_u32x2){epi.epa, epi.epb};
     };
-    constexpr int MID_OPS = 5;
-    // second-convolution unit, quad q: skip add (plain v_add_f32, see az_conv.h), rounding, ReLU, 8-byte store.  9 micro-ops.
+    // second-convolution unit, quad q: skip add, rounding, ReLU, 8-byte store
     auto epi_out_op = [&](int set, int m0, unsigned char* out, int q, int op, bool store_ok) {
         const int j = q >> 1, sl = q & 1;
-        if (op == 0) ev[0] = cw_add_f32(acc[set][j][sl][0], cv_bf16_lo(rr[set][q].x));
-        else if (op == 1) ev[1] = cw_add_f32(acc[set][j][sl][1], cv_bf16_hi(rr[set][q].x));
-        else if (op == 2) ev[2] = cw_add_f32(acc[set][j][sl][2], cv_bf16_lo(rr[set][q].y));
-        else if (op == 3) ev[3] = cw_add_f32(acc[set][j][sl][3], cv_bf16_hi(rr[set][q].y));
-        else if (op == 4) epa = cw_pk_bf16(ev[0], ev[1]);
-        else if (op == 5) epb = cw_pk_bf16(ev[2], ev[3]);
-        else if (op == 6) epa = cw_pk_max_i16(epa, 0u);
-        else if (op == 7) epb = cw_pk_max_i16(epb, 0u);
-        else if (op == 8) {
-            if (store_ok) *(cv_u32x2*)(out + ((lmap[m0 + j] >> 16) * 16u + gconst[sl])) = (cv_u32x2){epa, epb};
-        }
+        if (op < OUT_OPS - 1) epi.op<true>(op, acc[set][j][sl], rr[set][q], 0u);
+        else if (store_ok) *(cv_u32x2*)(out + ((lmap[m0 + j] >> 16) * 16u + gconst[sl])) = (cv_u32x2){epi.epa, epi.epb};
     };
-    constexpr int OUT_OPS = 9;
     auto epi_mid = [&](int set, int m0, int q) {  // whole quad at once (the exposed epilogue before B2)
 #pragma unroll
         for (int op = 0; op < MID_OPS; ++op) epi_mid_op(set, m0, q, op);

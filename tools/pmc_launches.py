@@ -1,7 +1,7 @@
 """A handful of launches of ONE tower-convolution kernel family on post-ReLU-like data, for `rocprofv3 --pmc ...` / `--kernel-trace` passes.
 usage: python tools/pmc_launches.py <family> [boards]    family: split9 (k_conv3x3_sp2p, 9x9 x 128), split9_64, split17 (k_conv3x3_sp17,
 17x17 x 64), splitblock17 / splitblock9_64 (k_resblock_sp: one launch per ResNetBlock, 17x17 x 64 / 9x9 x 64), tiled9 (k_conv3x3_tiled bf16, 9x9 x 128), hb19
-(k_conv3x3_hb19 bf16, 19x19 x 256, two launches per convolution), spg19 (k_conv3x3_spgw: the wave-per-tile fp32-class convolution on 19x19 x 256, 1024 boards).
+(bf16, 19x19 x 256: k_conv3x3_op19q, one launch per convolution; with AZSP_CONV19_TWO_LAUNCH=1 k_conv3x3_hb19, two launches), spg19 (k_conv3x3_spgw: the wave-per-tile fp32-class convolution on 19x19 x 256, 1024 boards).
 Launch i uses a residual when i is odd (the forward alternates plain / residual layers)."""
 import os
 import sys

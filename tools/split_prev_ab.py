@@ -4,8 +4,10 @@
 Cases: the 9x9 x 128 convolution (k_conv3x3_sp2p, plain and with a residual), the 9x9 x 64 and 17x17 x 64 convolutions (k_conv3x3_sp<.., 8, 1>,
 k_conv3x3_sp17<.., 8>, plain and with a residual), the fused 17x17 x 64 and 9x9 x 64 blocks (k_resblock_sp<Sb17 | Sb9>), the three tailored stems
 (9x9 -> 128, 9x9 -> 64, 13x13 pad 3 -> 17x17 x 64: k_conv3x3_sp / k_conv3x3_sp17 with 4 input chunks) through azsp_stem_split (random fp32 planes)
-and azsp_stem_split_exact (0 / 1 planes), (+ the bf16 19x19 x 256 convolution, k_conv3x3_op19q).  PREV_AB_CASES=<substring>[,<substring>...]
-selects cases.  other_lib may be a comma-separated list: with a second COPY of the other build (another file) the same run also gives the A/A
+and azsp_stem_split_exact (0 / 1 planes); and the lower-precision (bf16) kernels through the tiled ABI: azsp_conv3x3_tiled at 9x9 x 64 and
+17x17 x 64 (k_conv3x3_t64) and at 19x19 x 256 (k_conv3x3_op19q; k_conv3x3_hb19 twice in a process started with AZSP_CONV19_TWO_LAUNCH=1), plain
+and with a residual, azsp_resblock_tiled at both 64-filter geometries (k_resblock64), azsp_stem_tiled at 9x9 -> 64, 13x13 pad 3 -> 64
+(k_conv3x3_t64 with 4 input chunks) and 19x19 -> 256 (k_conv3x3_hb19 with 4).  PREV_AB_CASES=<substring>[,<substring>...] selects cases.  other_lib may be a comma-separated list: with a second COPY of the other build (another file) the same run also gives the A/A
 spread of every case -- the margin below which a tree / other ratio says nothing.
 usage: python tools/split_prev_ab.py [other_lib[,other_lib2...]] [rounds]"""
 import ctypes
@@ -91,11 +93,13 @@ def case_stem(n, pad, C, exact):
     return run, ys, 2.0 * B * S * S * 32 * C * 9 * (2 if exact else 3)
 
 
-def case_conv19(residual, boards=4096):
-    """the bf16 19x19 x 256 tower convolution (BASELINE C5's dominant kernel, k_conv3x3_op19q) through azsp_conv3x3_tiled"""
-    S, C = 19, 256
-    d = libs["tree"].dll
-    g = torch.Generator().manual_seed(3)
+TILED_BOARDS = {9: 12288, 17: 4096, 19: 4096}  # 4096 tiles (9x9: three boards per tile) = 16 per workgroup
+
+
+@functools.lru_cache(maxsize=1)
+def make_tiled(S, C, seed):
+    """bf16 activations x, r in the tiled layout, two packed weight banks, two biases, an output per build"""
+    boards, d, g = TILED_BOARDS[S], libs["tree"].dll, torch.Generator().manual_seed(seed)
     n = d.azsp_tiled_bytes(boards, S, C) // 2
     xt, rt = (torch.zeros(n, dtype=torch.bfloat16, device="cuda") for _ in range(2))
     for dst in (xt, rt):
@@ -103,17 +107,54 @@ def case_conv19(residual, boards=4096):
         t = torch.where(torch.rand(boards, C, S, S, generator=g) < 0.5, torch.zeros(()), t.abs()).to(torch.bfloat16).cuda().contiguous(memory_format=torch.channels_last)
         assert d.azsp_tile_layout(t.data_ptr(), dst.data_ptr(), boards, S, C, 1, None) == 0
         del t
-    w = (torch.randn(C, C, 3, 3, generator=g) * (2.0 / (9 * C)) ** 0.5).to(torch.bfloat16).cuda()
-    wp = w.permute(2, 3, 0, 1).reshape(9, C, C).contiguous()
-    bias = (torch.randn(C, generator=g) * 0.1).cuda()
+    ws = [(torch.randn(C, C, 3, 3, generator=g) * (2.0 / (9 * C)) ** 0.5).to(torch.bfloat16).cuda().permute(2, 3, 0, 1).reshape(9, C, C).contiguous() for _ in range(2)]
+    bs = [(torch.randn(C, generator=g) * 0.1).cuda() for _ in range(2)]
     ys = {k: torch.zeros(n, dtype=torch.bfloat16, device="cuda") for k in libs}
+    torch.cuda.synchronize()
+    return boards, xt, rt, ws, bs, ys
+
+
+def case_conv_tiled(S, C, residual):
+    """a bf16 tower convolution through azsp_conv3x3_tiled (19x19 x 256: BASELINE C5's dominant kernel)"""
+    boards, xt, rt, ws, bs, ys = make_tiled(S, C, 3)
+
+    def run(k, reps, o=None):
+        for _ in range(reps):
+            assert libs[k].dll.azsp_conv3x3_tiled(xt.data_ptr(), ws[0].data_ptr(), bs[0].data_ptr(), rt.data_ptr() if residual else None, ys[o or k].data_ptr(), boards, S, C, 1, st) == 0
+
+    return run, ys, 2.0 * boards * S * S * C * C * 9
+
+
+def case_block_tiled(S, C):
+    boards, xt, rt, ws, bs, ys = make_tiled(S, C, 5)
+
+    def run(k, reps, o=None):
+        for _ in range(reps):
+            assert libs[k].dll.azsp_resblock_tiled(xt.data_ptr(), ws[0].data_ptr(), bs[0].data_ptr(), ws[1].data_ptr(), bs[1].data_ptr(), ys[o or k].data_ptr(), boards, S, C, st) == 0
+
+    return run, ys, 2 * 2.0 * boards * S * S * C * C * 9
+
+
+def case_stem_tiled(n, pad, C):
+    """a bf16 stem: n x n boards of 17 planes in 32 tiled channels -> C filters on planes of n + 2 (pad - 1)"""
+    S, d, g = n + 2 * (pad - 1), libs["tree"].dll, torch.Generator().manual_seed(6)
+    boards = TILED_BOARDS[S]
+    x = torch.zeros(boards, 32, n, n)
+    x[:, :17] = (torch.rand(boards, 17, n, n, generator=g) > 0.6).float()
+    feat = torch.zeros(d.azsp_tiled_bytes(boards, n, 32) // 2, dtype=torch.bfloat16, device="cuda")
+    xc = x.to(torch.bfloat16).cuda().contiguous(memory_format=torch.channels_last)
+    assert d.azsp_tile_layout(xc.data_ptr(), feat.data_ptr(), boards, n, 32, 1, None) == 0
+    w32 = torch.zeros(C, 32, 3, 3)
+    w32[:, :17] = torch.randn(C, 17, 3, 3, generator=g) * 0.1
+    w, bias = w32.to(torch.bfloat16).cuda().permute(2, 3, 0, 1).reshape(9, C, 32).contiguous(), (torch.randn(C, generator=g) * 0.1).cuda()
+    ys = {k: torch.zeros(d.azsp_tiled_bytes(boards, S, C) // 2, dtype=torch.bfloat16, device="cuda") for k in libs}
     torch.cuda.synchronize()
 
     def run(k, reps, o=None):
         for _ in range(reps):
-            assert libs[k].dll.azsp_conv3x3_tiled(xt.data_ptr(), wp.data_ptr(), bias.data_ptr(), rt.data_ptr() if residual else None, ys[o or k].data_ptr(), boards, S, C, 1, st) == 0
+            assert libs[k].dll.azsp_stem_tiled(feat.data_ptr(), w.data_ptr(), bias.data_ptr(), ys[o or k].data_ptr(), boards, n, C, pad, 1, st) == 0
 
-    return run, ys, 2.0 * boards * S * S * C * C * 9
+    return run, ys, 2.0 * boards * S * S * 32 * C * 9
 
 
 CASES = (("conv 9x9 x 128 plain", lambda: case_conv(9, 128, False)), ("conv 9x9 x 128 residual", lambda: case_conv(9, 128, True)),
@@ -122,7 +163,10 @@ CASES = (("conv 9x9 x 128 plain", lambda: case_conv(9, 128, False)), ("conv 9x9 
          ("block 17x17 x 64", lambda: case_block(17, 64)), ("block 9x9 x 64", lambda: case_block(9, 64)),
          *((f"stem {n}x{n} pad {pad} -> {C}{' exact' if exact else ''}", lambda n=n, pad=pad, C=C, exact=exact: case_stem(n, pad, C, exact))
            for n, pad, C in ((9, 1, 128), (9, 1, 64), (13, 3, 64)) for exact in (False, True)),
-         ("conv 19x19 x 256 bf16 plain", lambda: case_conv19(False)), ("conv 19x19 x 256 bf16 residual", lambda: case_conv19(True)))
+         *((f"conv {S}x{S} x {C} bf16 {'residual' if res else 'plain'}", lambda S=S, C=C, res=res: case_conv_tiled(S, C, res))
+           for S, C in ((9, 64), (17, 64), (19, 256)) for res in (False, True)),
+         ("block 9x9 x 64 bf16", lambda: case_block_tiled(9, 64)), ("block 17x17 x 64 bf16", lambda: case_block_tiled(17, 64)),
+         *((f"stem {n}x{n} pad {pad} -> {C} bf16", lambda n=n, pad=pad, C=C: case_stem_tiled(n, pad, C)) for n, pad, C in ((9, 1, 64), (13, 3, 64), (19, 1, 256))))
 ONLY = os.environ.get("PREV_AB_CASES", "").split(",")
 for name, mk in [c for c in CASES if any(o in c[0] for o in ONLY)]:
     run, ys, flops = mk()
