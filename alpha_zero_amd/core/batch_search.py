@@ -17,15 +17,17 @@ import torch
 
 from .. import _abi
 from ..envs.base import BoardGameEnv
-from .engine import Engine, EngineConfig, forced_playouts_k
+from .engine import Engine, EngineConfig, check_gumbel_alone, forced_playouts_k, gumbel_params
 
 
 def dropin_engine(game, board_size, num_games, num_simulations, num_parallel, c_puct_base, c_puct_init, root_noise, komi=7.5, max_steps=0,
-                  num_to_win=5, num_stack=8, binding=None, device=None, leaf_symmetry=None, forced_playouts=None):
+                  num_to_win=5, num_stack=8, binding=None, device=None, leaf_symmetry=None, forced_playouts=None, gumbel=None):
     """The engine of a drop-in search, `uct_search`'s with one game and a BatchSearch's with `capacity`: it stops after every move
     (`stop_after_move`), hands out int8 observation planes and logs no moves.  Without a `binding` it runs the product library on the GPU.
-    leaf_symmetry: EngineConfig.leaf_symmetry (None = off).  forced_playouts: EngineConfig.forced_playouts (None = off)."""
+    leaf_symmetry: EngineConfig.leaf_symmetry (None = off).  forced_playouts: EngineConfig.forced_playouts (None = off).
+    gumbel: EngineConfig.gumbel (None = off)."""
     forced_playouts_k(forced_playouts)  # ValueError before anything is built
+    check_gumbel_alone(gumbel, forced_playouts)
     if binding is None:
         from .. import _lib
 
@@ -33,7 +35,7 @@ def dropin_engine(game, board_size, num_games, num_simulations, num_parallel, c_
     cfg = EngineConfig(game=game, board_size=board_size, num_games=num_games, num_parallel=num_parallel, num_simulations=num_simulations,
                        c_puct_base=c_puct_base, c_puct_init=c_puct_init, root_noise=root_noise, komi=komi, max_steps=max_steps or 0,
                        num_to_win=num_to_win, num_stack=num_stack, stop_after_move=True, feature_dtype=_abi.FEAT_I8, log_moves=False,
-                       leaf_symmetry=leaf_symmetry, forced_playouts=forced_playouts)
+                       leaf_symmetry=leaf_symmetry, forced_playouts=forced_playouts, gumbel=gumbel)
     return Engine(binding, cfg, device=device)
 
 
@@ -209,10 +211,12 @@ def choose_move(env, search_pi, child_n, root_legal, warm_up, deterministic):
 
 class SearchResults:
     """`BatchSearch.results()`: device tensors, one row per active slot; `.cpu()` returns pi, child_N and root_Q as NumPy arrays.
-    target_pi: None, or with forced playouts on float64[n, A], the pruned policy target of every slot's search (pi stays unpruned)."""
+    target_pi: None, or with forced playouts on float64[n, A], the pruned policy target of every slot's search (pi stays unpruned); with
+    the Gumbel root search on, the completed-Q target pi'.  gumbel_move: None, or with the Gumbel root search on int32[n], the move a*
+    of every slot's search -- the one to commit."""
 
-    def __init__(self, pi, child_N, root_Q, target_pi=None):
-        self.pi, self.child_N, self.root_Q, self.target_pi = pi, child_N, root_Q, target_pi
+    def __init__(self, pi, child_N, root_Q, target_pi=None, gumbel_move=None):
+        self.pi, self.child_N, self.root_Q, self.target_pi, self.gumbel_move = pi, child_N, root_Q, target_pi, gumbel_move
 
     def cpu(self):
         return self.pi.cpu().numpy(), self.child_N.cpu().numpy(), self.root_Q.cpu().numpy()
@@ -225,8 +229,12 @@ class BatchSearch:
     """
 
     def __init__(self, game, board_size, capacity, num_simulations, num_parallel=1, c_puct_base=19652.0, c_puct_init=1.25, root_noise=False,
-                 komi=7.5, max_steps=0, num_to_win=5, num_stack=8, binding=None, device=None, leaf_symmetry=None, forced_playouts=None):
-        """forced_playouts: None or k >= 0 (Engine.set_forced_playouts; the reference search has none): forced playouts at the root; the
+                 komi=7.5, max_steps=0, num_to_win=5, num_stack=8, binding=None, device=None, leaf_symmetry=None, forced_playouts=None,
+                 gumbel=None):
+        """gumbel: None, m or (m, c_visit, c_scale) (Engine.set_gumbel; the reference search has none): Gumbel root search; the move to
+        commit is `results().gumbel_move`, the sample to record `results().target_pi`; `search(noise=...)` takes the Gumbel(0, 1) rows
+        (None: drawn here with np.random.gumbel) and root_noise is ignored.  Not together with forced_playouts.
+        forced_playouts: None or k >= 0 (Engine.set_forced_playouts; the reference search has none): forced playouts at the root; the
         move is still to be chosen from `results().pi`, the sample to record is `results().target_pi` (None when off).
         leaf_symmetry: None, "random" or an op 0..7 (Engine.set_leaf_symmetry; the reference search has none): `eval_func` -- host
         callback or resident evaluator -- is handed every leaf position under that board symmetry ("random": one drawn per feature row)
@@ -235,10 +243,12 @@ class BatchSearch:
             raise ValueError(f"capacity must be at least 1, got {capacity}")
         check_num_simulations(num_simulations)
         self.forced_playouts = forced_playouts_k(forced_playouts) > 0.0
+        check_gumbel_alone(gumbel, forced_playouts)
+        self.gumbel = gumbel_params(gumbel)[0] > 0
         self.game, self.capacity, self.num_simulations, self.num_parallel = game, int(capacity), int(num_simulations), int(num_parallel)
         self.key = _key(game, board_size, komi, max_steps, num_to_win, num_stack)
         self.eng = dropin_engine(game, board_size, self.capacity, num_simulations, num_parallel, c_puct_base, c_puct_init, root_noise, komi,
-                                 max_steps, num_to_win, num_stack, binding, device, leaf_symmetry, forced_playouts)
+                                 max_steps, num_to_win, num_stack, binding, device, leaf_symmetry, forced_playouts, gumbel)
         self.slots = np.zeros(0, dtype=np.int64)  # the active slots (a position is loaded, or a sub-tree was kept), ascending
         self._status = np.full(self.capacity, _abi.ST_IDLE, dtype=np.int32)  # host mirror of the slots' status after load / search / commit
         self._budgets_set = False  # an earlier search left per-slot budgets in the engine (search(num_simulations=...))
@@ -328,7 +338,8 @@ class BatchSearch:
 
     # -- search ---------------------------------------------------------------------------------------
     def search(self, eval_func, noise=None, warm_up=False, num_simulations=None):
-        """Run every active slot's search to its end (status MOVE_DONE).  noise: float64[len(slots), A] Dirichlet draws or None; warm_up:
+        """Run every active slot's search to its end (status MOVE_DONE).  noise: float64[len(slots), A] Dirichlet draws or None (with
+        `gumbel` on: Gumbel(0, 1) draws; None = drawn here from np.random); warm_up:
         a bool, or one bool per active slot (both in `self.slots` order).  num_simulations: None = this object's own number for every
         slot; an int, or one int per active slot in `self.slots` order, in 1..self.num_simulations = that slot's budget for THIS call
         (a kept sub-tree whose root already has that many visits is done at once, as in the reference's `while root.N < budget`).
@@ -351,6 +362,8 @@ class BatchSearch:
         warm = np.full(G, _abi.BM_SKIP, dtype=np.int32)
         warm[sl] = np.broadcast_to(np.asarray(warm_up, dtype=bool), (len(sl),)).astype(np.int32)
         full_noise = None
+        if noise is None and self.gumbel:
+            noise = np.random.gumbel(size=(len(sl), eng.A))
         if noise is not None:
             nz = noise if isinstance(noise, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(noise, dtype=np.float64))
             nz = nz.to(device=eng.device, dtype=torch.float64).reshape(len(sl), eng.A)
@@ -372,8 +385,9 @@ class BatchSearch:
         pi = pi.index_select(0, idx)
         if self.game != "go":
             pi = pi.to(torch.float32)  # float64 for Go, float32 for Gomoku
-        target = self.eng.target_policies().index_select(0, idx) if self.forced_playouts else None
-        return SearchResults(pi, cn.index_select(0, idx), q.index_select(0, idx)[:, _abi.STQ_ROOT_Q].contiguous(), target)
+        target = self.eng.target_policies().index_select(0, idx) if (self.forced_playouts or self.gumbel) else None
+        moves = self.eng.gumbel_moves().index_select(0, idx) if self.gumbel else None
+        return SearchResults(pi, cn.index_select(0, idx), q.index_select(0, idx)[:, _abi.STQ_ROOT_Q].contiguous(), target, moves)
 
     def commit(self, moves):
         """The chosen move of every active slot (`self.slots` order).  Returns (best_child_Q float64[n], reusable bool[n]): a slot whose

@@ -56,6 +56,7 @@ class EngineConfig:
     device_index: int = 0
     leaf_symmetry: object = None     # None | "random" | 0..7: the board symmetry leaf positions are evaluated under (Engine.set_leaf_symmetry)
     forced_playouts: object = None   # None | k >= 0: forced playouts at the root with policy-target pruning (Engine.set_forced_playouts)
+    gumbel: object = None            # None | m | (m, c_visit, c_scale): Gumbel root search with the completed-Q target (Engine.set_gumbel)
 
 
 def leaf_symmetry_mode(mode):
@@ -78,6 +79,28 @@ def forced_playouts_k(k):
     if not isinstance(k, (bool, str)) and isinstance(k, (int, float, np.integer, np.floating)) and math.isfinite(float(k)) and float(k) >= 0.0:
         return float(k)
     raise ValueError(f"forced_playouts must be None (off) or a finite number k >= 0, got {k!r}")
+
+
+def gumbel_params(gumbel):
+    """The azsp_set_gumbel arguments (m, c_visit, c_scale) of a `gumbel` value: None = off (m = 0), an integer m >= 0 (c_visit = 50,
+    c_scale = 1.0, the paper's), or (m, c_visit, c_scale) with finite c_visit, c_scale >= 0.  Anything else raises ValueError naming these."""
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)  # noqa: E731
+    is_num = lambda v: (not isinstance(v, (bool, str)) and isinstance(v, (int, float, np.integer, np.floating))  # noqa: E731
+                        and math.isfinite(float(v)) and float(v) >= 0.0)
+    if gumbel is None:
+        return 0, 50.0, 1.0
+    if is_int(gumbel) and 0 <= int(gumbel) < 2 ** 31:
+        return int(gumbel), 50.0, 1.0
+    if isinstance(gumbel, (tuple, list)) and len(gumbel) == 3 and is_int(gumbel[0]) and 0 <= int(gumbel[0]) < 2 ** 31 and is_num(gumbel[1]) \
+            and is_num(gumbel[2]):
+        return int(gumbel[0]), float(gumbel[1]), float(gumbel[2])
+    raise ValueError(f"gumbel must be None (off), an integer m >= 0 or (m, c_visit, c_scale) with finite c_visit, c_scale >= 0, got {gumbel!r}")
+
+
+def check_gumbel_alone(gumbel, forced_playouts):
+    """Gumbel root search and forced playouts both own the root's choice: one of them at most."""
+    if gumbel_params(gumbel)[0] > 0 and forced_playouts_k(forced_playouts) > 0.0:
+        raise ValueError("gumbel and forced_playouts cannot be on together: both decide what the root selects")
 
 
 MAX_NUM_STACK = 8  # the engine's history ring holds 8 boards (include/azsp.h AzspConfig.num_stack)
@@ -109,6 +132,8 @@ class Engine:
         check_num_stack(cfg.num_stack)
         sym = leaf_symmetry_mode(cfg.leaf_symmetry)
         forced = forced_playouts_k(cfg.forced_playouts)
+        gum = gumbel_params(cfg.gumbel)
+        check_gumbel_alone(cfg.gumbel, cfg.forced_playouts)
         c = AzspConfig()
         c.game = _abi.GAME_GO if cfg.game == "go" else _abi.GAME_GOMOKU
         c.board_size, c.num_games, c.num_parallel, c.num_simulations = cfg.board_size, cfg.num_games, cfg.num_parallel, cfg.num_simulations
@@ -151,9 +176,13 @@ class Engine:
         self._harvest_bufs = None
         if sym != _abi.SYM_OFF:
             self.set_leaf_symmetry(cfg.leaf_symmetry)  # before the first select: the first root evaluation is transformed too
+        self._forced_k, self._gumbel_m = 0.0, 0  # what is on now: the two rules exclude each other
         self.forced_playouts = False  # forced playouts have been on at least once: the target rows exist (target_policies)
         if forced > 0.0:
             self.set_forced_playouts(forced)
+        self.gumbel = False  # the Gumbel root search has been on at least once: the n0 and target rows exist (gumbel_moves, target_policies)
+        if gum[0] > 0:
+            self.set_gumbel(cfg.gumbel)
 
     # -- plumbing ---------------------------------------------------------------------------------
     def _ck(self, rc, what):
@@ -374,12 +403,38 @@ class Engine:
         search did not want; False forces without pruning.  The move, the logs and `read_searches` stay those of the unpruned search.
         Holds for the selections and move ends from now on."""
         kk = forced_playouts_k(k)
+        if kk > 0.0 and self._gumbel_m > 0:
+            raise ValueError("gumbel and forced_playouts cannot be on together: both decide what the root selects")
         self._ck(self.b.dll.azsp_set_forced_playouts(self.h, C.c_double(kk), int(bool(prune_target))), "azsp_set_forced_playouts")
+        self._forced_k = kk
         self.forced_playouts = self.forced_playouts or kk > 0.0
 
+    def set_gumbel(self, gumbel):
+        """Gumbel root search (azsp_set_gumbel; Danihelka et al., ICLR 2022; the reference search has none): None or 0 = off, m or
+        (m, c_visit, c_scale) = the root's actions are sampled without replacement with Gumbel noise, m at most are considered, the
+        simulations are spent on them by sequential halving, and the policy target is softmax(logits + sigma(completed Q)); below the
+        root the search stays PUCT.  Dirichlet noise is not applied; the noise rows of `begin_moves` / `set_injection` carry the Gumbel
+        draws.  The move is a* (`gumbel_moves()`; the actor plays it), the target `target_policies()` and the harvested pi rows; the
+        logs and `read_searches` keep the plain visit policy.  A fast move of the playout cap runs the plain search.  Not together
+        with forced playouts (ValueError).  Holds for the searches that begin from now on."""
+        m, cv, cs = gumbel_params(gumbel)
+        if m > 0 and self._forced_k > 0.0:
+            raise ValueError("gumbel and forced_playouts cannot be on together: both decide what the root selects")
+        self._ck(self.b.dll.azsp_set_gumbel(self.h, m, C.c_double(cv), C.c_double(cs)), "azsp_set_gumbel")
+        self._gumbel_m = m
+        self.gumbel = self.gumbel or m > 0
+
+    def gumbel_moves(self):
+        """int32[G] on the engine's device: a* of every slot's last finished Gumbel root search, -1 before the first and after a fast move
+        (azsp_read_gumbel_moves).  Only once the mode has been enabled.  Nothing is synchronised."""
+        out = torch.empty(self.G, dtype=torch.int32, device=self.device)
+        self._ck(self.b.dll.azsp_read_gumbel_moves(self.h, out.data_ptr(), self._stream()), "azsp_read_gumbel_moves")
+        return out
+
     def target_policies(self):
-        """float64[G, A] on the engine's device: per slot the policy target of its last search that finished with forced playouts on
-        (azsp_read_target_policies; zero rows before the first).  Only once forced playouts have been enabled.  Nothing is synchronised."""
+        """float64[G, A] on the engine's device: per slot the policy target of its last search that finished with forced playouts or the
+        Gumbel root search on (azsp_read_target_policies; zero rows before the first).  Only once one of them has been enabled.  Nothing
+        is synchronised."""
         out = torch.empty((self.G, self.A), dtype=torch.float64, device=self.device)
         self._ck(self.b.dll.azsp_read_target_policies(self.h, out.data_ptr(), self._stream()), "azsp_read_target_policies")
         return out

@@ -107,7 +107,7 @@ class SelfPlayActor:
                  resign_threshold=-1.0, komi=7.5, num_to_win=5, seed=1, rank=0, device="cuda", net_dtype=torch.float32,
                  use_graph=True, training_steps=0, binding=None, root_noise=True, deterministic=False, tiled_features=None, engine_kw=None,
                  use_split_evaluator=True, auto_widen=None, num_stack=8, split_any_board=False, playout_cap=None,
-                 leaf_symmetry=None, forced_playouts=None, prune_policy_target=True):
+                 leaf_symmetry=None, forced_playouts=None, prune_policy_target=True, gumbel=None):
         """net_dtype: precision class of the leaf evaluator.  The default is the REFERENCE'S: fp32 (pipeline.py:91-123 evaluates in fp32,
         no autocast anywhere) -- on the hand-written split-precision kernels (hi + lo f16 pairs, three MFMA products, fp32 accumulation:
         include/azsp.h azsp_conv3x3_split) for 9x9 x {128, 64} and 13x13 Gomoku x 64 networks, on library fp32 convolutions (announced
@@ -134,13 +134,19 @@ class SelfPlayActor:
         forced_playouts: None, or k >= 0 (Engine.set_forced_playouts; KataGo's forced playouts, k = 2 there; the reference has none):
         in every search that is no fast move of the playout cap, a root child in play gets at least sqrt(k P(c) sum N) visits.
         prune_policy_target: the harvested pi rows leave out the forced visits the search did not want (policy-target pruning);
-        False records the plain policy of the forced search.  The move is always chosen from the unpruned policy."""
+        False records the plain policy of the forced search.  The move is always chosen from the unpruned policy.
+        gumbel: None, m or (m, c_visit, c_scale) (Engine.set_gumbel; Gumbel AlphaZero, Danihelka et al. 2022; the reference has none):
+        every search that is no fast move of the playout cap samples m root actions with Gumbel noise instead of adding Dirichlet
+        noise, spends its simulations on them by sequential halving, plays the move a* it ends with (whatever warm-up and
+        `deterministic` say) and records softmax(logits + sigma(completed Q)) as the pi row.  Not together with forced_playouts."""
         from .. import _lib
-        from .engine import check_num_stack, forced_playouts_k, leaf_symmetry_mode
+        from .engine import check_gumbel_alone, check_num_stack, forced_playouts_k, gumbel_params, leaf_symmetry_mode
 
         leaf_symmetry_mode(leaf_symmetry)  # ValueError before anything is built
         self.leaf_symmetry = leaf_symmetry
         self.forced_playouts, self.prune_policy_target = forced_playouts_k(forced_playouts), bool(prune_policy_target)
+        check_gumbel_alone(gumbel, forced_playouts)
+        self.gumbel = gumbel_params(gumbel) if gumbel is not None else None
         self.num_stack = check_num_stack(num_stack)
         check_input_channels(network, self.num_stack)
 
@@ -173,7 +179,7 @@ class SelfPlayActor:
                            else _abi.FEAT_F16_SPLIT if self.split_features else _FEAT_OF[net_dtype]),
             training_steps=training_steps, seed=seed, rank=rank, num_stack=self.num_stack,
             device_index=self.device.index or 0, leaf_symmetry=leaf_symmetry,  # (set before the first root is selected)
-            forced_playouts=forced_playouts)
+            forced_playouts=forced_playouts, gumbel=gumbel)
         for k, v in (engine_kw or {}).items():  # further EngineConfig fields (move logs, max_plies, ...: tests and diagnostics)
             if not hasattr(self.cfg, k):
                 raise TypeError(f"unknown engine option {k}")
@@ -415,14 +421,15 @@ def run_selfplay_actor_loop(seed, rank, network, device, data_queue, env, num_si
                             warm_up_steps, check_resign_after_steps, disable_resign_ratio, save_sgf_dir=None, save_sgf_interval=0,
                             logs_dir=None, load_ckpt=None, log_level="INFO", var_ckpt=None, var_resign_threshold=None,
                             ckpt_event=None, stop_event=None, num_games=4096, net_dtype=torch.float32, harvest_every=64, binding=None,
-                            playout_cap=None, leaf_symmetry=None, forced_playouts=None):
+                            playout_cap=None, leaf_symmetry=None, forced_playouts=None, gumbel=None):
     """Same role and argument list as the reference actor entry point (pipeline.py:166-189), extended by
     `num_games`: one call drives `num_games` games on `device` and puts (game_seq, stats) tuples on
     `data_queue` exactly as `num_games` reference actors would.  `net_dtype` defaults to the reference's evaluator precision (fp32,
     see SelfPlayActor).  `playout_cap`: None or (fast_simulations, full_prob), see SelfPlayActor: the queued game_seq then hold the
     full-search samples only.  `leaf_symmetry`: None, "random" or an op 0..7, see SelfPlayActor: the search's evaluations are made under
     board symmetries, the queued samples stay in the true orientation.  `forced_playouts`: None or k >= 0, see SelfPlayActor: forced
-    playouts at the root, the queued pi rows are the pruned policy targets."""
+    playouts at the root, the queued pi rows are the pruned policy targets.  `gumbel`: None, m or (m, c_visit, c_scale), see
+    SelfPlayActor: Gumbel root search, the queued pi rows are the completed-Q targets."""
     import os
 
     game = "go" if env.has_pass_move else "gomoku"
@@ -438,7 +445,7 @@ def run_selfplay_actor_loop(seed, rank, network, device, data_queue, env, num_si
                           resign_threshold=thr, komi=getattr(env, "komi", 7.5), num_to_win=getattr(env, "num_to_win", 5),
                           seed=seed, rank=rank, device=device, net_dtype=net_dtype, training_steps=training_steps, binding=binding,
                           num_stack=getattr(env, "num_stack", 8), playout_cap=playout_cap, leaf_symmetry=leaf_symmetry,
-                          forced_playouts=forced_playouts)
+                          forced_playouts=forced_playouts, gumbel=gumbel)
     actor.drop_clamped_games = True  # the learner never sees a game that ran on a clamping evaluator (the reference's fp32 has no range)
     writer = None
     if logs_dir:  # per-actor statistics file with the reference's columns (pipeline.py:196, :268-271; logs/go/9x9/actor0.csv)

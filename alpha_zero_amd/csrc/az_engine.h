@@ -35,6 +35,9 @@
 // AzCfg::leaf_sym (azsp_set_leaf_symmetry): 0..7 = that dihedral op for every row, or one of these two
 #define AZ_SYM_OFF (-1)
 #define AZ_SYM_RANDOM (-2)
+// GameRec::root_noisy: 0 = the float32 priors, 1 = rootP holds the float64 priors with Dirichlet noise, AZ_ROOT_GUMBEL = a Gumbel root:
+// rootP holds the base row b(a) = g(a) + log P(a), gum_n0 the child N at search begin, and the root's selection is gumbel_child()
+#define AZ_ROOT_GUMBEL 2
 
 enum { AZS_NEED_ROOT = 0, AZS_SEARCH = 1, AZS_MOVE_DONE = 2, AZS_IDLE = 3, AZS_WAIT_BUF = 4 };
 enum { AZ_ERR_NODES = 1, AZ_ERR_SAMPLE = 4, AZ_ERR_STAGE = 8 };  // bit 2 (tree depth) retired: deep paths walk parent links
@@ -76,6 +79,10 @@ struct AzCfg {
     // A fast move of the playout cap is neither forced nor pruned.
     int prune_target;
     double forced_k;
+    // Gumbel root search (azsp_set_gumbel; gumbel_m = 0: off; include/azsp.h states the rule).  gumbel_m = the most actions considered,
+    // sigma(a) = (gumbel_cv + max N) * gumbel_cs * (completedQ(a) + 1) / 2.  Never on together with forced playouts.
+    int gumbel_m;
+    double gumbel_cv, gumbel_cs;
 };
 
 struct AzMem {
@@ -98,7 +105,8 @@ struct AzMem {
     double* log_pi;          // [G][log_cap][A]
     float* log_childN;       // [G][log_cap][A]
     double* log_q;           // [G][log_cap][4]  root_q, child_q, root_N before search (unused), move
-    double* target_pi;       // [G][A]  policy target of the slot's last finished search (forced playouts: pruned); null until they are first enabled
+    double* target_pi;       // [G][A]  policy target of the slot's last finished search (forced playouts: pruned; Gumbel: pi'); null until one of them is first enabled
+    float* gum_n0;           // [G][AP] Gumbel root search: the root's child N when the slot's search began; null until the mode is first enabled
     uint8_t* leaf_sym;       // [G][P]  the dihedral op the row's features were written under (0 = as they are): select writes, expand reads
     u32* sym_rows;           // [G]     feature rows this slot has written under a leaf symmetry since azsp_create: a counter word of its op stream
     u64* counters;           // [G][AZC_COUNT]  per-game rows (no atomics: 4096 waves hammering 12 shared words cost ~0.6 ms per launch)
@@ -121,6 +129,9 @@ template <int W> struct GameRec {
     double resign_thr;   // var_resign_threshold.value at game start (<= -1: no resignation in this game)
     int train_steps;     // training_steps of the weights in use at game start (pipeline.py:237, :271)
     int sim_budget;      // AZ_SB_*: the slot's own simulations per move (azsp_set_budgets, 0 = the engine's) and the class of the move in progress
+    int gum_rootN0;      // Gumbel root search: root_N when the slot's search began (n_sched = max(1, simulations - this))
+    int gum_m;           // Gumbel root search: m when the slot's search began
+    int gum_move;        // Gumbel root search: a* of the slot's last finished search, -1 = none (no Gumbel search yet, or a fast move)
     int16_t leaf_node[AZ_MAXP];
     uint8_t leaf_depth[AZ_MAXP];
 };
@@ -180,6 +191,9 @@ template <int W, int AP, int HW> struct Scratch {
             // batch so far, -1 = not on for this search; the forced child of the root for the descent that starts now, -1 = none
             float fv[AP];  // (float: the lane's address is the one of the N / W / P rows; a byte row cost the kernel two more VGPRs)
             int teff, fsel;
+            // select, Gumbel root (root_noisy == AZ_ROOT_GUMBEL): fv[a] = v(a) - n0(a), so that n(a) = N(a) + fv[a]; teff = t = sum n(a);
+            // fsel = the considered child for the descent that starts now; gm = m' = min(m, legal actions); gsched = n_sched
+            int gm, gsched;
         };
     };
     StagedRec<AP, HW> root;     // the root's record: staged ONCE per round, kept current in LDS while the P descents update it
@@ -263,19 +277,19 @@ template <class Wv, int N, int GAME> struct Engine {
     // The root visit count that ends this game's search (mcts_v2.py:378 / :568): its own simulations per move -- the slot's value, the
     // playout cap's on a fast move, else the engine's, clamped into [1, sims] because pool and tables are sized for `sims` -- plus P in
     // parallel mode, as azsp_create derives c.budget.
-    AZ_HD int game_budget() const {
+    AZ_HD int game_budget() const { return game_sims() + (c.parallel_mode ? c.P : 0); }
+    AZ_HD int game_sims() const {  // the simulations per move themselves
         const int sb = Wv::uni(gr.sim_budget);
         int s = (sb & AZ_SB_FAST) ? c.cap_fast : (sb & AZ_SB_SIMS_MASK);
         if (s == 0) s = c.sims;
-        s = s < 1 ? 1 : (s > c.sims ? c.sims : s);
-        return s + (c.parallel_mode ? c.P : 0);
+        return s < 1 ? 1 : (s > c.sims ? c.sims : s);
     }
     // Playout cap: the class of the move that starts now, from the game's own counter-based stream (a counter word of its own: the
     // Dirichlet stream uses `| action`, move sampling `| 0xFFF`, the leaf symmetry 0xFFD -- row_symmetry()).  Returns the move's
     // noise_pending.  (first lane only)
     AZ_HD int begin_move_class() {
         int sb = gr.sim_budget & ~AZ_SB_FAST;
-        int noise = c.root_noise;
+        int noise = c.gumbel_m > 0 ? AZ_ROOT_GUMBEL : c.root_noise;  // noise_pending names what is due (apply_noise): 1 = Dirichlet noise, 2 = the Gumbel base row
         if (c.cap_fast > 0 && !c.stop_after_move) {
             u32 r[4];
             Philox::gen(c.seed + (u64)c.rank, (u32)g, (u32)gr.uid, ((u32)gr.ply << 12) | 0xFFEu, 0x2000u, r);
@@ -617,6 +631,105 @@ template <class Wv, int N, int GAME> struct Engine {
         return -1;
     }
 
+    // ---- Gumbel root search (Danihelka et al., ICLR 2022; include/azsp.h azsp_set_gumbel states the rule) ----------------------
+    // The considered-visit sequence cv(t; m', n_sched): sequential halving over m' actions written as "the visit count the next
+    // considered action must have after t root visits of this search".  Wave-uniform integer loop, no table.
+    // Bounded whatever it is handed: m' <= A, n_sched and t within what a 16-bit simulation count allows, and once k has reached 2 -- e
+    // and k no longer change -- the rest of the loop in closed form, so it runs at most L + 1 times.
+    static AZ_HD int considered_visits(int t, int mp, int n_sched) {
+        mp = mp > A ? A : mp;
+        n_sched = n_sched < 1 ? 1 : (n_sched > AZ_SB_SIMS_MASK ? AZ_SB_SIMS_MASK : n_sched);
+        t = t < 0 ? 0 : (t > 2 * AZ_SB_SIMS_MASK ? 2 * AZ_SB_SIMS_MASK : t);
+        if (mp <= 1) return t;
+        int L = 0;
+        while ((1 << L) < mp) ++L;
+        int k = mp, base = 0;
+        for (;;) {
+            int e = n_sched / (L * k);
+            e = e < 1 ? 1 : e;
+            if (t < e * k) return base + t / k;
+            if (k == 2) return base + e * (t / (2 * e)) + (t % (2 * e)) / 2;
+            t -= e * k;
+            base += e;
+            k = k / 2 < 2 ? 2 : k / 2;
+        }
+    }
+    // completed Q and sigma of a root whose rows are rn / rw / rp (the staged record in select, the node's rows at the end of a move),
+    // with the root's own W and N: sig = (c_visit + max_legal N) * c_scale, vmix = the value an unvisited child is completed with.
+    // sigma(a) = sig * ((cq(a) + 1) / 2) with cq(a) = -W(a) / N(a) for a visited child, else vmix: gumbel_sigma().
+    AZ_HD void gumbel_stats(const S& s, const float* rn, const float* rw, const float* rp, double root_w, int root_n, double& sig, double& vmix) {
+        const int top = Wv::argmax_first([&](int lane, double& best, int& bi) {
+            for (int a = lane; a < A; a += AZ_WAVE)
+                if (action_legal(s, a) && (bi < 0 || (double)rn[a] > best)) {
+                    best = (double)rn[a];
+                    bi = a;
+                }
+        });
+        const double max_n = (top >= 0 && top < A) ? (double)rn[top] : 0.0;
+        const double T = Wv::sum_f64([&](int lane) -> double {
+            double part = 0.0;
+            for (int a = lane; a < A; a += AZ_WAVE) part += action_legal(s, a) ? (double)rn[a] : 0.0;
+            return part;
+        });
+        const double sp = Wv::sum_f64([&](int lane) -> double {
+            double part = 0.0;
+            for (int a = lane; a < A; a += AZ_WAVE) part += (action_legal(s, a) && rn[a] > 0.0f) ? (double)rp[a] : 0.0;
+            return part;
+        });
+        const double spq = Wv::sum_f64([&](int lane) -> double {
+            double part = 0.0;
+            for (int a = lane; a < A; a += AZ_WAVE)
+                part += (action_legal(s, a) && rn[a] > 0.0f) ? (double)rp[a] * (-((double)rw[a] / (double)rn[a])) : 0.0;
+            return part;
+        });
+        const double v_root = root_n > 0 ? root_w / (double)root_n : 0.0;
+        vmix = sp > 0.0 ? (v_root + T * (spq / sp)) / (1.0 + T) : v_root;
+        sig = (c.gumbel_cv + max_n) * c.gumbel_cs;
+    }
+    static AZ_HD double gumbel_sigma(float n, float w, double sig, double vmix) {
+        const double cq = n > 0.0f ? -((double)w / (double)n) : vmix;
+        return sig * ((cq + 1.0) / 2.0);
+    }
+    // The root's choice for the descent that starts now (select(), where forced_child runs; its state is in LDS for the same reason):
+    // among the legal actions with n(a) == cv(t) the largest b(a) + sigma(a), lowest index on ties; if no action has that count, among
+    // those with the smallest n(a).  n(a) = N(a) + sc.fv[a], b = sc.rP64.
+    AZ_HD int gumbel_child(const SR& r) {
+        const S& s = hdr_of(r).st;
+        double sig, vmix;
+        gumbel_stats(s, r.rN, r.rW, r.rP, hs_rootW, hs_rootN, sig, vmix);
+        float want = (float)considered_visits(Wv::uni(sc.teff), Wv::uni(sc.gm), Wv::uni(sc.gsched));
+        u64 hit = 0;
+        for (int j = 0; j < EPL; ++j)
+            hit |= Wv::ballot([&](int lane) -> bool {
+                const int a = lane + 64 * j;
+                return a < A && action_legal(s, a) && r.rN[a] + sc.fv[a] == want;
+            });
+        if (!hit) {
+            const int low = Wv::argmax_first([&](int lane, double& best, int& bi) {
+                for (int a = lane; a < A; a += AZ_WAVE) {
+                    const double neg = -(double)(r.rN[a] + sc.fv[a]);
+                    if (action_legal(s, a) && (bi < 0 || neg > best)) {
+                        best = neg;
+                        bi = a;
+                    }
+                }
+            });
+            if (low < 0 || low >= A) return -1;
+            want = Wv::uni(r.rN[low] + sc.fv[low]);
+        }
+        const int mv = Wv::argmax_first([&](int lane, double& best, int& bi) {
+            for (int a = lane; a < A; a += AZ_WAVE) {
+                if (!action_legal(s, a) || r.rN[a] + sc.fv[a] != want) continue;
+                const double sco = sc.rP64[a] + gumbel_sigma(r.rN[a], r.rW[a], sig, vmix);
+                if (bi < 0 || sco > best) {
+                    best = sco;
+                    bi = a;
+                }
+            }
+        });
+        return mv < A ? mv : -1;
+    }
+
     // One descent from the root.  Returns 0 = leaf reached (unexpanded, non-terminal), 1 = terminal.
     // On return `leaf_state` holds the leaf's position (used for the observation planes).
     AZ_HD int descend(int& node_out, int& depth_out, S& leaf_state) {
@@ -878,7 +991,9 @@ template <class Wv, int N, int GAME> struct Engine {
     }
 
     // ---- select phase -------------------------------------------------------------------------
-    AZ_HD void select(void* feat, unsigned char* valid) {
+    // GUM: the Gumbel root rule is compiled in.  The batched actor's select kernel has no register to spare (forced_child), so the rule
+    // lives in an instantiation of its own (OpSelectGumbel), launched once the mode has been enabled; select<false> is the kernel it was.
+    template <bool GUM> AZ_HD void select(void* feat, unsigned char* valid) {
         unsigned char* vrow = valid + (size_t)g * c.P;
         if (Wv::first()) {
             sc.free_base = -(1 << 30);  // no staged free-stack window yet
@@ -938,7 +1053,33 @@ template <class Wv, int N, int GAME> struct Engine {
                 Wv::sync();
                 stage_node(hs_root, sc.root, hs_noisy != 0);
             }
-            if (c.forced_k > 0.0 && !(Wv::uni(gr.sim_budget) & AZ_SB_FAST)) {  // forced playouts: T_eff and v(a) of this select phase
+            // A Gumbel root is tested first: a search that began under that rule keeps it, whatever has been switched since, and
+            // gumbel_child() reads nothing but what this branch writes
+            if (GUM && hs_noisy == AZ_ROOT_GUMBEL) {  // Gumbel root: t, v(a) - n0(a), m' and n_sched of this select phase
+                const float* n0 = m.gum_n0 + (size_t)g * AP;
+                const S& rs = hdr_of(sc.root).st;
+                const int sum = Wv::sum_i32([&](int lane) -> int {
+                    int part = 0;
+                    for (int a = lane; a < AP; a += AZ_WAVE) {
+                        const float was = n0[a];
+                        part += (int)sc.root.rN[a] - (int)was;
+                        sc.fv[a] = -was;
+                    }
+                    return part;
+                });
+                const int legal = Wv::sum_i32([&](int lane) -> int {
+                    int part = 0;
+                    for (int a = lane; a < A; a += AZ_WAVE) part += action_legal(rs, a) ? 1 : 0;
+                    return part;
+                });
+                const int sched = game_sims() - Wv::uni(gr.gum_rootN0), gm = Wv::uni(gr.gum_m);
+                if (Wv::first()) {
+                    sc.teff = sum;
+                    sc.gm = legal < gm || gm < 1 ? legal : gm;
+                    sc.gsched = sched < 1 ? 1 : sched;
+                }
+                Wv::sync();
+            } else if (c.forced_k > 0.0 && !(Wv::uni(gr.sim_budget) & AZ_SB_FAST)) {  // forced playouts: T_eff and v(a) of this select phase
                 const int sum = Wv::sum_i32([&](int lane) -> int {
                     int part = 0;
                     for (int a = lane; a < AP; a += AZ_WAVE) {
@@ -957,8 +1098,8 @@ template <class Wv, int N, int GAME> struct Engine {
                 attempts++;
                 int node, depth;
                 S leaf;
-                if (Wv::uni(sc.teff) >= 0) {  // (wave-uniform) forced playouts
-                    const int f = forced_child(sc.root);
+                if (Wv::uni(sc.teff) >= 0) {  // (wave-uniform) forced playouts, or a Gumbel root
+                    const int f = (GUM && hs_noisy == AZ_ROOT_GUMBEL) ? gumbel_child(sc.root) : forced_child(sc.root);
                     if (Wv::first()) sc.fsel = f;
                     Wv::sync();
                 }
@@ -1082,7 +1223,52 @@ template <class Wv, int N, int GAME> struct Engine {
             }
         }
     }
+    // Gumbel(0, 1) draw of (game uid, ply, action) from the slot's counter-based stream: g = -log(-log u), u = (k + 1/2) 2^-52 with k
+    // the top 52 bits of a Philox word pair, so 0 < u < 1 exactly.  Counter word 0x4000: the Dirichlet stream of the same (ply, action)
+    // uses 0, 1, 2, ...
+    AZ_HD double gumbel_draw(u64 key, u32 uid, int ply, int a) const {
+        u32 r[4];
+        Philox::gen(key, (u32)g, uid, ((u32)ply << 12) | (u32)a, 0x4000u, r);
+        const double u = ((double)((((u64)r[0] << 32) | r[1]) >> 12) + 0.5) * (1.0 / 4503599627370496.0);
+        return -log(-log(u));
+    }
+    // The start of a Gumbel root search, where apply_noise() adds the Dirichlet noise otherwise: the base row
+    // b(a) = g(a) + log(max((double)P(a), 1e-45)) into the slot's float64 root row, and the snapshot n0 / root_N of the kept visits.
+    // g(a) is the injected row (azsp_set_injection, azsp_begin_move[s]) or the slot's own draw.  The priors stay as they are.
+    AZ_HD void apply_gumbel() {
+        const int root = gr.root;
+        const float* rp = rowP(root);
+        const float* rn = rowN(root);
+        double* rp64 = rootP();
+        float* n0 = m.gum_n0 + (size_t)g * AP;
+        const double* inj = c.inject ? m.inj_noise + ((size_t)g * c.inj_moves + (gr.ply < c.inj_moves ? gr.ply : c.inj_moves - 1)) * A : nullptr;
+        const u64 key = c.seed + (u64)c.rank;
+        const u32 uid = (u32)gr.uid;
+        const int ply = gr.ply;
+        Wv::lanes([&](int lane) {
+            for (int a = lane; a < AP; a += AZ_WAVE) {
+                double v = 0.0;
+                if (a < A) {
+                    const double p = (double)rp[a];
+                    v = (inj ? inj[a] : gumbel_draw(key, uid, ply, a)) + log(p > 1e-45 ? p : 1e-45);
+                }
+                rp64[a] = v;
+                n0[a] = rn[a];
+            }
+        });
+        if (Wv::first()) {
+            gr.root_noisy = AZ_ROOT_GUMBEL;
+            gr.noise_pending = 0;
+            gr.gum_rootN0 = gr.root_N;
+            gr.gum_m = c.gumbel_m;  // (0 if the mode was switched off since the move was classed: every legal action is considered)
+        }
+        Wv::sync();
+    }
     AZ_HD void apply_noise() {
+        if (Wv::uni(gr.noise_pending) == AZ_ROOT_GUMBEL) {  // what the move was classed as when it began, not what the mode is now
+            apply_gumbel();
+            return;
+        }
         const int root = gr.root;
         const S& s = hdr(root).st;
         const float* rp = rowP(root);
@@ -1128,7 +1314,12 @@ template <class Wv, int N, int GAME> struct Engine {
         const u64 key = c.seed + (u64)c.rank;
         const u32 uid = (u32)Wv::uni((int)gr.uid);
         for (int ply = 0; ply < plies; ++ply) {
-            if (noise) {
+            if (noise && c.gumbel_m > 0) {  // Gumbel root search on: the rows are the g(a) apply_gumbel draws
+                double* row = noise + ((size_t)g * plies + ply) * A;
+                Wv::lanes([&](int lane) {
+                    for (int a = lane; a < A; a += AZ_WAVE) row[a] = gumbel_draw(key, uid, ply, a);
+                });
+            } else if (noise) {
                 double* row = noise + ((size_t)g * plies + ply) * A;
                 const double tot = Wv::sum_f64([&](int lane) -> double {
                     double acc = 0.0;
@@ -1317,6 +1508,96 @@ template <class Wv, int N, int GAME> struct Engine {
         Wv::lanes([&](int lane) {
             for (int a = lane; a < A; a += AZ_WAVE) tp[a] = sc.pi[a];
         });
+        Wv::sync();
+    }
+
+    // End of a Gumbel root search (no virtual loss outstanding): a* = the largest b(a) + sigma(a) among the legal actions with the largest
+    // N(a) - n0(a) -- and N(a) > 0 where the search made no simulation and a visited child exists --, lowest index on ties, into gr.gum_move; pi'(a) = softmax over the legal actions of log(max(P, 1e-45)) + sigma(a),
+    // maximum subtracted first, float64, into sc.pi -- which record_sample stages -- and the slot's target_pi row.  The logs keep the
+    // plain visit policy search_policy wrote.  Returns a*.  (sc.cdf is free: no move is sampled in this mode)
+    AZ_HD int gumbel_target() {
+        const int root = gr.root;
+        const S& s = hdr(root).st;
+        const float* rn = rowN(root);
+        const float* rw = rowW(root);
+        const float* rp = rowP(root);
+        const double* b = rootP();
+        const float* n0 = m.gum_n0 + (size_t)g * AP;
+        double sig, vmix;
+        gumbel_stats(s, rn, rw, rp, Wv::uni(gr.root_W), Wv::uni(gr.root_N), sig, vmix);
+        const int most = Wv::argmax_first([&](int lane, double& best, int& bi) {
+            for (int a = lane; a < A; a += AZ_WAVE)
+                if (action_legal(s, a) && (bi < 0 || (double)(rn[a] - n0[a]) > best)) {
+                    best = (double)(rn[a] - n0[a]);
+                    bi = a;
+                }
+        });
+        int astar = -1;
+        if (most >= 0 && most < A) {
+            const float want = Wv::uni(rn[most] - n0[most]);
+            // a search that made no simulation (the kept sub-tree already held the budget): among the visited children, if there is
+            // one, so that the move has a child node as a sampled move always has
+            bool seen = false;
+            if (want == 0.0f)
+                for (int j = 0; j < EPL; ++j)
+                    seen = seen || Wv::ballot([&](int lane) -> bool {
+                               const int a = lane + 64 * j;
+                               return a < A && action_legal(s, a) && rn[a] > 0.0f;
+                           }) != 0;
+            astar = Wv::argmax_first([&](int lane, double& best, int& bi) {
+                for (int a = lane; a < A; a += AZ_WAVE) {
+                    if (!action_legal(s, a) || rn[a] - n0[a] != want || (seen && !(rn[a] > 0.0f))) continue;
+                    const double sco = b[a] + gumbel_sigma(rn[a], rw[a], sig, vmix);
+                    if (bi < 0 || sco > best) {
+                        best = sco;
+                        bi = a;
+                    }
+                }
+            });
+        }
+        const int top = Wv::argmax_first([&](int lane, double& best, int& bi) {
+            for (int a = lane; a < A; a += AZ_WAVE) {
+                if (!action_legal(s, a)) continue;
+                const double p = (double)rp[a];
+                const double logit = log(p > 1e-45 ? p : 1e-45) + gumbel_sigma(rn[a], rw[a], sig, vmix);
+                sc.cdf[a] = logit;
+                if (bi < 0 || logit > best) {
+                    best = logit;
+                    bi = a;
+                }
+            }
+        });
+        Wv::sync();
+        const double mx = (top >= 0 && top < A) ? sc.cdf[top] : 0.0;
+        const double sum = Wv::sum_f64([&](int lane) -> double {
+            double part = 0.0;
+            for (int a = lane; a < A; a += AZ_WAVE) {
+                const double e = action_legal(s, a) ? exp(sc.cdf[a] - mx) : 0.0;
+                sc.pi[a] = e;
+                part += e;
+            }
+            return part;
+        });
+        Wv::sync();
+        double* tp = m.target_pi + (size_t)g * A;
+        Wv::lanes([&](int lane) {
+            for (int a = lane; a < A; a += AZ_WAVE) {
+                const double v = sum > 0.0 ? sc.pi[a] / sum : sc.pi[a];
+                sc.pi[a] = v;
+                tp[a] = v;
+            }
+        });
+        if (Wv::first()) gr.gum_move = astar;
+        Wv::sync();
+        return astar;
+    }
+    // Gumbel mode on, but this search ran the plain rule (a fast move of the playout cap): the target row is the plain policy, no a*.
+    AZ_HD void plain_target() {
+        double* tp = m.target_pi + (size_t)g * A;
+        Wv::lanes([&](int lane) {
+            for (int a = lane; a < A; a += AZ_WAVE) tp[a] = sc.pi[a];
+        });
+        if (Wv::first()) gr.gum_move = -1;
         Wv::sync();
     }
 
@@ -1530,8 +1811,11 @@ template <class Wv, int N, int GAME> struct Engine {
                 for (int a = lane; a < A; a += AZ_WAVE) ln[a] = rn[a];
             });
         }
+        const bool gumbel = Wv::uni(gr.root_noisy) == AZ_ROOT_GUMBEL;  // this search ran the Gumbel root rule
         if (c.stop_after_move) {
-            if (c.forced_k > 0.0) make_target(warm);
+            if (gumbel) gumbel_target();
+            else if (c.forced_k > 0.0) make_target(warm);
+            else if (c.gumbel_m > 0) plain_target();
             if (Wv::first()) {
                 gr.out_root_q = root_q();
                 gr.status = AZS_MOVE_DONE;
@@ -1540,7 +1824,9 @@ template <class Wv, int N, int GAME> struct Engine {
             return;
         }
         int mv;
-        if (c.deterministic) {
+        if (gumbel) {
+            mv = gumbel_target();  // a* is the move, whatever warm-up and `deterministic` say; the sample records pi'
+        } else if (c.deterministic) {
             mv = Wv::argmax_first([&](int lane, double& best, int& bi) {  // np.argmax(child_N), unmasked (:429)
                 for (int a = lane; a < A; a += AZ_WAVE)
                     if (bi < 0 || (double)rn[a] > best) {
@@ -1551,7 +1837,8 @@ template <class Wv, int N, int GAME> struct Engine {
         } else {
             mv = sample_move(warm);
         }
-        if (c.forced_k > 0.0) make_target(warm);  // the move came from the unpruned policy; the sample records the target
+        if (!gumbel && c.forced_k > 0.0) make_target(warm);  // the move came from the unpruned policy; the sample records the target
+        else if (!gumbel && c.gumbel_m > 0) plain_target();
         commit_actor(mv);
     }
 

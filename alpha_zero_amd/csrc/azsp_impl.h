@@ -31,6 +31,7 @@ struct OpReset {
             e.gr.cur_buf = 0;
             e.gr.noise_ready = 0;
             e.gr.warm_override = -1;
+            e.gr.gum_move = -1;
             int* sh = e.m.stg_hdr + (size_t)e.g * 2 * SH_COUNT;
             sh[SH_STATE] = AZB_FREE;
             sh[SH_COUNT + SH_STATE] = AZB_FREE;
@@ -73,7 +74,17 @@ struct OpSelect {
     void* feat;
     unsigned char* valid;
     template <class E> AZ_HD void operator()(E& e) const {
-        e.select(feat, valid);
+        e.template select<false>(feat, valid);
+        e.cnt[AZC_ROUNDS]++;
+        e.flush_counters();
+    }
+};
+// OpSelect with the Gumbel root rule compiled in (azsp_set_gumbel): what the select entry points launch once the mode has been enabled
+struct OpSelectGumbel {
+    void* feat;
+    unsigned char* valid;
+    template <class E> AZ_HD void operator()(E& e) const {
+        e.template select<true>(feat, valid);
         e.cnt[AZC_ROUNDS]++;
         e.flush_counters();
     }
@@ -142,7 +153,7 @@ struct OpDropinStep {
             e.endmove_phase();
             E::Wave::sync();
         }
-        e.select(feat, valid);
+        e.template select<true>(feat, valid);
         e.cnt[AZC_ROUNDS]++;
         e.flush_counters();
         E::Wave::sync();
@@ -183,6 +194,13 @@ struct OpReadTargets {
         E::Wave::lanes([&](int lane) {
             for (int a = lane; a < A; a += AZ_WAVE) out[(size_t)e.g * A + a] = src[a];
         });
+    }
+};
+// azsp_read_gumbel_moves: a* of the slot's last finished Gumbel root search (-1 = none yet)
+struct OpReadGumbelMoves {
+    int* out;  // [G]
+    template <class E> AZ_HD void operator()(E& e) const {
+        if (E::Wave::first()) out[e.g] = e.gr.gum_move;
     }
 };
 struct OpRngProbe {
@@ -1099,12 +1117,23 @@ static int az_select_launched(AzHandle* h, int rc, int g0, int g1) {
     if (rc == AZSP_OK && h->cfg.leaf_sym == AZSP_SYM_OFF && g0 == 0 && g1 == h->cfg.G) h->cfg.sym_live = 0;
     return rc;
 }
+// The select launch over the games [g0, g1): the kernel with the Gumbel root rule once the mode has been enabled (a search that began
+// under it may still be in flight after it was turned off), else the plain one.  An engine that has enabled the mode once pays for
+// the larger kernel (9x9: three waves per SIMD instead of four) for the rest of its life, also with m = 0 again: whether a slot still
+// has a Gumbel root is known on the device only, and an actor is built with the mode on or off, not switched.
+static int az_select(AzHandle* h, void* feat, uint8_t* valid, void* stream, int g0, int g1) {
+    if (h->mem.gum_n0) {
+        OpSelectGumbel op = {feat, valid};
+        return az_select_launched(h, az_run(h, op, stream, g0, g1), g0, g1);
+    }
+    OpSelect op = {feat, valid};
+    return az_select_launched(h, az_run(h, op, stream, g0, g1), g0, g1);
+}
 
 int azsp_select(void* e, void* feat, uint8_t* valid, void* stream) {
     AzHandle* h = (AzHandle*)e;
     if (!h || !feat || !valid) return AZSP_EINVAL;
-    OpSelect op = {feat, valid};
-    return az_select_launched(h, az_run(h, op, stream), 0, h->cfg.G);
+    return az_select(h, feat, valid, stream, 0, h->cfg.G);
 }
 
 int azsp_expand_backup(void* e, const float* priors, const float* values, void* stream) {
@@ -1121,8 +1150,7 @@ static int az_range_ok(AzHandle* h, int32_t g0, int32_t g1) { return h && g0 >= 
 int azsp_select_range(void* e, void* feat, uint8_t* valid, int32_t g0, int32_t g1, void* stream) {
     AzHandle* h = (AzHandle*)e;
     if (!h || !feat || !valid || !az_range_ok(h, g0, g1)) return AZSP_EINVAL;
-    OpSelect op = {feat, valid};
-    return az_select_launched(h, az_run(h, op, stream, g0, g1), g0, g1);
+    return az_select(h, feat, valid, stream, g0, g1);
 }
 
 int azsp_expand_backup_range(void* e, const float* priors, const float* values, int32_t g0, int32_t g1, void* stream) {
@@ -1327,6 +1355,7 @@ int azsp_leaf_symmetries(void* e, uint8_t* ops_dev, void* stream) {
 int azsp_set_forced_playouts(void* e, double k, int32_t prune_target) {
     AzHandle* h = (AzHandle*)e;
     if (!h || !(k >= 0.0) || !(k <= 1.7976931348623157e308)) return AZSP_EINVAL;  // negative, NaN, infinite
+    if (k > 0.0 && h->cfg.gumbel_m > 0) return AZSP_EINVAL;  // not next to the Gumbel root search: both rules own the root's choice
     if (k > 0.0 && !h->mem.target_pi) {  // the first enabling call allocates the target rows: never a launch path
         if (azb::set_device(h->pub.device) != 0) return AZSP_EDEVICE;  // the engine's device, as azsp_create selects it, whatever the calling thread's is
         h->mem.target_pi = az_new<double>(h, (size_t)h->cfg.G * h->A);  // (zero-initialised, like every engine allocation)
@@ -1341,6 +1370,30 @@ int azsp_read_target_policies(void* e, double* pi_dev, void* stream) {
     AzHandle* h = (AzHandle*)e;
     if (!h || !pi_dev || !h->mem.target_pi) return AZSP_EINVAL;  // no rows before forced playouts were first enabled
     OpReadTargets op = {pi_dev};
+    return az_run(h, op, stream);
+}
+
+int azsp_set_gumbel(void* e, int32_t m, double c_visit, double c_scale) {
+    AzHandle* h = (AzHandle*)e;
+    if (!h || m < 0 || !(c_visit >= 0.0) || !(c_visit <= 1.7976931348623157e308) || !(c_scale >= 0.0) || !(c_scale <= 1.7976931348623157e308))
+        return AZSP_EINVAL;  // negative, NaN, infinite
+    if (m > 0 && h->cfg.forced_k > 0.0) return AZSP_EINVAL;  // not next to forced playouts: both rules own the root's choice
+    if (m > 0 && (!h->mem.target_pi || !h->mem.gum_n0)) {  // the first enabling call allocates the rows: never a launch path
+        if (azb::set_device(h->pub.device) != 0) return AZSP_EDEVICE;  // the engine's device, as azsp_create selects it
+        if (!h->mem.target_pi) h->mem.target_pi = az_new<double>(h, (size_t)h->cfg.G * h->A);  // (forced playouts may have made them)
+        if (!h->mem.gum_n0) h->mem.gum_n0 = az_new<float>(h, (size_t)h->cfg.G * h->AP);
+        if (!h->mem.target_pi || !h->mem.gum_n0) return AZSP_ENOMEM;
+    }
+    h->cfg.gumbel_m = m;  // AzCfg travels by value with every launch: the searches whose root row is formed after this call
+    h->cfg.gumbel_cv = c_visit;
+    h->cfg.gumbel_cs = c_scale;
+    return AZSP_OK;
+}
+
+int azsp_read_gumbel_moves(void* e, int32_t* move_dev, void* stream) {
+    AzHandle* h = (AzHandle*)e;
+    if (!h || !move_dev || !h->mem.gum_n0) return AZSP_EINVAL;  // never enabled
+    OpReadGumbelMoves op = {move_dev};
     return az_run(h, op, stream);
 }
 

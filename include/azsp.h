@@ -40,6 +40,9 @@
  *                                     caller which one each feature row was written under
  *   azsp_set_forced_playouts          no counterpart in the reference: opt-in.  Forced playouts at the root with policy-target pruning
  *                                     (KataGo, Wu 2019, 3.2); azsp_read_target_policies hands a drop-in caller the pruned targets
+ *   azsp_set_gumbel                   no counterpart in the reference: opt-in.  Gumbel root search (Danihelka et al. 2022): sequential
+ *                                     halving at the root and the completed-Q policy target; azsp_read_gumbel_moves hands a drop-in
+ *                                     caller the move
  *   azsp_replay_gather                UniformReplay.sample + batch tensors + random transformation (core/replay.py:72-83,
  *                                      core/pipeline.py:636-643)
  *   azsp_dihedral                     apply_horizontal_flip / apply_vertical_flip / apply_rotation
@@ -420,6 +423,48 @@ int azsp_set_forced_playouts(void* engine, double k, int32_t prune_target);
  * it equals the plain policy.  AZSP_EINVAL before forced playouts were enabled for the first time (the rows are allocated by that
  * call, never by a launch).  Does not synchronise. */
 int azsp_read_target_policies(void* engine, double* pi_dev, void* stream);
+
+/* Gumbel root search: sequential halving over Gumbel-sampled root actions and a completed-Q policy target (Danihelka et al., ICLR 2022,
+ * "Policy improvement by planning with Gumbel"; no counterpart in the reference search: opt-in, off by default).  Below the root the
+ * search stays PUCT, unchanged.  m = the most root actions considered (0 = off; < 0 is AZSP_EINVAL), c_visit and c_scale finite and
+ * >= 0 (the paper uses 50 and 1.0), else AZSP_EINVAL.  Valid in actor and drop-in mode.  m holds for the moves that begin after the
+ * call: a move is classed when its root is ready (first evaluated, or kept by a commit), and it keeps its class and its m -- Gumbel or
+ * plain, with or without Dirichlet noise -- until it ends, whatever is set meanwhile (AZSP_STC_NOISE_PENDING reads 2 while a Gumbel base
+ * row is due, 1 while Dirichlet noise is); c_visit and c_scale are read when they are used.  AZSP_EINVAL while forced playouts are on, and azsp_set_forced_playouts(k > 0) is AZSP_EINVAL while this is on.
+ *   Quantities at the root of slot g.  n0(a) = N(a) of the root's children when the search begins (non-zero only with reuse_tree);
+ *   n(a) = N(a) - n0(a) + v(a), v(a) = the leaves of the current batch whose path starts with a; t = sum_a n(a);
+ *   n_sched = max(1, S - rootN_begin), S = the slot's simulations for this move, rootN_begin = the root's visit count when the search
+ *   begins; m' = min(m, number of legal actions) -- pass is legal wherever the selection admits it.
+ *   Considered-visit sequence cv(t; m', n_sched), integer arithmetic, t unbounded.  If m' <= 1: t.  Else L = ceil(log2 m'), k = m',
+ *   base = 0, and repeat: e = max(1, n_sched div (L k)); if t < e k return base + t div k; else t -= e k, base += e,
+ *   k = max(2, k div 2).
+ *   Base row.  b(a) = g(a) + log(max((double)P(a), 1e-45)): g(a) = the slot's Gumbel(0, 1) draw for this search, P(a) = the root's
+ *   float32 prior.  Formed once per search where the Dirichlet noise is added otherwise, which is not applied in this mode (root_noise
+ *   is ignored).  g(a) = -log(-log u) from the engine's counter-based stream; with injection (azsp_set_injection) the `noise` table
+ *   carries g(a) instead of Dirichlet vectors, and in drop-in mode the noise row of azsp_begin_move[s] does (a row never handed over
+ *   reads as it was left: zero at first, which makes the search the deterministic one on the priors).
+ *   Values, float64, evaluated as written.  q(a) = -W(a) / N(a) from the root's row as it stands (kept visits and virtual losses
+ *   included); T = sum_legal N(a); v_root = root_W / root_N; v_mix = (v_root + T * (sum_{N(a)>0} P(a) q(a) / sum_{N(a)>0} P(a))) / (1 + T),
+ *   v_root when no child is visited (or their priors sum to 0); cq(a) = q(a) if N(a) > 0 else v_mix;
+ *   sigma(a) = ((c_visit + max_legal N) * c_scale) * ((cq(a) + 1) / 2); score(a) = b(a) + sigma(a).  The two prior-weighted sums are
+ *   added in no fixed order: scores are defined up to that rounding.
+ *   Root selection, in front of every descent.  Among the legal actions with n(a) == cv(t) the largest score, ties to the lowest
+ *   index; if no action has that count, the largest score among the legal actions with the smallest n(a).
+ *   End of the move.  a* = the largest score among the legal actions with the largest N(a) - n0(a), ties to the lowest index; in a
+ *   search that made no simulation (a kept sub-tree that already holds the budget: every N(a) - n0(a) is 0) only children with
+ *   N(a) > 0 are candidates if there is one, so that the move has a child node, as a sampled move always has.  In actor
+ *   mode it is the move, whatever warm_up_steps and `deterministic` say; azsp_read_gumbel_moves hands it to a drop-in caller.
+ *   pi'(a) = softmax over the legal a of log(max(P(a), 1e-45)) + sigma(a), the maximum subtracted first, 0 for illegal a.
+ * What uses which: pi' is the slot's target row (azsp_read_target_policies) and the pi row staged for the sample; the move log,
+ * azsp_get_search and azsp_read_searches keep the plain visit policy, child N and Q.  A fast move of the playout cap runs the plain
+ * search: its target row is the plain policy and it has no a* (-1).  With m = 0 nothing of this is evaluated and every output is what it
+ * is without this call.  While m > 0 the noise rows of azsp_rng_probe are the g(a) the searches draw.  The first call with m > 0
+ * allocates the n0 rows, and the target rows unless forced playouts already have, on the engine's device and leaves it selected.
+ * The effect on playing strength is a training experiment; it has not been measured. */
+int azsp_set_gumbel(void* engine, int32_t m, double c_visit, double c_scale);
+/* move_dev int32[G]: a* of each slot's most recent finished Gumbel root search, -1 before the first and after a fast move -- the move
+ * a drop-in caller commits.  AZSP_EINVAL before the mode was enabled for the first time.  Does not synchronise. */
+int azsp_read_gumbel_moves(void* engine, int32_t* move_dev, void* stream);
 
 /* counters_host uint64[16]: simulations, best_child calls, backup edges, leaves, duplicate leaves, terminal hits,
  * moves, games, root evaluations, nodes created, game-rounds, buffer stalls, speculative record prefetches of the select phase and
