@@ -17,17 +17,15 @@ import torch
 
 from .. import _abi
 from ..envs.base import BoardGameEnv
-from .engine import Engine, EngineConfig, check_gumbel_alone, forced_playouts_k, gumbel_params
+from .engine import Engine, EngineConfig, SearchOptions
 
 
 def dropin_engine(game, board_size, num_games, num_simulations, num_parallel, c_puct_base, c_puct_init, root_noise, komi=7.5, max_steps=0,
                   num_to_win=5, num_stack=8, binding=None, device=None, leaf_symmetry=None, forced_playouts=None, gumbel=None):
     """The engine of a drop-in search, `uct_search`'s with one game and a BatchSearch's with `capacity`: it stops after every move
     (`stop_after_move`), hands out int8 observation planes and logs no moves.  Without a `binding` it runs the product library on the GPU.
-    leaf_symmetry: EngineConfig.leaf_symmetry (None = off).  forced_playouts: EngineConfig.forced_playouts (None = off).
-    gumbel: EngineConfig.gumbel (None = off)."""
-    forced_playouts_k(forced_playouts)  # ValueError before anything is built
-    check_gumbel_alone(gumbel, forced_playouts)
+    leaf_symmetry, forced_playouts, gumbel: SearchOptions.of."""
+    SearchOptions.of(leaf_symmetry, forced_playouts, gumbel=gumbel)  # ValueError before anything is built
     if binding is None:
         from .. import _lib
 
@@ -231,20 +229,16 @@ class BatchSearch:
     def __init__(self, game, board_size, capacity, num_simulations, num_parallel=1, c_puct_base=19652.0, c_puct_init=1.25, root_noise=False,
                  komi=7.5, max_steps=0, num_to_win=5, num_stack=8, binding=None, device=None, leaf_symmetry=None, forced_playouts=None,
                  gumbel=None):
-        """gumbel: None, m or (m, c_visit, c_scale) (Engine.set_gumbel; the reference search has none): Gumbel root search; the move to
-        commit is `results().gumbel_move`, the sample to record `results().target_pi`; `search(noise=...)` takes the Gumbel(0, 1) rows
-        (None: drawn here with np.random.gumbel) and root_noise is ignored.  Not together with forced_playouts.
-        forced_playouts: None or k >= 0 (Engine.set_forced_playouts; the reference search has none): forced playouts at the root; the
-        move is still to be chosen from `results().pi`, the sample to record is `results().target_pi` (None when off).
-        leaf_symmetry: None, "random" or an op 0..7 (Engine.set_leaf_symmetry; the reference search has none): `eval_func` -- host
-        callback or resident evaluator -- is handed every leaf position under that board symmetry ("random": one drawn per feature row)
-        and the engine maps its priors back; pi, child_N and Q are in the true orientation."""
+        """leaf_symmetry, forced_playouts, gumbel: SearchOptions.of.  What they mean here: with gumbel the move to commit is
+        `results().gumbel_move` and the sample to record `results().target_pi`; `search(noise=...)` takes the Gumbel(0, 1) rows (None:
+        drawn here with np.random.gumbel) and root_noise is ignored.  With forced_playouts the move is still to be chosen from
+        `results().pi`, the sample to record is `results().target_pi` (None when both are off).  Under leaf_symmetry `eval_func` --
+        host callback or resident evaluator -- is handed every leaf position under that board symmetry."""
+        opt = SearchOptions.of(leaf_symmetry, forced_playouts, gumbel=gumbel)
         if capacity < 1:
             raise ValueError(f"capacity must be at least 1, got {capacity}")
         check_num_simulations(num_simulations)
-        self.forced_playouts = forced_playouts_k(forced_playouts) > 0.0
-        check_gumbel_alone(gumbel, forced_playouts)
-        self.gumbel = gumbel_params(gumbel)[0] > 0
+        self.forced_playouts, self.gumbel = opt.forced_k > 0.0, opt.gumbel[0] > 0
         self.game, self.capacity, self.num_simulations, self.num_parallel = game, int(capacity), int(num_simulations), int(num_parallel)
         self.key = _key(game, board_size, komi, max_steps, num_to_win, num_stack)
         self.eng = dropin_engine(game, board_size, self.capacity, num_simulations, num_parallel, c_puct_base, c_puct_init, root_noise, komi,

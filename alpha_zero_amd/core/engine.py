@@ -54,9 +54,9 @@ class EngineConfig:
     seed: int = 1
     rank: int = 0
     device_index: int = 0
-    leaf_symmetry: object = None     # None | "random" | 0..7: the board symmetry leaf positions are evaluated under (Engine.set_leaf_symmetry)
-    forced_playouts: object = None   # None | k >= 0: forced playouts at the root with policy-target pruning (Engine.set_forced_playouts)
-    gumbel: object = None            # None | m | (m, c_visit, c_scale): Gumbel root search with the completed-Q target (Engine.set_gumbel)
+    leaf_symmetry: object = None     # the opt-in search rules, as SearchOptions.of takes them: None | "random" | 0..7,
+    forced_playouts: object = None   # None | k >= 0,
+    gumbel: object = None            # None | m | (m, c_visit, c_scale)
 
 
 def leaf_symmetry_mode(mode):
@@ -97,10 +97,48 @@ def gumbel_params(gumbel):
     raise ValueError(f"gumbel must be None (off), an integer m >= 0 or (m, c_visit, c_scale) with finite c_visit, c_scale >= 0, got {gumbel!r}")
 
 
-def check_gumbel_alone(gumbel, forced_playouts):
-    """Gumbel root search and forced playouts both own the root's choice: one of them at most."""
-    if gumbel_params(gumbel)[0] > 0 and forced_playouts_k(forced_playouts) > 0.0:
-        raise ValueError("gumbel and forced_playouts cannot be on together: both decide what the root selects")
+EXCLUSIVE = "gumbel and forced_playouts cannot be on together: both decide what the root selects"
+
+
+@dataclass(frozen=True)
+class SearchOptions:
+    """The opt-in search rules of one engine, validated: what EngineConfig, dropin_engine, BatchSearch, SelfPlayActor and
+    run_selfplay_actor_loop take as `leaf_symmetry`, `forced_playouts`, `prune_policy_target`, `gumbel` and `playout_cap`."""
+    leaf_symmetry: object = None         # as given: None | "random" | 0..7
+    forced_k: float = 0.0                # 0.0 = off
+    prune_policy_target: bool = True
+    gumbel: tuple = (0, 50.0, 1.0)       # (m, c_visit, c_scale), m = 0 = off
+    playout_cap: object = None           # None | (fast_simulations, full_prob)
+
+    @classmethod
+    def of(cls, leaf_symmetry=None, forced_playouts=None, prune_policy_target=True, gumbel=None, playout_cap=None, num_simulations=None):
+        """The one place these values are checked (ValueError naming the allowed ones); the reference search has none of the rules and
+        all are off by default.
+        leaf_symmetry: None, "random" or an op 0..7 (Engine.set_leaf_symmetry): every leaf position is evaluated under that board
+        symmetry -- "random": one drawn per feature row -- and its priors are mapped back before the node is expanded; the evaluator sees
+        nothing but a different board, and pi, child_N, Q and harvested samples stay in the true orientation.
+        forced_playouts: None or a finite k >= 0 (Engine.set_forced_playouts; KataGo's, k = 2 there): in every search that is no fast
+        move of the playout cap, a root child in play gets at least sqrt(k P(c) sum N) visits.  The move is chosen from the unpruned
+        policy; prune_policy_target: the recorded pi rows (Engine.target_policies, the harvest) leave out the forced visits the search
+        did not want, False records the plain policy of the forced search.
+        gumbel: None, m or (m, c_visit, c_scale) (Engine.set_gumbel; Gumbel AlphaZero, Danihelka et al. 2022): every search that is no
+        fast move samples m root actions with Gumbel noise instead of adding Dirichlet noise, spends its simulations on them by
+        sequential halving, ends with the move a* (Engine.gumbel_moves; the actor plays it whatever warm-up and `deterministic` say)
+        and records softmax(logits + sigma(completed Q)) as the pi row.  Not together with forced_playouts.
+        playout_cap: None or (fast_simulations, full_prob) (Engine.set_playout_cap; the batched actor only): a move is a full search
+        (the slot's budget, root noise) with probability full_prob, else a fast one of fast_simulations (1..num_simulations, the upper
+        end checked where `num_simulations` is given) without noise that only moves the game on."""
+        leaf_symmetry_mode(leaf_symmetry)
+        k, g = forced_playouts_k(forced_playouts), gumbel_params(gumbel)
+        if g[0] > 0 and k > 0.0:
+            raise ValueError(EXCLUSIVE)
+        if playout_cap is not None:
+            fast, prob = playout_cap
+            top = float("inf") if num_simulations is None else num_simulations
+            if isinstance(fast, bool) or not isinstance(fast, (int, np.integer)) or not 1 <= fast <= top or not 0.0 <= float(prob) <= 1.0:
+                raise ValueError(f"playout_cap must be (fast_simulations in 1..{num_simulations}, full_prob in [0, 1]), got {playout_cap!r}")
+            playout_cap = (int(fast), float(prob))
+        return cls(leaf_symmetry, k, bool(prune_policy_target), g, playout_cap)
 
 
 MAX_NUM_STACK = 8  # the engine's history ring holds 8 boards (include/azsp.h AzspConfig.num_stack)
@@ -126,14 +164,12 @@ def pbc_tables(c_puct_base, c_puct_init, n):
 class Engine:
     """One engine = G concurrent games on one device.  `binding` comes from alpha_zero_amd._lib.load()."""
 
-    def __init__(self, binding: Binding, cfg: EngineConfig, device="cuda"):
+    def __init__(self, binding: Binding, cfg: EngineConfig, device="cuda", prune_policy_target=True, playout_cap=None):
+        """cfg.leaf_symmetry / .forced_playouts / .gumbel, prune_policy_target and playout_cap: SearchOptions.of."""
+        opt = SearchOptions.of(cfg.leaf_symmetry, cfg.forced_playouts, prune_policy_target, cfg.gumbel, playout_cap, cfg.num_simulations)
         self.b, self.cfg, self.device = binding, cfg, torch.device(device)
         self.on_launch = None
         check_num_stack(cfg.num_stack)
-        sym = leaf_symmetry_mode(cfg.leaf_symmetry)
-        forced = forced_playouts_k(cfg.forced_playouts)
-        gum = gumbel_params(cfg.gumbel)
-        check_gumbel_alone(cfg.gumbel, cfg.forced_playouts)
         c = AzspConfig()
         c.game = _abi.GAME_GO if cfg.game == "go" else _abi.GAME_GOMOKU
         c.board_size, c.num_games, c.num_parallel, c.num_simulations = cfg.board_size, cfg.num_games, cfg.num_parallel, cfg.num_simulations
@@ -174,15 +210,17 @@ class Engine:
         self.values = torch.zeros((self.rows,), dtype=torch.float32, device=self.device)
         self._actions = torch.zeros((self.G,), dtype=torch.int32, device=self.device)
         self._harvest_bufs = None
-        if sym != _abi.SYM_OFF:
-            self.set_leaf_symmetry(cfg.leaf_symmetry)  # before the first select: the first root evaluation is transformed too
         self._forced_k, self._gumbel_m = 0.0, 0  # what is on now: the two rules exclude each other
-        self.forced_playouts = False  # forced playouts have been on at least once: the target rows exist (target_policies)
-        if forced > 0.0:
-            self.set_forced_playouts(forced)
-        self.gumbel = False  # the Gumbel root search has been on at least once: the n0 and target rows exist (gumbel_moves, target_policies)
-        if gum[0] > 0:
-            self.set_gumbel(cfg.gumbel)
+        # each has been on at least once, so its rows exist: the target rows (target_policies); the n0 rows too (gumbel_moves)
+        self.forced_playouts = self.gumbel = False
+        if opt.leaf_symmetry is not None:
+            self.set_leaf_symmetry(opt.leaf_symmetry)  # before the first select: the first root evaluation is transformed too
+        if opt.forced_k > 0.0:
+            self.set_forced_playouts(opt.forced_k, opt.prune_policy_target)
+        if opt.gumbel[0] > 0:
+            self.set_gumbel(opt.gumbel)
+        if opt.playout_cap is not None:
+            self.set_playout_cap(*opt.playout_cap)  # before the first root: the first move of every game draws its class too
 
     # -- plumbing ---------------------------------------------------------------------------------
     def _ck(self, rc, what):
@@ -404,7 +442,7 @@ class Engine:
         Holds for the selections and move ends from now on."""
         kk = forced_playouts_k(k)
         if kk > 0.0 and self._gumbel_m > 0:
-            raise ValueError("gumbel and forced_playouts cannot be on together: both decide what the root selects")
+            raise ValueError(EXCLUSIVE)
         self._ck(self.b.dll.azsp_set_forced_playouts(self.h, C.c_double(kk), int(bool(prune_target))), "azsp_set_forced_playouts")
         self._forced_k = kk
         self.forced_playouts = self.forced_playouts or kk > 0.0
@@ -419,7 +457,7 @@ class Engine:
         with forced playouts (ValueError).  Holds for the searches that begin from now on."""
         m, cv, cs = gumbel_params(gumbel)
         if m > 0 and self._forced_k > 0.0:
-            raise ValueError("gumbel and forced_playouts cannot be on together: both decide what the root selects")
+            raise ValueError(EXCLUSIVE)
         self._ck(self.b.dll.azsp_set_gumbel(self.h, m, C.c_double(cv), C.c_double(cs)), "azsp_set_gumbel")
         self._gumbel_m = m
         self.gumbel = self.gumbel or m > 0

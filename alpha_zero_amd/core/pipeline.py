@@ -47,7 +47,7 @@ import warnings  # noqa: E402
 
 import torch  # noqa: E402
 
-from .engine import Engine, EngineConfig  # noqa: E402
+from .engine import Engine, EngineConfig, SearchOptions, check_num_stack  # noqa: E402
 from .network import AlphaZeroNet, InferenceNet, capture_graph, widen_for_kernels  # noqa: E402
 from .replay import Transition  # noqa: E402
 
@@ -124,29 +124,14 @@ class SelfPlayActor:
         the caller disabled the kernels' feature layouts); True / False force it.
         num_stack: history boards per observation (the env's num_stack, 1..8): the engine writes 2 * num_stack + 1 planes, which must be
         the network's input channels.
-        playout_cap: None, or (fast_simulations, full_prob) = playout-cap randomisation (Engine.set_playout_cap; the reference has none):
-        a move is a full search (num_simulations, root noise) with probability full_prob, else a fast one of fast_simulations without
-        noise that only moves the game on.  Every move is recorded; `harvest()` hands the learner the full-search samples only,
-        `harvest_tensors()` leaves the flags in `last_harvest_full`.
-        leaf_symmetry: None, "random" or an op 0..7 (Engine.set_leaf_symmetry; the reference search has none): every leaf position is
-        evaluated under that board symmetry -- "random": one drawn per feature row -- and its priors are mapped back before the node is
-        expanded.  The evaluator sees nothing but a different board; harvested samples stay in the true orientation.
-        forced_playouts: None, or k >= 0 (Engine.set_forced_playouts; KataGo's forced playouts, k = 2 there; the reference has none):
-        in every search that is no fast move of the playout cap, a root child in play gets at least sqrt(k P(c) sum N) visits.
-        prune_policy_target: the harvested pi rows leave out the forced visits the search did not want (policy-target pruning);
-        False records the plain policy of the forced search.  The move is always chosen from the unpruned policy.
-        gumbel: None, m or (m, c_visit, c_scale) (Engine.set_gumbel; Gumbel AlphaZero, Danihelka et al. 2022; the reference has none):
-        every search that is no fast move of the playout cap samples m root actions with Gumbel noise instead of adding Dirichlet
-        noise, spends its simulations on them by sequential halving, plays the move a* it ends with (whatever warm-up and
-        `deterministic` say) and records softmax(logits + sigma(completed Q)) as the pi row.  Not together with forced_playouts."""
+        playout_cap, leaf_symmetry, forced_playouts, prune_policy_target, gumbel: the opt-in search rules, SearchOptions.of.  Under a
+        playout cap every move is recorded; `harvest()` hands the learner the full-search samples only, `harvest_tensors()` leaves the
+        flags in `last_harvest_full`."""
+        opt = SearchOptions.of(leaf_symmetry, forced_playouts, prune_policy_target, gumbel, playout_cap, num_simulations)  # ValueError before anything is built
         from .. import _lib
-        from .engine import check_gumbel_alone, check_num_stack, forced_playouts_k, gumbel_params, leaf_symmetry_mode
 
-        leaf_symmetry_mode(leaf_symmetry)  # ValueError before anything is built
-        self.leaf_symmetry = leaf_symmetry
-        self.forced_playouts, self.prune_policy_target = forced_playouts_k(forced_playouts), bool(prune_policy_target)
-        check_gumbel_alone(gumbel, forced_playouts)
-        self.gumbel = gumbel_params(gumbel) if gumbel is not None else None
+        self.leaf_symmetry, self.forced_playouts, self.prune_policy_target = opt.leaf_symmetry, opt.forced_k, opt.prune_policy_target
+        self.gumbel, self.playout_cap = opt.gumbel if gumbel is not None else None, opt.playout_cap
         self.num_stack = check_num_stack(num_stack)
         check_input_channels(network, self.num_stack)
 
@@ -184,16 +169,7 @@ class SelfPlayActor:
             if not hasattr(self.cfg, k):
                 raise TypeError(f"unknown engine option {k}")
             setattr(self.cfg, k, v)
-        self.engine = Engine(self.binding, self.cfg, device=self.device)
-        if self.forced_playouts > 0.0 and not self.prune_policy_target:
-            self.engine.set_forced_playouts(self.forced_playouts, prune_target=False)
-        self.playout_cap = None
-        if playout_cap is not None:
-            fast, prob = playout_cap
-            if isinstance(fast, bool) or not isinstance(fast, (int, np.integer)) or not 1 <= fast <= num_simulations or not 0.0 <= float(prob) <= 1.0:
-                raise ValueError(f"playout_cap must be (fast_simulations in 1..{num_simulations}, full_prob in [0, 1]), got {playout_cap!r}")
-            self.playout_cap = (int(fast), float(prob))
-            self.engine.set_playout_cap(*self.playout_cap)  # before the first root: the first move of every game draws its class too
+        self.engine = Engine(self.binding, self.cfg, device=self.device, prune_policy_target=self.prune_policy_target, playout_cap=self.playout_cap)
         self.last_harvest_full = torch.zeros(0, dtype=torch.bool, device=self.device)
         self.engine.reset_games()
         self._graph = None
@@ -425,11 +401,9 @@ def run_selfplay_actor_loop(seed, rank, network, device, data_queue, env, num_si
     """Same role and argument list as the reference actor entry point (pipeline.py:166-189), extended by
     `num_games`: one call drives `num_games` games on `device` and puts (game_seq, stats) tuples on
     `data_queue` exactly as `num_games` reference actors would.  `net_dtype` defaults to the reference's evaluator precision (fp32,
-    see SelfPlayActor).  `playout_cap`: None or (fast_simulations, full_prob), see SelfPlayActor: the queued game_seq then hold the
-    full-search samples only.  `leaf_symmetry`: None, "random" or an op 0..7, see SelfPlayActor: the search's evaluations are made under
-    board symmetries, the queued samples stay in the true orientation.  `forced_playouts`: None or k >= 0, see SelfPlayActor: forced
-    playouts at the root, the queued pi rows are the pruned policy targets.  `gumbel`: None, m or (m, c_visit, c_scale), see
-    SelfPlayActor: Gumbel root search, the queued pi rows are the completed-Q targets."""
+    see SelfPlayActor).  `playout_cap`, `leaf_symmetry`, `forced_playouts`, `gumbel`: the opt-in search rules, SearchOptions.of; under a
+    playout cap the queued game_seq hold the full-search samples only, and the queued pi rows are the rule's policy targets."""
+    SearchOptions.of(leaf_symmetry, forced_playouts, gumbel=gumbel, playout_cap=playout_cap, num_simulations=num_simulations)
     import os
 
     game = "go" if env.has_pass_move else "gomoku"

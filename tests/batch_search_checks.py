@@ -269,7 +269,7 @@ def check_begin_moves(kind, game="go", n=5, K=8, G=4, sims=24):
     pos[:, _abi.PS_TO_PLAY] = [1, -1, 1, -1] if game == "go" else [1, 2, 1, 2]
     pos[:, _abi.PS_KO], pos[:, _abi.PS_LAST_PASS] = -1, 0  # (no pass ends a game here: every slot keeps a sub-tree for the second move)
     rng = np.random.Generator(np.random.PCG64(5))
-    A = n * n + (1 if game == "go" else 0)
+    A = eu.num_actions(game, n)
     na, nb, nc, nd = (rng.dirichlet(np.full(A, 0.3), size=G) for _ in range(4))
     S = _abi.BM_SKIP
     many = make_engine(kind, game, n, K, G, P=1, sims=sims, root_noise=True)

@@ -62,7 +62,7 @@ def check_mixed_budgets_equal_uniform_searches(kind, game="go", n=5, P=1):
     is done at once and keeps its count; any other stops in the first round that reaches the budget (P = 1: exactly at the budget).
 
     Last, the positions are loaded again and search(num_simulations=None) equals the fresh uniform search at 24."""
-    A = n * n + (1 if game == "go" else 0)
+    A = eu.num_actions(game, n)
     extra = P if P > 1 else 0  # the reference's parallel search stops at num_simulations + num_parallel root visits (mcts_v2.py:568)
     boards, hist, pos = bc.positions(game, n, 8, GAMES)
     # slot s starts at BUDGETS[s % 3]; by (s // 3) % 3 it keeps that budget, changes it at the second and again at the third move, or
@@ -234,7 +234,7 @@ MAX_STEPS = 14  # short games (go.py:176-178 ends a game at max_steps): every sl
 
 def _actor(kind, P, game="go", n=5, G=GAMES, sims=SIMS, net=None, seed=5, **kw):
     b, dev = eu.backend(kind)
-    A = n * n + (1 if game == "go" else 0)
+    A = eu.num_actions(game, n)
     net = net or AlphaZeroNet((17, n, n), A, 1, 8, 8, gomoku=(game != "go"))
     ekw = dict(log_moves=True, log_capacity=MAX_STEPS if game == "go" else n * n, stop_at_game_end=True)
     if game == "go":

@@ -2,11 +2,13 @@
   * the host twin (tests/hosttwin, CPU, `-m "not gpu"`): identical engine source, WaveHost policy
   * libazsp.so on a MI355X (`-m gpu`): the product
 and compare with the golden vectors produced by the reference / with the CPU oracle."""
+import contextlib
 import ctypes
 import hashlib
 import os
 import subprocess
 from types import SimpleNamespace
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -211,24 +213,83 @@ def random_openings(engine, plies, rng):
 # ---------------------------------------------------------------------------------------------------
 # search / actor replay with injected randomness (an MCTS golden file, or the CPU oracle's games)
 # ---------------------------------------------------------------------------------------------------
-def run_injected_search(kind, noise, unif, eval_batch, plies=None, on_features=None, max_rounds=None, **engine_kw):
+class SearchRun(NamedTuple):
+    """What run_injected_search returns: logs[g][k] = dict(pi, child_N, root_q, child_q, move) of game g's k-th logged search, the harvest
+    (states, pi, z, games) of every finished game, evaluations per game and ply, the counters, and rows[j][g] = the g-th row of array
+    j of `rows_after_move` after every move of slot g (() when nothing was read)."""
+    logs: list
+    harvest: tuple
+    n_evals: np.ndarray
+    counters: dict
+    rows: tuple
+
+
+def search_logs(eng, plies):
+    """Per game the logged searches (Engine.get_search) of its first plies[g] moves."""
+    logs = []
+    for gi in range(eng.G):
+        per = []
+        for k in range(int(plies[gi])):
+            pi, cn, q = eng.get_search(gi, k)
+            per.append(dict(pi=pi, child_N=cn, root_q=q[_abi.SQ_ROOT_Q], child_q=q[_abi.SQ_CHILD_Q], move=int(q[_abi.SQ_MOVE])))
+        logs.append(per)
+    return logs
+
+
+def harvest_all(eng):
+    """(states, pi, z, games) of every finished game as host arrays, game rows with START rebased.  The output window may be smaller
+    than all finished games: harvest until drained."""
+    parts, base = [], 0
+    while True:
+        states, pi, z, games = eng.harvest()
+        if len(games) == 0:
+            break
+        games = games.copy()
+        games[:, _abi.GR_START] += base
+        base += len(z)
+        parts.append((states.cpu().numpy().copy(), pi.cpu().numpy().copy(), z.cpu().numpy().copy(), games))
+    if not parts:
+        return (np.zeros((0, eng.planes, eng.N, eng.N), np.int8), np.zeros((0, eng.A), np.float32), np.zeros(0, np.float32),
+                np.zeros((0, _abi.GR_COUNT), np.int32))
+    return tuple(np.concatenate([p[i] for p in parts]) for i in range(4))
+
+
+def run_injected_search(kind, noise, unif, eval_batch, plies=None, on_features=None, max_rounds=None, setup=None, on_round=None, inject=True,
+                        rows_after_move=None, **engine_kw):
     """The batched actor on noise.shape[0] games with the given randomness injected (noise [G, M, A], unif [G, M, 16]; engine_kw: the
     other EngineConfig fields): select -> eval_batch on the decoded planes of the valid rows -> round, until every game idles.
-    on_features(round, decoded planes, engine) sees every round; max_rounds: stop after that many rounds and return None (feature
-    checks that need no search results).  Returns (per game the logged searches of its first plies[g] moves -- default: all it played --,
-    the harvest (states, pi, z, games) of every finished game, evaluations per game and ply, counters)."""
+    setup(eng) runs before the injection and reset_games; inject=False: a seeded engine that draws for itself (noise only gives the
+    shape).  on_round(eng, i) runs in front of round i; on_features(round, decoded planes, engine) sees every round; max_rounds: stop
+    after that many rounds and return None (feature checks that need no search results).  rows_after_move(eng) -> a tuple of [G, ...]
+    arrays, or None to read nothing this round: called at the top of every round, and the rows of the slots whose ply advanced since
+    the last one are kept (SearchRun.rows).  plies: the logged searches per game, default all it played.  Returns a SearchRun."""
     binding, dev = backend(kind)
     G, M, A = noise.shape
-    eng = Engine(binding, EngineConfig(num_games=G, inject_random=True, inject_moves=M, stop_at_game_end=True, log_moves=True, log_capacity=M,
-                                       **engine_kw), device=dev)
-    eng.set_injection(noise, unif)
+    eng = Engine(binding, EngineConfig(num_games=G, inject_random=inject, inject_moves=M if inject else 0, stop_at_game_end=True, log_moves=True,
+                                       log_capacity=M, **engine_kw), device=dev)
+    if setup is not None:
+        setup(eng)
+    if inject:
+        eng.set_injection(noise, unif)
     eng.reset_games()
+    eng.counters(reset=True)  # (all zero here unless `setup` ran searches of its own)
     n_evals = np.zeros((G, M), dtype=np.int64)
-    rounds = 0
+    kept, seen = (), np.zeros(G, dtype=np.int64)
     eng.select()
-    while True:
+    for rounds in range(200000):
+        if on_round is not None:
+            on_round(eng, rounds)
         valid = eng.valid.cpu().numpy().astype(bool)
         st, _ = eng.status()
+        got = rows_after_move(eng) if rows_after_move is not None else None
+        if got is not None:
+            kept = kept or tuple([[] for _ in range(G)] for _ in got)
+            ply = np.minimum(st[:, _abi.STC_PLY], M)
+            assert np.all(ply - seen <= 1)  # (a kept sub-tree never holds a whole budget in these shapes: one move per round)
+            for g in np.flatnonzero(ply > seen):
+                for per, arr in zip(kept, got):
+                    per[g].append(arr[g].copy())
+            seen = ply.astype(np.int64)
         if not valid.any() and np.all(st[:, _abi.STC_STATUS] == _abi.ST_IDLE):
             break
         feats = decode_features(eng)
@@ -246,31 +307,11 @@ def run_injected_search(kind, noise, unif, eval_batch, plies=None, on_features=N
         eng.priors.copy_(torch.from_numpy(pri))
         eng.values.copy_(torch.from_numpy(val))
         eng.round()
-        rounds += 1
-        assert rounds < 200000
-    if plies is None:
-        plies = np.minimum(st[:, _abi.STC_PLY], M)
-    logs = []
-    for gi in range(G):
-        per = []
-        for k in range(int(plies[gi])):
-            pi, cn, q = eng.get_search(gi, k)
-            per.append(dict(pi=pi, child_N=cn, root_q=q[_abi.SQ_ROOT_Q], child_q=q[_abi.SQ_CHILD_Q], move=int(q[_abi.SQ_MOVE])))
-        logs.append(per)
-    parts, base = [], 0
-    while True:  # the output window may be smaller than all finished games: harvest until drained
-        states, pi, z, games = eng.harvest()
-        if len(games) == 0:
-            break
-        games = games.copy()
-        games[:, _abi.GR_START] += base
-        base += len(z)
-        parts.append((states.cpu().numpy().copy(), pi.cpu().numpy().copy(), z.cpu().numpy().copy(), games))
-    hv = (tuple(np.concatenate([p[i] for p in parts]) for i in range(4)) if parts else
-          (np.zeros((0, eng.planes, eng.N, eng.N), np.int8), np.zeros((0, A), np.float32), np.zeros(0, np.float32), np.zeros((0, _abi.GR_COUNT), np.int32)))
-    counters = eng.counters()
+    else:
+        raise AssertionError("the games did not finish")
+    out = SearchRun(search_logs(eng, np.minimum(st[:, _abi.STC_PLY], M) if plies is None else plies), harvest_all(eng), n_evals, eng.counters(), kept)
     eng.close()
-    return logs, hv, n_evals, counters
+    return out
 
 
 def run_golden_selfplay(kind, G_gold, eval_batch, feature_dtype=_abi.FEAT_I8, num_stack=None, **kw):
@@ -295,42 +336,103 @@ def run_golden_selfplay(kind, G_gold, eval_batch, feature_dtype=_abi.FEAT_I8, nu
 # ---------------------------------------------------------------------------------------------------
 # engine vs CPU oracle on fresh seeded games (no golden file needed; used by -m gpu tests and smoke())
 # ---------------------------------------------------------------------------------------------------
-def oracle_selfplay(game, n, sims, P, ngames, seed, max_moves, eval_func_factory, warm_up_steps=4, resign_threshold=-1.0,
-                    resign_disabled=True, check_resign_after_steps=40, max_steps=0):
-    """Plays `ngames` games with the CPU oracle; returns (noise, uniforms, per-move logs, game results)."""
-    from oracle import actor, mcts
+def num_actions(game, n):
+    return n * n + (1 if game == "go" else 0)
+
+
+def make_oracle_env(game, n, max_steps=0, num_to_win=5):
     from oracle.envs import OracleGoEnv, OracleGomokuEnv
 
+    return OracleGoEnv(n, max_steps=max_steps) if game == "go" else OracleGomokuEnv(n, num_to_win=num_to_win)
+
+
+def empty_positions(n, G):
+    """(boards, hist, pos) of BatchSearch.load / Engine.set_states: the empty board with black to move in every one of G slots."""
+    boards, hist = np.zeros((G, n, n), np.int8), np.zeros((G, 8, n, n), np.int8)
+    pos = np.zeros((G, _abi.PS_COUNT), np.int32)
+    pos[:, _abi.PS_TO_PLAY], pos[:, _abi.PS_KO] = 1, -1
+    return boards, hist, pos
+
+
+def small_go9_device_evaluator():
+    """(InferenceNet, DeviceEvaluator) of a small seeded 9x9 network on the fp32-class (split-precision) kernels.  (Device only.)"""
+    from alpha_zero_amd import _lib
+    from alpha_zero_amd.core.evaluate import DeviceEvaluator
+    from alpha_zero_amd.core.network import AlphaZeroNet, InferenceNet
+
+    torch.manual_seed(0)
+    inf = InferenceNet(AlphaZeroNet((17, 9, 9), 82, 2, 128, 64), dtype=torch.float32, binding=_lib.load()).cuda()
+    return inf, DeviceEvaluator(inf)
+
+
+def shape_table(shapes, **fixed):
+    """The two readers of a module's SHAPES table (name -> dict(game, n, sims, G, max_moves, seed[, max_steps, num_to_win])):
+    selfplay_args(name, P) = the arguments of oracle_selfplay for that shape, engine_kw(name, P, **more) = the EngineConfig fields of the
+    same games (`fixed`: fields every case of the module shares)."""
+    def selfplay_args(name, P):
+        s = shapes[name]
+        return (s["game"], s["n"], s["sims"], P, s["G"], s["seed"], s["max_moves"]), dict(max_steps=s.get("max_steps", 0), num_to_win=s.get("num_to_win", 5))
+
+    def engine_kw(name, P, **more):
+        s = shapes[name]
+        return dict(game=s["game"], board_size=s["n"], num_parallel=P, num_simulations=s["sims"], max_plies=s["max_moves"], warm_up_steps=4,
+                    max_steps=s.get("max_steps", 0), num_to_win=s.get("num_to_win", 5), force_resign_disabled=1, **fixed, **more)
+
+    return selfplay_args, engine_kw
+
+
+def oracle_selfplay(game, n, sims, P, ngames, seed, max_moves, rule=None, noise=None, unif=None, eval_factory=None, root_noise=True,
+                    reuse_tree=True, num_to_win=5, warm_up_steps=4, resign_threshold=-1.0, resign_disabled=True, check_resign_after_steps=40,
+                    max_steps=0):
+    """Plays `ngames` games with the CPU oracle's actor; returns (noise, uniforms, per game the per-move logs, per game (seq, stats),
+    what the rule counted).  noise / unif: the injected rows; None = drawn from PCG64(seed), Dirichlet rows first.  rule: None, or a
+    callable that gives a context manager under which the oracle searches by another rule (forced_checks.restated,
+    gumbel_checks.restated); it yields a dict whose 'searches' hold one record per finished search, which is merged into that move's
+    log (its 'N' as child_N), and whose other entries (event counts, margins) are summed over the games."""
+    from oracle import actor, mcts
+    from synth_eval import make_eval_func
+
     rng = np.random.Generator(np.random.PCG64(seed))
-    A = n * n + (1 if game == "go" else 0)
+    A = num_actions(game, n)
     M = max_moves + 1
-    noise = rng.dirichlet(np.full(A, 0.03), size=(ngames, M))
-    unif = rng.random((ngames, M, 16))
-    logs, results = [], []
+    if noise is None:
+        noise = rng.dirichlet(np.full(A, 0.03), size=(ngames, M))
+    if unif is None:
+        unif = rng.random((ngames, M, 16))
+    logs, results, counted = [], [], {}
     for gi in range(ngames):
-        env = OracleGoEnv(n, max_steps=max_steps) if game == "go" else OracleGomokuEnv(n)
+        env = make_oracle_env(game, n, max_steps, num_to_win)
         per = []
 
         def on_move(k, env_, move, pi, rq, cq, root):
             cn = root.N[root.parent[root.root]].copy() if root is not None else None
             per.append(dict(move=int(move), pi=np.asarray(pi, dtype=np.float64), root_q=float(rq), child_q=float(cq), child_N=cn))
 
-        seq, stats = actor.play_one_game(
-            env, eval_func_factory(A), num_simulations=sims, num_parallel=P, warm_up_steps=warm_up_steps,
-            check_resign_after_steps=check_resign_after_steps, resign_threshold=resign_threshold, resign_disabled=resign_disabled,
-            rand_for_move=lambda k: mcts.InjectedRand(noise[gi, k], unif[gi, k]), on_move=on_move, max_moves=max_moves)
+        with (rule() if rule is not None else contextlib.nullcontext(dict(searches=[]))) as rec:
+            seq, stats = actor.play_one_game(
+                env, (eval_factory or make_eval_func)(A), num_simulations=sims, num_parallel=P, warm_up_steps=warm_up_steps,
+                check_resign_after_steps=check_resign_after_steps, resign_threshold=resign_threshold, resign_disabled=resign_disabled,
+                root_noise=root_noise, reuse_tree=reuse_tree, rand_for_move=lambda k: mcts.InjectedRand(noise[gi, k], unif[gi, k]),
+                on_move=on_move, max_moves=max_moves)
+        assert rule is None or len(rec["searches"]) >= len(per)
+        for move, s in zip(per, rec["searches"]):
+            assert move["move"] == s.get("move", move["move"])
+            move.update(s, child_N=s["N"])
+        for key, v in rec.items():
+            if key != "searches":
+                counted[key] = counted[key] + v if key in counted else v
         logs.append(per)
         results.append((seq, stats))
-    return noise, unif, logs, results
+    return noise, unif, logs, results, counted
 
 
 def compare_engine_with_oracle(kind, game, n, sims, P, ngames, seed, max_moves, **kw):
     """Bit-exact comparison of the engine with the oracle on seeded games; returns the engine counters."""
     from alpha_zero_amd.core.pipeline import game_stats_from_row
-    from synth_eval import eval_batch, make_eval_func
+    from synth_eval import eval_batch
 
-    noise, unif, ologs, ores = oracle_selfplay(game, n, sims, P, ngames, seed, max_moves, lambda A: make_eval_func(A), **kw)
-    elogs, (states, pis, zs, games), _, cnt = run_injected_search(
+    noise, unif, ologs, ores, _ = oracle_selfplay(game, n, sims, P, ngames, seed, max_moves, **kw)
+    elogs, (states, pis, zs, games), _, cnt, _ = run_injected_search(
         kind, noise, unif, eval_batch, game=game, board_size=n, num_parallel=P, num_simulations=sims, max_plies=max_moves,
         warm_up_steps=kw.get("warm_up_steps", 4), resign_threshold=kw.get("resign_threshold", -1.0),
         check_resign_after_steps=kw.get("check_resign_after_steps", 40), force_resign_disabled=1 if kw.get("resign_disabled", True) else 0,

@@ -19,9 +19,7 @@ from alpha_zero_amd import _abi
 from alpha_zero_amd.core.batch_search import BatchSearch
 from alpha_zero_amd.core.engine import Engine, EngineConfig
 from alpha_zero_amd.core.network import AlphaZeroNet
-from oracle import actor as oactor
 from oracle import mcts
-from oracle.envs import OracleGoEnv, OracleGomokuEnv
 from synth_eval import eval_batch, make_eval_func
 
 K = 2.0  # KataGo's factor
@@ -135,113 +133,30 @@ def restated(k, prune=True, cb=CB, ci=CI):
         mcts._best_child, mcts._finish = best, finish
 
 
-def make_env(game, n, max_steps=0, num_to_win=5):
-    return OracleGoEnv(n, max_steps=max_steps) if game == "go" else OracleGomokuEnv(n, num_to_win=num_to_win)
-
-
-def restated_selfplay(game, n, sims, P, G, seed, max_moves, k, root_noise, max_steps=0, num_to_win=5, warm_up_steps=4, prune=True,
-                      noise=None, eval_factory=make_eval_func):
-    """G games of the oracle's actor under the rule: (noise, uniforms, per game the per-move records, the rule's event counts)."""
-    A = n * n + (1 if game == "go" else 0)
-    M = max_moves + 1
-    rng = np.random.Generator(np.random.PCG64(seed))
-    if noise is None:
-        noise = rng.dirichlet(np.full(A, 0.03), size=(G, M))
-    unif = rng.random((G, M, 16))
-    logs, events = [], dict(forced=0, ended=0)
-    for gi in range(G):
-        env = make_env(game, n, max_steps, num_to_win)
-        per = []
-
-        def on_move(kk, env_, move, pi, rq, cq, root):
-            per.append(dict(move=int(move), pi=np.asarray(pi), root_q=float(rq), child_q=float(cq)))
-
-        with restated(k, prune) as rec:
-            seq, _ = oactor.play_one_game(env, eval_factory(A), num_simulations=sims, num_parallel=P, warm_up_steps=warm_up_steps,
-                                          root_noise=root_noise, rand_for_move=lambda kk: mcts.InjectedRand(noise[gi, kk], unif[gi, kk]),
-                                          on_move=on_move, max_moves=max_moves)
-        assert len(rec["searches"]) >= len(per)
-        for move, s in zip(per, rec["searches"]):
-            move.update(child_N=s["N"], Np=s["Np"], target=s["target"], legal=s["legal"])
-        logs.append(dict(moves=per, finished=seq is not None))
-        events["forced"] += rec["forced"]
-        events["ended"] += rec["ended"]
-    return noise, unif, logs, events
+def restated_selfplay(game, n, sims, P, G, seed, max_moves, k, root_noise, max_steps=0, num_to_win=5, prune=True, noise=None, eval_factory=None):
+    """G games of the oracle's actor under the rule: (noise, uniforms, per game the per-move records, the rule's event counts).  The
+    randomness is eu.oracle_selfplay's own: PCG64(seed), the Dirichlet rows (unless given), then the uniforms."""
+    noise, unif, logs, results, events = eu.oracle_selfplay(game, n, sims, P, G, seed, max_moves, rule=lambda: restated(k, prune), noise=noise,
+                                                            eval_factory=eval_factory, root_noise=root_noise, max_steps=max_steps, num_to_win=num_to_win)
+    return noise, unif, [dict(moves=per, finished=seq is not None) for per, (seq, _) in zip(logs, results)], events
 
 
 # ---------------------------------------------------------------------------------------------------
-# the engine under injected randomness, with the target rows of every move
+# the engine under injected randomness (eu.run_injected_search), with the target rows of every move
 # ---------------------------------------------------------------------------------------------------
-def run_engine(kind, noise, unif, evaluator, setup=None, read_targets=True, **engine_kw):
-    """engine_util.run_injected_search that also reads the slots' target rows (Engine.target_policies) after every round.  setup(eng)
-    runs before the games are reset; read_targets=False leaves the target rows alone.  Returns dict(logs, targets, harvest, counters): logs[g][k] = pi / child_N / root_q / child_q / move,
-    targets[g][k] = float64[A] (empty lists while forced playouts were never on), harvest = (states, pi, z, games)."""
-    b, dev = eu.backend(kind)
-    G, M, A = noise.shape
-    eng = Engine(b, EngineConfig(num_games=G, inject_random=True, inject_moves=M, stop_at_game_end=True, log_moves=True, log_capacity=M,
-                                 **engine_kw), device=dev)
-    if setup is not None:
-        setup(eng)
-    eng.set_injection(noise, unif)
-    eng.reset_games()
-    eng.counters(reset=True)
-    targets = [[] for _ in range(G)]
-    seen = np.zeros(G, dtype=np.int64)
-    eng.select()
-    for _ in range(200000):
-        valid = eng.valid.cpu().numpy().astype(bool)
-        st, _ = eng.status()
-        if eng.forced_playouts and read_targets:
-            tp = eng.target_policies().cpu().numpy()
-            ply = np.minimum(st[:, _abi.STC_PLY], M)
-            assert np.all(ply - seen <= 1)  # (a kept sub-tree never holds a whole budget in these shapes: one move per round)
-            for g in np.flatnonzero(ply > seen):
-                targets[g].append(tp[g].copy())
-            seen = ply.astype(np.int64)
-        if not valid.any() and np.all(st[:, _abi.STC_STATUS] == _abi.ST_IDLE):
-            break
-        pri, val = np.zeros((eng.rows, A), dtype=np.float32), np.zeros(eng.rows, dtype=np.float32)
-        rows = np.flatnonzero(valid)
-        if len(rows):
-            pri[rows], val[rows] = evaluator(eu.decode_features(eng)[rows], A)
-        eng.priors.copy_(torch.from_numpy(pri))
-        eng.values.copy_(torch.from_numpy(val))
-        eng.round()
-    else:
-        raise AssertionError("the games did not finish")
-    logs = []
-    for g in range(G):
-        per = []
-        for k in range(int(min(st[g, _abi.STC_PLY], M))):
-            pi, cn, q = eng.get_search(g, k)
-            per.append(dict(pi=pi, child_N=cn, root_q=q[_abi.SQ_ROOT_Q], child_q=q[_abi.SQ_CHILD_Q], move=int(q[_abi.SQ_MOVE])))
-        logs.append(per)
-    parts, base = [], 0
-    while True:
-        states, pi, z, games = eng.harvest()
-        if len(games) == 0:
-            break
-        games = games.copy()
-        games[:, _abi.GR_START] += base
-        base += len(z)
-        parts.append((states.cpu().numpy().copy(), pi.cpu().numpy().copy(), z.cpu().numpy().copy(), games))
-    hv = (tuple(np.concatenate([p[i] for p in parts]) for i in range(4)) if parts else
-          (np.zeros((0, eng.planes, eng.N, eng.N), np.int8), np.zeros((0, A), np.float32), np.zeros(0, np.float32), np.zeros((0, _abi.GR_COUNT), np.int32)))
-    counters = eng.counters()
-    eng.close()
-    return dict(logs=logs, targets=targets, harvest=hv, counters=counters)
+def target_rows(eng):
+    """rows_after_move of eu.run_injected_search: the slots' target rows (SearchRun.rows[0]), nothing while forced playouts were never on."""
+    return (eng.target_policies().cpu().numpy(),) if eng.forced_playouts else None
 
 
 def same_run(a, b, targets=True):
-    """Bit for bit: logs, harvest, counters (and the target rows)."""
+    """Bit for bit: two SearchRuns' logs, harvest, evaluations per ply, counters (and the rows read after every move)."""
     try:
-        sc.assert_same_outputs((a["logs"], a["harvest"], 0, a["counters"]), (b["logs"], b["harvest"], 0, b["counters"]))
+        sc.assert_same_outputs(a, b)
     except AssertionError:
         return False
-    if targets:
-        return len(a["targets"]) == len(b["targets"]) and all(len(x) == len(y) and all(p.tobytes() == q.tobytes() for p, q in zip(x, y))
-                                                              for x, y in zip(a["targets"], b["targets"]))
-    return True
+    as_bytes = lambda run: [[[r.tobytes() for r in per] for per in arr] for arr in run.rows]  # noqa: E731
+    return not targets or as_bytes(a) == as_bytes(b)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -259,17 +174,17 @@ SHAPES = {
 CASES = [("go5", 1), ("go5", 4), ("go9", 1), ("go9", 4), ("go9", 8), ("gomoku7", 1), ("gomoku7", 4), ("go19", 4)]
 
 
+_selfplay_args, _shape_kw = eu.shape_table(SHAPES)
+
+
 @functools.lru_cache(maxsize=None)
 def _restated_case(shape, P, root_noise, k=K, prune=True):
-    s = SHAPES[shape]
-    return restated_selfplay(s["game"], s["n"], s["sims"], P, s["G"], s["seed"], s["max_moves"], k, root_noise, max_steps=s.get("max_steps", 0),
-                             num_to_win=s.get("num_to_win", 5), prune=prune)
+    args, kw = _selfplay_args(shape, P)
+    return restated_selfplay(*args, k, root_noise, prune=prune, **kw)
 
 
 def _engine_kw(shape, P, root_noise):
-    s = SHAPES[shape]
-    return dict(game=s["game"], board_size=s["n"], num_parallel=P, num_simulations=s["sims"], max_plies=s["max_moves"], warm_up_steps=4,
-                max_steps=s.get("max_steps", 0), num_to_win=s.get("num_to_win", 5), root_noise=root_noise, force_resign_disabled=1)
+    return _shape_kw(shape, P, root_noise=root_noise)
 
 
 def assert_pruning_invariants(move, A, f32):
@@ -287,19 +202,20 @@ def check_restatement(kind, shape, P, root_noise, k=K, expect_ended=True, read_t
     """The engine with forced_playouts = k (2) against the restated search over consecutive moves with tree reuse: child_N, the unpruned
     pi, root and child Q, the moves; target_pi exactly; the harvested pi rows against the float32 cast of the target.
     read_targets=False is for searches in which a kept sub-tree can hold a whole budget, so that a slot makes two moves in one round and
-    run_engine cannot read its target row in between: the targets are then compared through the harvested rows only."""
+    the driver cannot read its target row in between: the targets are then compared through the harvested rows only."""
     s = SHAPES[shape]
     noise, unif, want, events = _restated_case(shape, P, root_noise, k)
-    got = run_engine(kind, noise, unif, eval_batch, forced_playouts=k, read_targets=read_targets, **_engine_kw(shape, P, root_noise))
+    got = eu.run_injected_search(kind, noise, unif, eval_batch, forced_playouts=k, rows_after_move=target_rows if read_targets else None,
+                                 **_engine_kw(shape, P, root_noise))
     A = noise.shape[2]
     f32 = s["game"] != "go"
     assert events["forced"] > 0
     if P > 1 and expect_ended:
         assert events["ended"] > 0, "no select phase in which the in-flight count ended the forcing of a child"
-    by_slot = {int(r[_abi.GR_SLOT]): r for r in got["harvest"][3]}
+    by_slot = {int(r[_abi.GR_SLOT]): r for r in got.harvest[3]}
     for g, game in enumerate(want):
-        e_moves = got["logs"][g]
-        t_rows = got["targets"][g] if read_targets else [np.asarray(m["target"], dtype=np.float64) for m in game["moves"]]
+        e_moves = got.logs[g]
+        t_rows = got.rows[0][g] if read_targets else [np.asarray(m["target"], dtype=np.float64) for m in game["moves"]]
         assert len(e_moves) == len(game["moves"]) == len(t_rows) >= 2, (g, len(e_moves), len(game["moves"]), len(t_rows))
         for k, (e, o, tp) in enumerate(zip(e_moves, game["moves"], t_rows)):
             where = (shape, P, root_noise, g, k)
@@ -311,7 +227,7 @@ def check_restatement(kind, shape, P, root_noise, k=K, expect_ended=True, read_t
             assert_pruning_invariants(o, A, f32)
             assert abs(tp.sum() - 1.0) <= A * np.finfo(np.float32 if f32 else np.float64).eps, where
         if game["finished"]:
-            rows = eu.samples_of(by_slot[g], got["harvest"][1])
+            rows = eu.samples_of(by_slot[g], got.harvest[1])
             assert rows.tobytes() == np.stack([np.asarray(m["target"], dtype=np.float32) for m in game["moves"]]).tobytes(), (shape, P, g)
         else:
             assert g not in by_slot
@@ -363,8 +279,8 @@ def check_off_is_the_parent(kind, shape="go5", P=4):
     prune_target = 0 gives a harvested pi equal to the logged pi of the (forced) search."""
     noise, unif, _, _ = _restated_case(shape, P, True)
     kw = _engine_kw(shape, P, True)
-    never = run_engine(kind, noise, unif, eval_batch, **kw)
-    assert all(len(t) == 0 for t in never["targets"]) and sum(len(g) for g in never["logs"]) >= 4
+    never = eu.run_injected_search(kind, noise, unif, eval_batch, rows_after_move=target_rows, **kw)
+    assert never.rows == () and sum(len(g) for g in never.logs) >= 4
 
     def used_then_off(eng):
         eng.set_forced_playouts(K)
@@ -375,24 +291,25 @@ def check_off_is_the_parent(kind, shape="go5", P=4):
             eng.round()
         eng.set_forced_playouts(0.0)
 
-    zero = run_engine(kind, noise, unif, eval_batch, setup=lambda eng: eng.set_forced_playouts(0.0), **kw)
-    off = run_engine(kind, noise, unif, eval_batch, setup=used_then_off, read_targets=False, **kw)
-    cfg0 = run_engine(kind, noise, unif, eval_batch, forced_playouts=0.0, **kw)
+    zero = eu.run_injected_search(kind, noise, unif, eval_batch, setup=lambda eng: eng.set_forced_playouts(0.0), rows_after_move=target_rows, **kw)
+    off = eu.run_injected_search(kind, noise, unif, eval_batch, setup=used_then_off, **kw)
+    cfg0 = eu.run_injected_search(kind, noise, unif, eval_batch, forced_playouts=0.0, rows_after_move=target_rows, **kw)
     for other in (zero, off, cfg0):
         assert same_run(never, other, targets=False)
-    on = run_engine(kind, noise, unif, eval_batch, forced_playouts=K, **kw)
+    on = eu.run_injected_search(kind, noise, unif, eval_batch, forced_playouts=K, rows_after_move=target_rows, **kw)
     assert not same_run(never, on, targets=False)
-    unpruned = run_engine(kind, noise, unif, eval_batch, setup=lambda eng: eng.set_forced_playouts(K, prune_target=False), **kw)
-    assert unpruned["counters"] == on["counters"]  # the same searches: pruning touches the target only
+    unpruned = eu.run_injected_search(kind, noise, unif, eval_batch, setup=lambda eng: eng.set_forced_playouts(K, prune_target=False),
+                                      rows_after_move=target_rows, **kw)
+    assert unpruned.counters == on.counters  # the same searches: pruning touches the target only
     n_rows = 0
-    for row in unpruned["harvest"][3]:
+    for row in unpruned.harvest[3]:
         g = int(row[_abi.GR_SLOT])
-        rows = eu.samples_of(row, unpruned["harvest"][1])
-        assert rows.tobytes() == np.stack([m["pi"].astype(np.float32) for m in unpruned["logs"][g]]).tobytes()
-        assert all(t.tobytes() == m["pi"].tobytes() for t, m in zip(unpruned["targets"][g], unpruned["logs"][g]))
-        assert all(a["pi"].tobytes() == b["pi"].tobytes() and a["move"] == b["move"] for a, b in zip(unpruned["logs"][g], on["logs"][g]))
+        rows = eu.samples_of(row, unpruned.harvest[1])
+        assert rows.tobytes() == np.stack([m["pi"].astype(np.float32) for m in unpruned.logs[g]]).tobytes()
+        assert all(t.tobytes() == m["pi"].tobytes() for t, m in zip(unpruned.rows[0][g], unpruned.logs[g]))
+        assert all(a["pi"].tobytes() == b["pi"].tobytes() and a["move"] == b["move"] for a, b in zip(unpruned.logs[g], on.logs[g]))
         n_rows += len(rows)
-    assert n_rows >= 4 and unpruned["harvest"][1].tobytes() != on["harvest"][1].tobytes()
+    assert n_rows >= 4 and unpruned.harvest[1].tobytes() != on.harvest[1].tobytes()
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -427,10 +344,10 @@ def check_discriminating_case(kind, sims=48):
     p0 = float(np.float64(np.float32(1.0 / A) * np.float32(0.75)) + 1.0 * 0.25)  # the noisy root prior of action 0, as the search forms it
     n_end = {}
     for k in (K, 0.0):
-        got = run_engine(kind, noise, unif, corner_eval, **(dict(kw, forced_playouts=k) if k else kw))
-        cn = got["logs"][0][0]["child_N"]
+        got = eu.run_injected_search(kind, noise, unif, corner_eval, rows_after_move=target_rows, **(dict(kw, forced_playouts=k) if k else kw))
+        cn = got.logs[0][0]["child_N"]
         want = restated_selfplay("go", 5, sims, 1, 1, 7, 1, k, True, noise=noise, eval_factory=corner_eval_func)[2][0]["moves"][0]
-        assert np.array_equal(cn, want["child_N"]) and got["logs"][0][0]["pi"].tobytes() == np.asarray(want["pi"], np.float64).tobytes()
+        assert np.array_equal(cn, want["child_N"]) and got.logs[0][0]["pi"].tobytes() == np.asarray(want["pi"], np.float64).tobytes()
         n_end[k] = (float(cn[0]), float(cn.sum()))
     n0, T = n_end[K]
     assert n0 * n0 >= K * p0 * (T - 1), (n0, T, p0)
@@ -493,10 +410,10 @@ def check_playout_cap(kind, P=1, G=12):
 def check_leaf_symmetry(kind, op=3, shape="go5", P=4):
     """The forced search under a fixed op equals the forced search around the wrapped evaluator."""
     noise, unif, _, _ = _restated_case(shape, P, True)
-    kw = _engine_kw(shape, P, True)
-    under_op = run_engine(kind, noise, unif, eval_batch, forced_playouts=K, leaf_symmetry=op, **kw)
-    wrapped = run_engine(kind, noise, unif, sc.wrapped_eval(op, SHAPES[shape]["n"]), forced_playouts=K, **kw)
-    plain = run_engine(kind, noise, unif, eval_batch, forced_playouts=K, **kw)
+    kw = dict(_engine_kw(shape, P, True), forced_playouts=K, rows_after_move=target_rows)
+    under_op = eu.run_injected_search(kind, noise, unif, eval_batch, leaf_symmetry=op, **kw)
+    wrapped = eu.run_injected_search(kind, noise, unif, sc.wrapped_eval(op, SHAPES[shape]["n"]), **kw)
+    plain = eu.run_injected_search(kind, noise, unif, eval_batch, **kw)
     assert same_run(under_op, wrapped) and not same_run(under_op, plain)
 
 
@@ -507,15 +424,13 @@ def check_batch_search(kind, game="go", n=5, P=1, budgets=(24, 9, 16, 24)):
     """BatchSearch(forced_playouts = 2) on the empty board in every slot, slots with different budgets, noise rows and warm flags, two
     moves with tree reuse: pi, child_N, root Q and target_pi of every slot are those of the restated oracle search; target_pi is None
     when off."""
-    A = n * n + (1 if game == "go" else 0)
+    A = eu.num_actions(game, n)
     G = len(budgets)
     b, dev = eu.backend(kind)
     rng = np.random.Generator(np.random.PCG64(41))
     noise = rng.dirichlet(np.full(A, 0.03), size=(2, G))
     warm = np.array([s % 2 == 0 for s in range(G)])
-    boards, hist = np.zeros((G, n, n), np.int8), np.zeros((G, 8, n, n), np.int8)
-    pos = np.zeros((G, _abi.PS_COUNT), np.int32)
-    pos[:, _abi.PS_TO_PLAY], pos[:, _abi.PS_KO] = 1, -1
+    boards, hist, pos = eu.empty_positions(n, G)
     ef = make_eval_func(A)
     off = BatchSearch(game, n, G, max(budgets), num_parallel=P, root_noise=True, binding=b, device=dev)
     assert np.all(off.load(boards, hist, pos) == _abi.SS_OK)
@@ -526,7 +441,7 @@ def check_batch_search(kind, game="go", n=5, P=1, budgets=(24, 9, 16, 24)):
     bs = BatchSearch(game, n, G, max(budgets), num_parallel=P, root_noise=True, binding=b, device=dev, forced_playouts=K)
     assert np.all(bs.load(boards, hist, pos) == _abi.SS_OK)
     assert not bs.eng.target_policies().cpu().numpy().any()  # zero before the first finished search
-    envs, trees = [make_env(game, n) for _ in range(G)], [None] * G
+    envs, trees = [eu.make_oracle_env(game, n) for _ in range(G)], [None] * G
     differs = 0
     for move in range(2):
         bs.search(ef, noise=noise[move], warm_up=warm, num_simulations=list(budgets))
@@ -579,14 +494,8 @@ def check_resident_identity_gpu():
     """BatchSearch(forced_playouts = 2) behind a DeviceEvaluator on a small 9x9 fp32-class network: the resident loop equals the host
     callback loop around the same evaluator, target_pi included, and is another search than the plain one.  (Device only.)"""
     import batch_search_checks as bc
-    from alpha_zero_amd import _lib
-    from alpha_zero_amd.core.evaluate import DeviceEvaluator
-    from alpha_zero_amd.core.network import InferenceNet
 
-    torch.manual_seed(0)
-    net = AlphaZeroNet((17, 9, 9), 82, 2, 128, 64)
-    inf = InferenceNet(net, dtype=torch.float32, binding=_lib.load()).cuda()
-    ev = DeviceEvaluator(inf)
+    inf, ev = eu.small_go9_device_evaluator()
     boards, hist, pos = bc.positions("go", 9, 8, 6)
     rows = {}
     for route, forced in (("resident", K), ("callback", K), ("plain", None)):

@@ -179,96 +179,20 @@ def restated(m, sims, c_visit=C_VISIT, c_scale=C_SCALE):
 
 def restated_selfplay(game, n, sims, P, G, seed, max_moves, m, max_steps=0, num_to_win=5, reuse=True):
     """G games of the oracle's actor under the rule: (gumbel rows, uniforms, per game the per-move records, all margins)."""
-    A = n * n + (1 if game == "go" else 0)
-    M = max_moves + 1
+    A, M = eu.num_actions(game, n), max_moves + 1
     gum = np.random.default_rng(seed).gumbel(size=(G, M, A))
     unif = np.random.default_rng(seed + 1).random((G, M, 16))
-    logs, margins = [], []
-    for gi in range(G):
-        env = fc.make_env(game, n, max_steps, num_to_win)
-        per = []
-
-        def on_move(kk, env_, move, pi, rq, cq, root):
-            per.append(dict(move=int(move), pi=np.asarray(pi), root_q=float(rq), child_q=float(cq)))
-
-        with restated(m, sims) as rec:
-            seq, _ = oactor.play_one_game(env, make_eval_func(A), num_simulations=sims, num_parallel=P, warm_up_steps=4, root_noise=True,
-                                          reuse_tree=reuse, rand_for_move=lambda kk: mcts.InjectedRand(gum[gi, kk], unif[gi, kk]),
-                                          on_move=on_move, max_moves=max_moves)
-        assert len(rec["searches"]) >= len(per)
-        for move, s in zip(per, rec["searches"]):
-            assert move["move"] == s["move"]
-            move.update(child_N=s["N"], target=s["target"], legal=s["legal"])
-        logs.append(dict(moves=per, finished=seq is not None))
-        margins += rec["margins"]
-    return gum, unif, logs, margins
+    _, _, logs, results, counted = eu.oracle_selfplay(game, n, sims, P, G, seed, max_moves, rule=lambda: restated(m, sims), noise=gum, unif=unif,
+                                                      reuse_tree=reuse, max_steps=max_steps, num_to_win=num_to_win)
+    return gum, unif, [dict(moves=per, finished=seq is not None) for per, (seq, _) in zip(logs, results)], counted["margins"]
 
 
 # ---------------------------------------------------------------------------------------------------
-# the engine under injected randomness, with the target rows and a* of every move
+# the engine under injected randomness (eu.run_injected_search), with the target rows and a* of every move
 # ---------------------------------------------------------------------------------------------------
-def run_engine(kind, noise, unif, evaluator, setup=None, read_rows=True, inject=True, on_round=None, **engine_kw):
-    """forced_checks.run_engine for this mode: after every round the target rows and a* of the slots that finished a move.
-    inject=False: a seeded engine that draws for itself (noise only gives the shape); on_round(eng, i) runs in front of round i.
-    Returns dict(logs, targets, astar, harvest, counters)."""
-    b, dev = eu.backend(kind)
-    G, M, A = noise.shape
-    eng = Engine(b, EngineConfig(num_games=G, inject_random=inject, inject_moves=M if inject else 0, stop_at_game_end=True, log_moves=True,
-                                 log_capacity=M, **engine_kw), device=dev)
-    if setup is not None:
-        setup(eng)
-    if inject:
-        eng.set_injection(noise, unif)
-    eng.reset_games()
-    eng.counters(reset=True)
-    targets, astar = [[] for _ in range(G)], [[] for _ in range(G)]
-    seen = np.zeros(G, dtype=np.int64)
-    eng.select()
-    for i in range(200000):
-        if on_round is not None:
-            on_round(eng, i)
-        valid = eng.valid.cpu().numpy().astype(bool)
-        st, _ = eng.status()
-        if eng.gumbel and read_rows:
-            tp, mv = eng.target_policies().cpu().numpy(), eng.gumbel_moves().cpu().numpy()
-            ply = np.minimum(st[:, _abi.STC_PLY], M)
-            assert np.all(ply - seen <= 1)
-            for g in np.flatnonzero(ply > seen):
-                targets[g].append(tp[g].copy())
-                astar[g].append(int(mv[g]))
-            seen = ply.astype(np.int64)
-        if not valid.any() and np.all(st[:, _abi.STC_STATUS] == _abi.ST_IDLE):
-            break
-        pri, val = np.zeros((eng.rows, A), dtype=np.float32), np.zeros(eng.rows, dtype=np.float32)
-        rows = np.flatnonzero(valid)
-        if len(rows):
-            pri[rows], val[rows] = evaluator(eu.decode_features(eng)[rows], A)
-        eng.priors.copy_(torch.from_numpy(pri))
-        eng.values.copy_(torch.from_numpy(val))
-        eng.round()
-    else:
-        raise AssertionError("the games did not finish")
-    logs = []
-    for g in range(G):
-        per = []
-        for k in range(int(min(st[g, _abi.STC_PLY], M))):
-            pi, cn, q = eng.get_search(g, k)
-            per.append(dict(pi=pi, child_N=cn, root_q=q[_abi.SQ_ROOT_Q], child_q=q[_abi.SQ_CHILD_Q], move=int(q[_abi.SQ_MOVE])))
-        logs.append(per)
-    parts, base = [], 0
-    while True:
-        states, pi, z, games = eng.harvest()
-        if len(games) == 0:
-            break
-        games = games.copy()
-        games[:, _abi.GR_START] += base
-        base += len(z)
-        parts.append((states.cpu().numpy().copy(), pi.cpu().numpy().copy(), z.cpu().numpy().copy(), games))
-    hv = (tuple(np.concatenate([p[i] for p in parts]) for i in range(4)) if parts else
-          (np.zeros((0, eng.planes, eng.N, eng.N), np.int8), np.zeros((0, A), np.float32), np.zeros(0, np.float32), np.zeros((0, _abi.GR_COUNT), np.int32)))
-    counters = eng.counters()
-    eng.close()
-    return dict(logs=logs, targets=targets, astar=astar, harvest=hv, counters=counters)
+def gumbel_rows(eng):
+    """rows_after_move of eu.run_injected_search: the slots' target rows and a* (SearchRun.rows[0], [1]), nothing while the mode was never on."""
+    return (eng.target_policies().cpu().numpy(), eng.gumbel_moves().cpu().numpy()) if eng.gumbel else None
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -286,17 +210,17 @@ CASES = [("go5", 1, 4, True), ("go5", 4, 4, True), ("go5", 1, 16, False), ("go5"
          ("go9", 4, 200, False), ("gomoku7", 1, 4, True), ("gomoku7", 4, 16, True), ("gomoku7", 1, 100, False)]
 
 
+_selfplay_args, _shape_kw = eu.shape_table(SHAPES, root_noise=True)
+
+
 @functools.lru_cache(maxsize=None)
 def _restated_case(shape, P, m, reuse):
-    s = SHAPES[shape]
-    return restated_selfplay(s["game"], s["n"], s["sims"], P, s["G"], s["seed"], s["max_moves"], m, max_steps=s.get("max_steps", 0),
-                             num_to_win=s.get("num_to_win", 5), reuse=reuse)
+    args, kw = _selfplay_args(shape, P)
+    return restated_selfplay(*args, m, reuse=reuse, **kw)
 
 
 def _engine_kw(shape, P, reuse=True):
-    s = SHAPES[shape]
-    return dict(game=s["game"], board_size=s["n"], num_parallel=P, num_simulations=s["sims"], max_plies=s["max_moves"], warm_up_steps=4,
-                max_steps=s.get("max_steps", 0), num_to_win=s.get("num_to_win", 5), root_noise=True, force_resign_disabled=1, reuse_tree=reuse)
+    return _shape_kw(shape, P, reuse_tree=reuse)
 
 
 def check_margins():
@@ -314,11 +238,11 @@ def check_restatement(kind, shape, P, m, reuse):
     for bit; the committed move and a*; pi' to PI_TOL; the harvested pi rows against float32(pi')."""
     gum, unif, want, margins = _restated_case(shape, P, m, reuse)
     assert min(margins) >= MIN_MARGIN
-    got = run_engine(kind, gum, unif, eval_batch, gumbel=m, **_engine_kw(shape, P, reuse))
+    got = eu.run_injected_search(kind, gum, unif, eval_batch, gumbel=m, rows_after_move=gumbel_rows, **_engine_kw(shape, P, reuse))
     A = gum.shape[2]
-    by_slot = {int(r[_abi.GR_SLOT]): r for r in got["harvest"][3]}
+    by_slot = {int(r[_abi.GR_SLOT]): r for r in got.harvest[3]}
     for g, game in enumerate(want):
-        e_moves, t_rows, stars = got["logs"][g], got["targets"][g], got["astar"][g]
+        e_moves, t_rows, stars = got.logs[g], got.rows[0][g], got.rows[1][g]
         assert len(e_moves) == len(game["moves"]) == len(t_rows) == len(stars) >= 2, (g, len(e_moves), len(game["moves"]), len(t_rows))
         for k, (e, o, tp, a_star) in enumerate(zip(e_moves, game["moves"], t_rows, stars)):
             where = (shape, P, m, reuse, g, k)
@@ -330,7 +254,7 @@ def check_restatement(kind, shape, P, m, reuse):
             assert tp.dtype == np.float64 and np.abs(tp - o["target"]).max() <= PI_TOL, where
             assert abs(tp.sum() - 1.0) <= 1e-12 and not tp[o["legal"] != 1].any(), where
         if game["finished"]:
-            rows = eu.samples_of(by_slot[g], got["harvest"][1])
+            rows = eu.samples_of(by_slot[g], got.harvest[1])
             assert np.abs(rows.astype(np.float64) - np.stack([m_["target"] for m_ in game["moves"]])).max() <= F32_TOL, (shape, P, g)
         else:
             assert g not in by_slot
@@ -365,7 +289,7 @@ def check_schedule(kind):
         gum, unif, want, margins = _restated_single(game, n, sims, m, seed)
         assert min(margins) >= MIN_MARGIN
         kw = dict(game=game, board_size=n, num_parallel=1, num_simulations=sims, max_plies=1, warm_up_steps=4, force_resign_disabled=1)
-        cn = run_engine(kind, gum, unif, eval_batch, gumbel=m, **kw)["logs"][0][0]["child_N"]
+        cn = eu.run_injected_search(kind, gum, unif, eval_batch, gumbel=m, rows_after_move=gumbel_rows, **kw).logs[0][0]["child_N"]
         assert np.array_equal(cn, want), (game, n, sims, m)
         got.append(cn)
     assert sorted(got[0][got[0] > 0].tolist()) == [2, 2, 6, 6], got[0]
@@ -380,13 +304,14 @@ def check_off_is_off(kind, shape="go5", P=4):
     """m = 0, given to the setter or to the config, and the mode used and then turned off, give the logs, harvests and counters of an
     engine that never heard of it, byte for byte; on, it is another run."""
     s = SHAPES[shape]
-    A = 26
+    A = eu.num_actions(s["game"], s["n"])
     rng = np.random.Generator(np.random.PCG64(s["seed"]))
     noise = rng.dirichlet(np.full(A, 0.03), size=(s["G"], s["max_moves"] + 1))
     unif = rng.random((s["G"], s["max_moves"] + 1, 16))
     kw = _engine_kw(shape, P)
-    never = run_engine(kind, noise, unif, eval_batch, **kw)
-    assert sum(len(g) for g in never["logs"]) >= 4 and len(never["harvest"][2]) >= 4
+    run = functools.partial(eu.run_injected_search, kind, noise, unif, eval_batch, **kw)
+    never = run(rows_after_move=gumbel_rows)
+    assert sum(len(g) for g in never.logs) >= 4 and len(never.harvest[2]) >= 4
 
     def used_then_off(eng):
         eng.set_gumbel(4)
@@ -397,13 +322,13 @@ def check_off_is_off(kind, shape="go5", P=4):
             eng.round()
         eng.set_gumbel(0)
 
-    zero = run_engine(kind, noise, unif, eval_batch, setup=lambda eng: eng.set_gumbel(0), **kw)
-    none = run_engine(kind, noise, unif, eval_batch, setup=lambda eng: eng.set_gumbel(None), **kw)
-    cfg0 = run_engine(kind, noise, unif, eval_batch, gumbel=0, **kw)
-    off = run_engine(kind, noise, unif, eval_batch, setup=used_then_off, read_rows=False, **kw)
+    zero = run(setup=lambda eng: eng.set_gumbel(0), rows_after_move=gumbel_rows)
+    none = run(setup=lambda eng: eng.set_gumbel(None), rows_after_move=gumbel_rows)
+    cfg0 = run(gumbel=0, rows_after_move=gumbel_rows)
+    off = run(setup=used_then_off)
     for other in (zero, none, cfg0, off):
         assert fc.same_run(never, other, targets=False)
-    on = run_engine(kind, noise, unif, eval_batch, gumbel=4, **kw)
+    on = run(gumbel=4, rows_after_move=gumbel_rows)
     assert not fc.same_run(never, on, targets=False)
 
 
@@ -463,13 +388,6 @@ def check_refusals(kind):
 # ---------------------------------------------------------------------------------------------------
 # 4. surfaces
 # ---------------------------------------------------------------------------------------------------
-def _empty_boards(n, G):
-    boards, hist = np.zeros((G, n, n), np.int8), np.zeros((G, 8, n, n), np.int8)
-    pos = np.zeros((G, _abi.PS_COUNT), np.int32)
-    pos[:, _abi.PS_TO_PLAY], pos[:, _abi.PS_KO] = 1, -1
-    return boards, hist, pos
-
-
 # per move; the last: at or below the visits a kept sub-tree holds unless its root has its one visit only (then one simulation is made),
 # so that a visited child always exists
 BATCH_BUDGETS = ((24, 16, 20, 32), (24, 16, 20, 32), (2, 2, 2, 2))
@@ -479,12 +397,12 @@ BATCH_BUDGETS = ((24, 16, 20, 32), (24, 16, 20, 32), (2, 2, 2, 2))
 def _restated_batch(game, n, P, m):
     """The restated oracle searches of check_batch_search, slot by slot over the moves of BATCH_BUDGETS with tree reuse:
     (gumbel rows [move, slot, A], warm flags, per move per slot dict(move, pi, root_q, N, target, sims), all margins)."""
-    A = n * n + (1 if game == "go" else 0)
+    A = eu.num_actions(game, n)
     G = len(BATCH_BUDGETS[0])
     gum = np.random.default_rng(71).gumbel(size=(len(BATCH_BUDGETS), G, A))
     warm = np.array([s % 2 == 0 for s in range(G)])
     ef = make_eval_func(A)
-    envs, trees = [fc.make_env(game, n) for _ in range(G)], [None] * G
+    envs, trees = [eu.make_oracle_env(game, n) for _ in range(G)], [None] * G
     out, margins = [], []
     for move, budgets in enumerate(BATCH_BUDGETS):
         row = []
@@ -528,7 +446,7 @@ def check_batch_search(kind, game="go", n=5, P=1, m=16):
     G = len(BATCH_BUDGETS[0])
     top = max(max(b) for b in BATCH_BUDGETS)
     b, dev = eu.backend(kind)
-    boards, hist, pos = _empty_boards(n, G)
+    boards, hist, pos = eu.empty_positions(n, G)
     ef = make_eval_func(A)
     off = BatchSearch(game, n, G, top, num_parallel=P, binding=b, device=dev)
     assert np.all(off.load(boards, hist, pos) == _abi.SS_OK)
@@ -655,13 +573,13 @@ def check_switch_in_flight(kind, shape="go5", P=4, m=4):
             eng.set_gumbel(0)
             eng.set_forced_playouts(2.0)
 
-    got = run_engine(kind, gum, unif, eval_batch, gumbel=m, on_round=switch, **_engine_kw(shape, P))
+    got = eu.run_injected_search(kind, gum, unif, eval_batch, gumbel=m, on_round=switch, rows_after_move=gumbel_rows, **_engine_kw(shape, P))
     for g, game in enumerate(want):
-        e, o = got["logs"][g][0], game["moves"][0]
-        assert np.array_equal(e["child_N"], o["child_N"]) and e["move"] == o["move"] == got["astar"][g][0], g
-        assert np.abs(got["targets"][g][0] - o["target"]).max() <= PI_TOL, g
-        assert len(got["logs"][g]) == SHAPES[shape]["max_moves"] and all(m_["child_N"].sum() > 0 for m_ in got["logs"][g]), g
-    assert len(got["harvest"][3]) == len(want)
+        e, o = got.logs[g][0], game["moves"][0]
+        assert np.array_equal(e["child_N"], o["child_N"]) and e["move"] == o["move"] == got.rows[1][g][0], g
+        assert np.abs(got.rows[0][g][0] - o["target"]).max() <= PI_TOL, g
+        assert len(got.logs[g]) == SHAPES[shape]["max_moves"] and all(m_["child_N"].sum() > 0 for m_ in got.logs[g]), g
+    assert len(got.harvest[3]) == len(want)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -681,17 +599,17 @@ def check_search_draws_are_the_probed_rows(kind, seed=77, sims=17, m=4):
 
     kw = dict(game="go", board_size=5, num_parallel=1, num_simulations=sims, max_plies=2, warm_up_steps=4, force_resign_disabled=1,
               max_steps=6, seed=seed)
-    got = run_engine(kind, np.zeros((1, 3, 26)), None, eval_batch, gumbel=m, inject=False, setup=probe, **kw)
+    got = eu.run_injected_search(kind, np.zeros((1, 3, 26)), None, eval_batch, gumbel=m, inject=False, setup=probe, rows_after_move=gumbel_rows, **kw)
     gum = rows["g"]
     assert np.isfinite(gum).all() and np.unique(gum).size == gum.size
-    env, per = fc.make_env("go", 5, 6), []
+    env, per = eu.make_oracle_env("go", 5, 6), []
     with restated(m, sims) as rec:
         oactor.play_one_game(env, make_eval_func(26), num_simulations=sims, num_parallel=1, warm_up_steps=4, root_noise=True,
                              rand_for_move=lambda kk: mcts.InjectedRand(gum[0, kk], []), max_moves=2,
                              on_move=lambda kk, e_, mv, pi, rq, cq, root: per.append(int(mv)))
-    assert min(rec["margins"]) >= MIN_MARGIN and len(per) == 2 == len(got["logs"][0])
+    assert min(rec["margins"]) >= MIN_MARGIN and len(per) == 2 == len(got.logs[0])
     for k in range(2):
         srec = rec["searches"][k]
-        assert np.array_equal(got["logs"][0][k]["child_N"], srec["N"]), k
-        assert got["logs"][0][k]["move"] == per[k] == got["astar"][0][k], k
-        assert np.abs(got["targets"][0][k] - srec["target"]).max() <= PI_TOL, k
+        assert np.array_equal(got.logs[0][k]["child_N"], srec["N"]), k
+        assert got.logs[0][k]["move"] == per[k] == got.rows[1][0][k], k
+        assert np.abs(got.rows[0][0][k] - srec["target"]).max() <= PI_TOL, k

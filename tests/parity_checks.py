@@ -49,7 +49,7 @@ def check_mcts_golden(kind, name, feature_dtype=_abi.FEAT_I8, prefix="mcts_"):
     <= 1e-6.  Returns (engine counters, number of finished games)."""
     G = golden_mcts.MctsGolden(name, prefix)
     g, cfg = G.g, G.cfg
-    logs, (states, pis, zs, games), n_evals, counters = eu.run_golden_selfplay(kind, G, eval_batch, feature_dtype)
+    logs, (states, pis, zs, games), n_evals, counters, _ = eu.run_golden_selfplay(kind, G, eval_batch, feature_dtype)
     for gi in range(cfg["games"]):
         ix = G.moves_of_game(gi)
         for k, i in enumerate(ix):

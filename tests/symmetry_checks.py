@@ -95,8 +95,7 @@ OTHER_DTYPES = (_abi.FEAT_F32, _abi.FEAT_BF16, _abi.FEAT_F16, _abi.FEAT_F16_TILE
 
 def _randomness(shape):
     s = SHAPES[shape]
-    n = s["kw"]["board_size"]
-    A = n * n + (1 if s["kw"]["game"] == "go" else 0)
+    A = eu.num_actions(s["kw"]["game"], s["kw"]["board_size"])
     rng = np.random.Generator(np.random.PCG64(s["seed"]))
     return rng.dirichlet(np.full(A, 0.03), size=(s["G"], s["M"])), rng.random((s["G"], s["M"], 16))
 
@@ -123,8 +122,9 @@ def _plain_run(kind, shape, op):
 
 
 def assert_same_outputs(a, b, where=None):
-    """Bit for bit: logs (pi, child_N, root_q, child_q, move), harvest (states, pi, z, game rows), evaluations per ply, counters."""
-    (la, ha, na, ca), (lb, hb, nb, cb) = a, b
+    """Bit for bit, two SearchRuns: logs (pi, child_N, root_q, child_q, move), harvest (states, pi, z, game rows), evaluations per ply,
+    counters."""
+    (la, ha, na, ca), (lb, hb, nb, cb) = a[:4], b[:4]
     assert len(la) == len(lb)
     for gi, (ga, gb) in enumerate(zip(la, lb)):
         assert len(ga) == len(gb) > 0, (where, gi, len(ga), len(gb))
@@ -142,7 +142,7 @@ def check_fixed_op(kind, shape, op, dtypes=None):
     """leaf_symmetry = op around E against the mode off around the wrapped evaluator, for every feature layout of the shape; the
     decoded features of every round are D_op of the plain run's."""
     plain, plain_feats = _plain_run(kind, shape, op)
-    assert sum(len(g) for g in plain[0]) >= 2 and plain[3]["leaves"] > 0
+    assert sum(len(g) for g in plain.logs) >= 2 and plain.counters["leaves"] > 0
     for dt in dtypes or SHAPE_DTYPES[shape]:
         got, feats = _run(kind, shape, eval_batch, feature_dtype=dt, leaf_symmetry=op)
         assert_same_outputs(got, plain, (shape, op, dt))
@@ -151,7 +151,7 @@ def check_fixed_op(kind, shape, op, dtypes=None):
             assert np.array_equal(f, d_planes(g, op)), (shape, op, dt, rnd)
     if op != 0:  # the comparison can fail: the plain run around E itself is another search
         base = _plain_run(kind, shape, None)[0]
-        assert any(x["child_N"].tobytes() != y["child_N"].tobytes() for ga, gb in zip(plain[0], base[0]) for x, y in zip(ga, gb))
+        assert any(x["child_N"].tobytes() != y["child_N"].tobytes() for ga, gb in zip(plain.logs, base.logs) for x, y in zip(ga, gb))
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -322,21 +322,14 @@ def check_identity_and_off(kind, shape="go5"):
                       eng.counters())
         eng.close()
     assert logs[True] == logs[False] and all(len(g) > 0 for g in logs[False][0])
-    assert [[x[0] for x in g] for g in logs[False][0]] == [[m["pi"].tobytes() for m in g] for g in plain[0]]
+    assert [[x[0] for x in g] for g in logs[False][0]] == [[m["pi"].tobytes() for m in g] for g in plain.logs]
 
 
 def check_resident_identity_gpu():
     """BatchSearch behind a DeviceEvaluator on a small 9x9 fp32-class (split-precision) network, the resident loop: op 0 is the plain
     search, bit for bit.  (Device only: the evaluator's kernels.)"""
-    from alpha_zero_amd import _lib
-    from alpha_zero_amd.core.evaluate import DeviceEvaluator
-    from alpha_zero_amd.core.network import InferenceNet
-
-    torch.manual_seed(0)
-    net = AlphaZeroNet((17, 9, 9), 82, 2, 128, 64)
-    inf = InferenceNet(net, dtype=torch.float32, binding=_lib.load()).cuda()
+    inf, ev = eu.small_go9_device_evaluator()
     assert "split-precision" in inf.evaluator_path(9, "cuda")
-    ev = DeviceEvaluator(inf)
     boards, hist, pos = bc.positions("go", 9, 8, 6)
     rows = {}
     for mode in (None, 0, 3):
@@ -361,7 +354,7 @@ def _search_rows(bs, ef):
 def check_batch_search(kind, game="go", n=5, P=1):
     """BatchSearch(leaf_symmetry=k) with a host eval_func equals the plain BatchSearch with the wrapped function, on 8 positions and
     32 simulations; "random" runs and differs from none of the contracts (pi sums to 1)."""
-    A = n * n + (1 if game == "go" else 0)
+    A = eu.num_actions(game, n)
     b, dev = eu.backend(kind)
     boards, hist, pos = bc.positions(game, n, 8, 8)
     ef = make_eval_func(A)

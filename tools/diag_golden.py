@@ -15,7 +15,7 @@ from synth_eval import eval_batch  # noqa: E402
 
 kind, name = sys.argv[1], sys.argv[2]
 G = golden_mcts.MctsGolden(name)
-logs, (states, pis, zs, games), nev, cnt = eu.run_golden_selfplay(kind, G, eval_batch)
+logs, (states, pis, zs, games), nev, cnt, _ = eu.run_golden_selfplay(kind, G, eval_batch)
 print("counters", {k: v for k, v in cnt.items() if v})
 print("games rows:\n", games)
 for gi in range(G.cfg["games"]):
