@@ -57,6 +57,7 @@ class EngineConfig:
     leaf_symmetry: object = None     # the opt-in search rules, as SearchOptions.of takes them: None | "random" | 0..7,
     forced_playouts: object = None   # None | k >= 0,
     gumbel: object = None            # None | m | (m, c_visit, c_scale)
+    aux_targets: bool = False        # auxiliary training targets per sample (Engine.set_aux_targets; harvest(with_aux=True))
 
 
 def leaf_symmetry_mode(mode):
@@ -221,6 +222,10 @@ class Engine:
             self.set_gumbel(opt.gumbel)
         if opt.playout_cap is not None:
             self.set_playout_cap(*opt.playout_cap)  # before the first root: the first move of every game draws its class too
+        self.aux_targets = False  # has been on at least once, so the staging rows exist (harvest(with_aux=True))
+        self._harvest_aux_bufs = None
+        if cfg.aux_targets:
+            self.set_aux_targets(True)  # before the first move is recorded
 
     # -- plumbing ---------------------------------------------------------------------------------
     def _ck(self, rc, what):
@@ -462,6 +467,15 @@ class Engine:
         self._gumbel_m = m
         self.gumbel = self.gumbel or m > 0
 
+    def set_aux_targets(self, on=True):
+        """Auxiliary training targets per sample (azsp_set_aux_targets; KataGo, Wu 2019, 4.1; the reference actor has none): the
+        engine stages the root value of every recorded move and the ownership of every point in the game's final position, and
+        `harvest(with_aux=True)` hands out ownership, score and root value in the mover's perspective.  The batched actor only
+        (an AzspError on a stop_after_move engine).  Holds for the moves recorded and the games finished from now on; what was staged
+        with it off reads 0.  Samples, game rows, logs and searches are untouched."""
+        self._ck(self.b.dll.azsp_set_aux_targets(self.h, int(bool(on))), "azsp_set_aux_targets")
+        self.aux_targets = self.aux_targets or bool(on)
+
     def gumbel_moves(self):
         """int32[G] on the engine's device: a* of every slot's last finished Gumbel root search, -1 before the first and after a fast move
         (azsp_read_gumbel_moves).  Only once the mode has been enabled.  Nothing is synchronised."""
@@ -478,10 +492,13 @@ class Engine:
         return out
 
     # -- samples ----------------------------------------------------------------------------------------
-    def harvest(self, sample_capacity=None, max_games=None, with_moves=False, with_class=False):
+    def harvest(self, sample_capacity=None, max_games=None, with_moves=False, with_class=False, with_aux=False):
         """Returns (states int8[n,2K+1,N,N], pi float32[n,A], z float32[n], games int32[k,GR_COUNT]) -- device tensors + host meta;
         with_moves=True appends moves int16[n] (the move played from every sample's position, -1 = resigned); with_class=True then
         appends full uint8[n] (1 = the sample's move was a full search, 0 = a fast move of the playout cap; all 1 with the cap off).
+        with_aux=True (only once aux targets have been enabled) then appends ownership int8[n,N,N] (+1 the mover's point, -1 the
+        opponent's, 0 nobody's, in the game's final position), score float32[n] (Go: the final area score with komi seen by the mover;
+        Gomoku: z) and root_q float32[n] (the root value of the sample's search): include/azsp.h, azsp_set_aux_targets.
         The per-game extras of the same call (azsp_harvest_extra) are left in `self.last_extra` int32[k,GX_COUNT].
         ALIASING: the device tensors are views of buffers this engine re-uses -- the NEXT harvest() overwrites them in place.
         Consume (or .clone()) them before harvesting again; SelfPlayActor.harvest_tensors(clone=True) does the latter."""
@@ -496,6 +513,13 @@ class Engine:
         st, pi, z, mvbuf, clbuf = self._harvest_bufs
         self._ck(self.b.dll.azsp_harvest_moves(self.h, mvbuf.data_ptr() if with_moves else None), "azsp_harvest_moves")
         self._ck(self.b.dll.azsp_harvest_search_class(self.h, clbuf.data_ptr() if with_class else None), "azsp_harvest_search_class")
+        if with_aux or self._harvest_aux_bufs is not None:  # (an engine that never asked for them makes no call: its harvest is what it was)
+            if with_aux and (self._harvest_aux_bufs is None or self._harvest_aux_bufs[0].shape[0] < st.shape[0]):
+                self._harvest_aux_bufs = (torch.empty((st.shape[0], self.N, self.N), dtype=torch.int8, device=self.device),
+                                          torch.empty((st.shape[0],), dtype=torch.float32, device=self.device),
+                                          torch.empty((st.shape[0],), dtype=torch.float32, device=self.device))
+            self._ck(self.b.dll.azsp_harvest_aux(self.h, *([t.data_ptr() for t in self._harvest_aux_bufs] if with_aux else [None] * 3)),
+                     "azsp_harvest_aux")
         games = np.zeros((mg, _abi.GR_COUNT), dtype=np.int32)
         extra = np.zeros((mg, _abi.GX_COUNT), dtype=np.int32)
         self._ck(self.b.dll.azsp_harvest_extra(self.h, extra.ctypes.data), "azsp_harvest_extra")
@@ -510,6 +534,8 @@ class Engine:
             out += (mvbuf[:n],)
         if with_class:
             out += (clbuf[:n],)
+        if with_aux:
+            out += tuple(t[:n] for t in self._harvest_aux_bufs)
         return out
 
     def counters(self, reset=False):

@@ -3,7 +3,7 @@
 `game_stats_from_row` rebuilds the per-game `stats` dict of play_and_record_one_game
 (pipeline.py:367-380) from the game row (include/azsp.h AZSP_GR_*, mirrored as _abi.GR_*) the engine emits at harvest time.
 """
-from typing import Any, Dict
+from typing import Any, Dict, NamedTuple
 
 import numpy as np
 
@@ -96,6 +96,13 @@ class ClampWindow:
         return m
 
 
+class HarvestAux(NamedTuple):
+    """The auxiliary targets of one harvest (SelfPlayActor.last_harvest_aux), row for row with its states: Engine.harvest(with_aux=True)."""
+    ownership: torch.Tensor  # int8[n, N, N]  +1 the mover's point, -1 the opponent's, 0 nobody's, in the game's final position
+    score: torch.Tensor      # float32[n]     Go: final area score with komi, seen by the mover; Gomoku: z
+    root_q: torch.Tensor     # float32[n]     root value of the sample's search
+
+
 class SelfPlayActor:
     """G concurrent self-play games on one GPU: replaces G `run_selfplay_actor_loop` processes
     (pipeline.py:166-286).  One round = engine kernel (expand/backup of the previous leaf batch, end-of-move
@@ -107,7 +114,7 @@ class SelfPlayActor:
                  resign_threshold=-1.0, komi=7.5, num_to_win=5, seed=1, rank=0, device="cuda", net_dtype=torch.float32,
                  use_graph=True, training_steps=0, binding=None, root_noise=True, deterministic=False, tiled_features=None, engine_kw=None,
                  use_split_evaluator=True, auto_widen=None, num_stack=8, split_any_board=False, playout_cap=None,
-                 leaf_symmetry=None, forced_playouts=None, prune_policy_target=True, gumbel=None):
+                 leaf_symmetry=None, forced_playouts=None, prune_policy_target=True, gumbel=None, aux_targets=False):
         """net_dtype: precision class of the leaf evaluator.  The default is the REFERENCE'S: fp32 (pipeline.py:91-123 evaluates in fp32,
         no autocast anywhere) -- on the hand-written split-precision kernels (hi + lo f16 pairs, three MFMA products, fp32 accumulation:
         include/azsp.h azsp_conv3x3_split) for 9x9 x {128, 64} and 13x13 Gomoku x 64 networks, on library fp32 convolutions (announced
@@ -126,7 +133,10 @@ class SelfPlayActor:
         the network's input channels.
         playout_cap, leaf_symmetry, forced_playouts, prune_policy_target, gumbel: the opt-in search rules, SearchOptions.of.  Under a
         playout cap every move is recorded; `harvest()` hands the learner the full-search samples only, `harvest_tensors()` leaves the
-        flags in `last_harvest_full`."""
+        flags in `last_harvest_full`.
+        aux_targets: True = every sample carries the auxiliary training targets (Engine.set_aux_targets: ownership of the final position,
+        final score, root value of its search, all in the mover's perspective); `harvest_tensors()` leaves them in `last_harvest_aux`.
+        Off by default; not with a drop-in engine (engine_kw stop_after_move: ValueError), which records no samples."""
         opt = SearchOptions.of(leaf_symmetry, forced_playouts, prune_policy_target, gumbel, playout_cap, num_simulations)  # ValueError before anything is built
         from .. import _lib
 
@@ -169,8 +179,13 @@ class SelfPlayActor:
             if not hasattr(self.cfg, k):
                 raise TypeError(f"unknown engine option {k}")
             setattr(self.cfg, k, v)
+        self.aux_targets = bool(aux_targets) or bool(self.cfg.aux_targets)
+        if self.aux_targets and self.cfg.stop_after_move:
+            raise ValueError("aux_targets needs the batched actor: a drop-in engine (stop_after_move) records no samples")
+        self.cfg.aux_targets = self.aux_targets
         self.engine = Engine(self.binding, self.cfg, device=self.device, prune_policy_target=self.prune_policy_target, playout_cap=self.playout_cap)
         self.last_harvest_full = torch.zeros(0, dtype=torch.bool, device=self.device)
+        self.last_harvest_aux = None  # HarvestAux of the last harvest_tensors() (aux_targets=True only)
         self.engine.reset_games()
         self._graph = None
         self.rounds = 0
@@ -270,8 +285,12 @@ class SelfPlayActor:
     def harvest_tensors(self, clone=False):
         """(states, pi, z, games) of the finished games as device tensors.  The tensors are views of buffers the engine re-uses: the
         next harvest overwrites them in place.  clone=True returns private copies (for consumers that keep them across harvests,
-        e.g. an asynchronous learner or a replay insert on another stream)."""
-        st, pi, z, games, full = self.engine.harvest(with_class=True)
+        e.g. an asynchronous learner or a replay insert on another stream).  With aux_targets the auxiliary targets of the same rows
+        are left in `last_harvest_aux` (ownership int8[n,N,N], score float32[n], root_q float32[n]; views or clones like the rest)."""
+        got = self.engine.harvest(with_class=True, with_aux=self.aux_targets)
+        st, pi, z, games, full = got[:5]
+        if self.aux_targets:
+            self.last_harvest_aux = HarvestAux(*(t.clone() if clone else t for t in got[5:]))
         self._check_evaluator_range()
         self.last_harvest_clamped = self.clamp_window.mask(games[:, _abi.GR_UID]) if len(games) else np.zeros(0, dtype=bool)
         self.clamped_games += int(self.last_harvest_clamped.sum())

@@ -22,9 +22,13 @@ class DeviceReplay:
     lives: harvested games go from the engine's output tensors into the ring device-to-device (`add_harvest`), and
     `sample_device` returns the batch as device tensors, already transformed by one dihedral op and cast for the network
     (core/pipeline.py:636-643), from one gather kernel (`azsp_replay_gather`) -- no host round trip per batch.
-    `add_game` / `sample` / `get_state` / `set_state` keep the reference's host-side signatures."""
+    `add_game` / `sample` / `get_state` / `set_state` keep the reference's host-side signatures.
+    aux_targets=True (no counterpart in the reference: opt-in) adds three rings for the auxiliary targets of `Engine.harvest(with_aux=True)`
+    -- ownership int8[capacity, N, N], score and root_q float32[capacity] -- written with the samples (`aux=`) and gathered by
+    `sample_device(with_aux=True)` in the same launch, the ownership under the same dihedral op as the state planes."""
 
-    def __init__(self, capacity, random_state, board_size, num_actions, channels=17, device="cuda", binding=None, pi_dtype=np.float64):
+    def __init__(self, capacity, random_state, board_size, num_actions, channels=17, device="cuda", binding=None, pi_dtype=np.float64,
+                 aux_targets=False):
         import torch
 
         if capacity <= 0:
@@ -42,17 +46,30 @@ class DeviceReplay:
         self.states = torch.zeros((capacity, channels, board_size, board_size), dtype=torch.int8, device=self.device)
         self.pi = torch.zeros((capacity, num_actions), dtype=torch.float32, device=self.device)
         self.z = torch.zeros((capacity,), dtype=torch.float32, device=self.device)
+        self.aux_targets = bool(aux_targets)
+        if self.aux_targets:
+            self.ownership = torch.zeros((capacity, board_size, board_size), dtype=torch.int8, device=self.device)
+            self.score = torch.zeros((capacity,), dtype=torch.float32, device=self.device)
+            self.root_q = torch.zeros((capacity,), dtype=torch.float32, device=self.device)
         self.num_games_added = 0
         self.num_samples_added = 0
 
     # -- writes ------------------------------------------------------------------------------------------------------
-    def add_samples(self, states, pi, z, num_games=1):
+    def _check_aux(self, aux, n):
+        """`aux` as the writes take it: (ownership, score, root_q) with one row per sample, required exactly when the replay has the rings."""
+        if self.aux_targets != (aux is not None):
+            raise ValueError("aux=(ownership, score, root_q) is required by a replay built with aux_targets=True and refused by one without")
+        if aux is not None and (len(aux) != 3 or any(int(t.shape[0]) != n for t in aux)):
+            raise ValueError(f"`aux` must be (ownership, score, root_q) with one row per sample ({n})")
+
+    def add_samples(self, states, pi, z, num_games=1, aux=None):
         """Appends samples in order (device or host tensors): the ring positions the reference's per-transition loop
         would have written (:55-68).  More samples than the capacity keep only the last `capacity` (the earlier ones
-        would have been overwritten by the same call)."""
+        would have been overwritten by the same call).  aux: (ownership, score, root_q) of the same rows, with aux_targets."""
         import torch
 
         n = int(z.shape[0])
+        self._check_aux(aux, n)
         if n:
             states = torch.as_tensor(states).to(self.device, torch.int8)
             pi = torch.as_tensor(pi).to(self.device, torch.float32)
@@ -63,13 +80,17 @@ class DeviceReplay:
             self.states.index_copy_(0, pos, states[skip:])
             self.pi.index_copy_(0, pos, pi[skip:])
             self.z.index_copy_(0, pos, z[skip:])
+            if aux is not None:
+                for ring, t in zip((self.ownership, self.score, self.root_q), aux):
+                    ring.index_copy_(0, pos, torch.as_tensor(t).to(self.device, ring.dtype).reshape((n,) + ring.shape[1:])[skip:])
             self.num_samples_added += n
         self.num_games_added += num_games
 
-    def add_harvest(self, states, pi, z, games, keep=None):
+    def add_harvest(self, states, pi, z, games, keep=None, aux=None):
         """Everything `SelfPlayActor.harvest_tensors()` returned: finished games, concatenated in harvest order.  keep: an optional
         bool per sample (e.g. the actor's `last_harvest_full` under a playout cap): only those rows are stored, in order; the games
-        count as before."""
+        count as before.  aux: the actor's `last_harvest_aux` of the same harvest (with aux_targets), filtered by `keep` like the samples."""
+        self._check_aux(aux, int(z.shape[0]))
         if keep is not None:
             import torch
 
@@ -77,7 +98,9 @@ class DeviceReplay:
             if k.shape[0] != int(z.shape[0]):
                 raise ValueError(f"`keep` must hold one flag per sample ({int(z.shape[0])}), got {k.shape[0]}")
             states, pi, z = (torch.as_tensor(t)[k.to(torch.as_tensor(t).device)] for t in (states, pi, z))
-        self.add_samples(states, pi, z, num_games=len(games))
+            if aux is not None:
+                aux = tuple(torch.as_tensor(t)[k.to(torch.as_tensor(t).device)] for t in aux)
+        self.add_samples(states, pi, z, num_games=len(games), aux=aux)
 
     def add_game(self, game_seq):
         import torch
@@ -93,7 +116,7 @@ class DeviceReplay:
         return min(self.num_samples_added, self.capacity)
 
     # -- reads -------------------------------------------------------------------------------------------------------
-    def _gather(self, indices, op, state_dtype):
+    def _gather(self, indices, op, state_dtype, with_aux=False):
         import ctypes
 
         import torch
@@ -107,6 +130,16 @@ class DeviceReplay:
         pi = torch.empty((B, self.A), dtype=torch.float32, device=self.device)
         z = torch.empty((B,), dtype=torch.float32, device=self.device)
         stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream) if self.device.type == "cuda" else None
+        if with_aux:  # the same launch gathers the auxiliary rings, the ownership under the same op
+            own = torch.empty((B, self.N, self.N), dtype=torch.float32, device=self.device)
+            sc = torch.empty((B,), dtype=torch.float32, device=self.device)
+            rq = torch.empty((B,), dtype=torch.float32, device=self.device)
+            rc = self.b.dll.azsp_replay_gather_aux(self.states.data_ptr(), self.pi.data_ptr(), self.z.data_ptr(), idx.data_ptr(), B, self.C, self.N,
+                                                   self.A, int(op), code, st.data_ptr(), pi.data_ptr(), z.data_ptr(), self.ownership.data_ptr(),
+                                                   self.score.data_ptr(), self.root_q.data_ptr(), own.data_ptr(), sc.data_ptr(), rq.data_ptr(), stream)
+            if rc != 0:
+                raise RuntimeError(f"azsp_replay_gather_aux failed with code {rc}")
+            return st, pi, z, own, sc, rq
         rc = self.b.dll.azsp_replay_gather(self.states.data_ptr(), self.pi.data_ptr(), self.z.data_ptr(), idx.data_ptr(), B, self.C, self.N, self.A,
                                            int(op), code, st.data_ptr(), pi.data_ptr(), z.data_ptr(), stream)
         if rc != 0:
@@ -121,15 +154,18 @@ class DeviceReplay:
         st, pi, z = self._gather(indices, 0, __import__("torch").int8)
         return Transition(st.cpu().numpy(), pi.cpu().numpy().astype(self.pi_dtype), z.cpu().numpy().astype(np.float64))
 
-    def sample_device(self, batch_size, transform=None, state_dtype=None):
+    def sample_device(self, batch_size, transform=None, state_dtype=None, with_aux=False):
         """The batch as device tensors (states cast to `state_dtype`, default float32 like core/pipeline.py:636).
         transform: None, an op code 0..7 (azsp_dihedral numbering) or "random" = apply_random_transformation
         (utils/transformation.py:160-167: with probability 0.5 one of the five reference transforms for the whole batch,
-        chosen with Python's `random`)."""
+        chosen with Python's `random`).  with_aux=True (a replay built with aux_targets) returns (states, pi, z, ownership float32[B,N,N],
+        score float32[B], root_q float32[B]): the ownership under the same op as the states, score and root_q as stored."""
         import random
 
         import torch
 
+        if with_aux and not self.aux_targets:
+            raise ValueError("with_aux=True needs a replay built with aux_targets=True")
         if self.size < batch_size:
             return None
         indices = self.random_state.randint(low=0, high=self.size, size=batch_size)
@@ -139,14 +175,17 @@ class DeviceReplay:
                 op = {"h_flip": 1, "v_flip": 2, "rotate90": 3, "rotate180": 4, "rotate270": 5}[random.choice(["h_flip", "v_flip", "rotate90", "rotate180", "rotate270"])]
         elif transform is not None:
             op = int(transform)
-        return self._gather(indices, op, state_dtype or torch.float32)
+        return self._gather(indices, op, state_dtype or torch.float32, with_aux)
 
     # -- persistence (reference dictionary, :99-111; uncompressed transitions) ----------------------------------------
     def get_state(self):
         n = self.size
         st, pi, z = self.states[:n].cpu().numpy(), self.pi[:n].cpu().numpy().astype(self.pi_dtype), self.z[:n].cpu().numpy()
         storage = [Transition(st[i].copy(), pi[i].copy(), float(z[i])) for i in range(n)] + [None] * (self.capacity - n)
-        return {"num_games_added": self.num_games_added, "num_samples_added": self.num_samples_added, "storage": storage}
+        out = {"num_games_added": self.num_games_added, "num_samples_added": self.num_samples_added, "storage": storage}
+        if self.aux_targets:  # next to the reference's keys, which stay as they are: the first `size` rows of the three rings
+            out["aux"] = {"ownership": self.ownership[:n].cpu().numpy(), "score": self.score[:n].cpu().numpy(), "root_q": self.root_q[:n].cpu().numpy()}
+        return out
 
     def set_state(self, state):
         import torch
@@ -163,5 +202,12 @@ class DeviceReplay:
             self.states[i] = torch.from_numpy(np.ascontiguousarray(s)).to(self.device)
             self.pi[i] = torch.from_numpy(np.asarray(t.pi_prob, dtype=np.float32)).to(self.device)
             self.z[i] = float(t.value)
+        if self.aux_targets:  # a state without the key (a reference replay, or one saved without aux targets) loads with zero rings
+            aux = state.get("aux")
+            for ring, key in ((self.ownership, "ownership"), (self.score, "score"), (self.root_q, "root_q")):
+                ring.zero_()
+                if aux is not None:
+                    rows = torch.from_numpy(np.ascontiguousarray(aux[key]))[: self.capacity]
+                    ring[: rows.shape[0]] = rows.to(self.device, ring.dtype)
         self.num_games_added = state["num_games_added"]
         self.num_samples_added = state["num_samples_added"]

@@ -83,6 +83,10 @@ struct AzCfg {
     // sigma(a) = (gumbel_cv + max N) * gumbel_cs * (completedQ(a) + 1) / 2.  Never on together with forced playouts.
     int gumbel_m;
     double gumbel_cv, gumbel_cs;
+    // auxiliary training targets (azsp_set_aux_targets; 0 = off): record_sample stages the root value of the move, finalize_game the
+    // owner bitboards of the final position.  AzMem::stg_own / stg_rootq are null until the first enabling call; once they exist, a
+    // move or a game end with the feature off stages zeros, so that a harvest never reads what an earlier game left there.
+    int aux;
 };
 
 struct AzMem {
@@ -101,6 +105,8 @@ struct AzMem {
     unsigned char* stg_meta; // [G][2][stage_cap]   AZ_META_*
     int16_t* stg_move;       // [G][2][stage_cap]   the move played from the sample's position (-1 = resigned)
     int* stg_hdr;            // [G][2][16]  see SH_*
+    u64* stg_own;            // [G][2][2][W]        owner bitboards (black, white) of the game's final position; null until azsp_set_aux_targets
+    float* stg_rootq;        // [G][2][stage_cap]   root value of the sample's search, mover's perspective; null until azsp_set_aux_targets
     // move log (tests / shim): per game per logged move
     double* log_pi;          // [G][log_cap][A]
     float* log_childN;       // [G][log_cap][A]
@@ -1641,7 +1647,7 @@ template <class Wv, int N, int GAME> struct Engine {
         return mv;
     }
 
-    AZ_HD void record_sample() {
+    AZ_HD void record_sample(double rq) {
         int* sh = m.stg_hdr + ((size_t)g * 2 + gr.cur_buf) * SH_COUNT;
         const int k = sh[SH_LEN];
         if (k >= c.stage_cap) {
@@ -1662,6 +1668,7 @@ template <class Wv, int N, int GAME> struct Engine {
         });
         if (Wv::first()) {
             m.stg_meta[idx] = (unsigned char)((me == 0 ? AZ_META_BLACK : 0) | ((gr.sim_budget & AZ_SB_FAST) ? AZ_META_FAST : 0));
+            if (m.stg_rootq) m.stg_rootq[idx] = c.aux ? (float)rq : 0.0f;
             sh[SH_LEN] = k + 1;
         }
         Wv::sync();
@@ -1766,6 +1773,25 @@ template <class Wv, int N, int GAME> struct Engine {
             sh[SH_LAST_PLAYER] = last_player;
             sh[SH_STATE] = AZB_COMPLETE;
             gr.games_done += 1;
+        }
+        if (m.stg_own) {
+            // auxiliary targets: who owns every point of the final position (Go: Tromp-Taylor area, whatever ended the game -- a
+            // resignation leaves the board as it was; Gomoku: the stones).  One word per lane.
+            B ob = O::zero(), ow = O::zero();
+            if (c.aux) {
+                if (GAME == AZ_GO) R::go_owner(R::ld(fin.stones[0]), R::ld(fin.stones[1]), ob, ow);
+                else {
+                    ob = R::ld(fin.stones[0]);
+                    ow = R::ld(fin.stones[1]);
+                }
+            }
+            u64* own = m.stg_own + ((size_t)g * 2 + gr.cur_buf) * 2 * W;
+            Wv::lanes([&](int lane) {
+                for (int w = 0; w < W; ++w) {
+                    if (lane == w) own[w] = ob.w[w];
+                    if (lane == W + w) own[W + w] = ow.w[w];
+                }
+            });
         }
         cnt[AZC_GAMES]++;
         Wv::sync();
@@ -1902,7 +1928,7 @@ template <class Wv, int N, int GAME> struct Engine {
             Wv::sync();
             return;
         }
-        record_sample();
+        record_sample(rq);
         const int mover = gr.env.to_play;
         bool resign = false;
         if (GAME == AZ_GO && c.has_resign && gr.resign_thr > -1.0 && gr.env.steps > c.check_resign_after) {

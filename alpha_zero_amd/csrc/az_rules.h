@@ -120,12 +120,19 @@ template <class Wv, int N> struct Rules {
     // go_engine.py:123-152 area_score (no dead-stone removal): an empty region counts for a colour
     // iff it touches that colour only <=> its points are reachable through empties from that colour
     // and not from the other.
-    static AZ_HD void go_area(const B& black, const B& white, int& ab, int& aw) {
+    // ob / ow: the points that count for black / white -- the ownership map of the position (azsp_set_aux_targets)
+    static AZ_HD void go_owner(const B& black, const B& white, B& ob, B& ow) {
         const B empty = O::inv(O::bor(black, white));
         const B rb = O::flood(O::band(O::nbr(black), empty), empty);
         const B rw = O::flood(O::band(O::nbr(white), empty), empty);
-        ab = O::count(black) + O::count(O::andnot(rb, rw));
-        aw = O::count(white) + O::count(O::andnot(rw, rb));
+        ob = O::bor(black, O::andnot(rb, rw));
+        ow = O::bor(white, O::andnot(rw, rb));
+    }
+    static AZ_HD void go_area(const B& black, const B& white, int& ab, int& aw) {
+        B ob, ow;
+        go_owner(black, white, ob, ow);
+        ab = O::count(ob);
+        aw = O::count(ow);
     }
 
     static AZ_HD void go_finish(S& o, const RuleCfg& rc, int mover) {

@@ -489,6 +489,10 @@ struct OpHarvest {
     int16_t* moves;   // optional: the move played from every sample's position (azsp_harvest_moves)
     int* extra;       // [max_games][AZSP_GX_COUNT]
     uint8_t* klass;   // optional: 1 = the sample's move was a full search, 0 = a fast one of the playout cap (azsp_harvest_search_class)
+    // optional auxiliary targets in the mover's perspective (azsp_harvest_aux; non-null only once the staging rows exist)
+    int8_t* own;      // [cap][NP]  +1 the mover's point, -1 the opponent's, 0 nobody's, in the game's final position
+    float* score;     // [cap]      Go: area(mover) - area(opponent) -+ komi of the final position; Gomoku: z
+    float* rootq;     // [cap]      root value of the sample's search
     template <class E> AZ_HD void operator()(E& e) const {
         const int NP = E::NP, A = E::A, W = E::W;
         const bool go = E::GAME_ID == AZ_GO;
@@ -506,6 +510,16 @@ struct OpHarvest {
             gi = E::Wave::bcast0(gi);
             if (start < 0) continue;
             const int reward = sh[SH_REWARD], last_player = sh[SH_LAST_PLAYER];
+            const u64* ob = e.m.stg_own ? e.m.stg_own + ((size_t)e.g * 2 + b) * 2 * W : nullptr;  // owner boards: black, then white
+            double black_score = 0.0;  // go_finish's expression on the staged boards
+            if (score && go) {
+                int cb = 0, cw = 0;
+                for (int w = 0; w < W; ++w) {
+                    cb += __builtin_popcountll(ob[w]);
+                    cw += __builtin_popcountll(ob[W + w]);
+                }
+                black_score = (double)cb - ((double)cw + e.c.rc.komi);
+            }
             for (int k = 0; k < len; ++k) {
                 const size_t idx = ((size_t)e.g * 2 + b) * e.c.stage_cap + k;
                 const u64* pl = e.m.stg_planes + idx * 16 * W;
@@ -520,11 +534,21 @@ struct OpHarvest {
                         so[x] = plane < KK ? (int8_t)((pl[plane * W + (p >> 6)] >> (p & 63)) & 1ull) : (int8_t)black;
                     }
                     for (int x = lane; x < A; x += AZ_WAVE) po[x] = spi[x];
+                    if (own) {
+                        int8_t* oo = own + (size_t)(start + k) * NP;
+                        for (int p = lane; p < NP; p += AZ_WAVE) {
+                            const int d = (int)((ob[p >> 6] >> (p & 63)) & 1ull) - (int)((ob[W + (p >> 6)] >> (p & 63)) & 1ull);
+                            oo[p] = (int8_t)(black ? d : -d);
+                        }
+                    }
                 });
                 if (E::Wave::first()) {
                     // pipeline.py:349-354: z = reward for the samples of the last player, -reward for the others
                     const int mover = black ? 0 : 1;
-                    z[start + k] = reward == 0 ? 0.0f : (mover == last_player ? (float)reward : (float)-reward);
+                    const float zk = reward == 0 ? 0.0f : (mover == last_player ? (float)reward : (float)-reward);
+                    z[start + k] = zk;
+                    if (score) score[start + k] = go ? (float)(black ? black_score : -black_score) : zk;
+                    if (rootq) rootq[start + k] = e.m.stg_rootq[idx];
                     if (moves) moves[start + k] = e.m.stg_move[idx];
                     if (klass) klass[start + k] = (meta & AZ_META_FAST) ? 0 : 1;
                 }
@@ -601,6 +625,13 @@ struct ReplayGatherArgs {
     float* op_;
     float* oz;
     int batch, ch, n, A, op, dtype;
+    // auxiliary rings (azsp_replay_gather_aux), each pair null or not: ownership [capacity][n][n] under the same op, score and root value like z
+    const int8_t* ro;
+    const float* rsc;
+    const float* rq;
+    float* oo;
+    float* osc;
+    float* oq;
 };
 AZ_HD uint16_t az_f32_to_bf16(float f);
 AZ_HD uint16_t az_f32_to_f16(float f);
@@ -629,7 +660,26 @@ AZ_HD void az_replay_gather_elem(const ReplayGatherArgs& a, long long t) {
         return;
     }
     t -= (long long)a.batch * a.A;
-    if (t < a.batch) a.oz[t] = a.rz[a.idx[t]];
+    if (t < a.batch) {
+        a.oz[t] = a.rz[a.idx[t]];
+        return;
+    }
+    // the auxiliary ranges follow: [batch][np] ownership, [batch] score, [batch] root value (the launch covers them only with aux rings)
+    t -= a.batch;
+    if (t < (long long)a.batch * np) {
+        if (!a.ro) return;
+        const long long b = t / np;
+        const int p = (int)(t - b * np);
+        a.oo[t] = (float)a.ro[a.idx[b] * np + az_dihedral_src(a.op, a.n, p / a.n, p % a.n)];
+        return;
+    }
+    t -= (long long)a.batch * np;
+    if (t < a.batch) {
+        if (a.rsc) a.osc[t] = a.rsc[a.idx[t]];
+        return;
+    }
+    t -= a.batch;
+    if (t < a.batch && a.rq) a.oq[t] = a.rq[a.idx[t]];
 }
 
 // Fused conv epilogue: 8 consecutive channels (16 B of bf16/fp16, 32 B of fp32) per work item, fp32 math, one rounding.
@@ -739,6 +789,9 @@ struct AzHandle {
     int* d_games;
     int d_games_cap;
     int16_t* harvest_moves = nullptr;  // optional per-sample move output of azsp_harvest (azsp_harvest_moves)
+    int8_t* harvest_own = nullptr;     // optional per-sample auxiliary outputs of azsp_harvest (azsp_harvest_aux)
+    float* harvest_score = nullptr;
+    float* harvest_rootq = nullptr;
     uint8_t* harvest_class = nullptr;  // optional per-sample search class output of azsp_harvest (azsp_harvest_search_class)
     int* d_gextra = nullptr;           // [d_games_cap][4] per-game extras (azsp_harvest_extra)
     int32_t* harvest_extra = nullptr;  // host destination of the extras, optional
@@ -1280,7 +1333,8 @@ int azsp_harvest(void* e, int8_t* states, float* pi, float* z, int32_t cap, int3
         h->err = std::string("kernel launch failed: ") + azb::backend_error();
         return AZSP_EDEVICE;
     }
-    OpHarvest op = {states, pi, z, cap, h->d_games, max_games, h->d_hofs, h->harvest_moves, h->d_gextra, h->harvest_class};
+    OpHarvest op = {states, pi, z, cap, h->d_games, max_games, h->d_hofs, h->harvest_moves, h->d_gextra, h->harvest_class,
+                    h->harvest_own, h->harvest_score, h->harvest_rootq};
     rc = az_run(h, op, stream);
     if (rc) return rc;
     int cnt[4];
@@ -1311,6 +1365,30 @@ int azsp_harvest_moves(void* e, int16_t* moves_dev) {
     AzHandle* h = (AzHandle*)e;
     if (!h) return AZSP_EINVAL;
     h->harvest_moves = moves_dev;
+    return AZSP_OK;
+}
+
+int azsp_set_aux_targets(void* e, int32_t on) {
+    AzHandle* h = (AzHandle*)e;
+    if (!h || h->cfg.stop_after_move) return AZSP_EINVAL;  // a drop-in engine records no samples
+    if (on && (!h->mem.stg_own || !h->mem.stg_rootq)) {  // the first enabling call allocates the staging rows: never a launch path
+        if (azb::set_device(h->pub.device) != 0) return AZSP_EDEVICE;  // the engine's device, as azsp_create selects it
+        const size_t G = (size_t)h->cfg.G;
+        if (!h->mem.stg_own) h->mem.stg_own = az_new<u64>(h, G * 2 * 2 * h->W);  // (zero-initialised, like every engine allocation)
+        if (!h->mem.stg_rootq) h->mem.stg_rootq = az_new<float>(h, G * 2 * h->cfg.stage_cap);
+        if (!h->mem.stg_own || !h->mem.stg_rootq) return AZSP_ENOMEM;
+    }
+    h->cfg.aux = on ? 1 : 0;  // AzCfg travels by value with every launch: the moves recorded and the games finished after this call
+    return AZSP_OK;
+}
+
+int azsp_harvest_aux(void* e, int8_t* ownership_dev, float* score_dev, float* root_q_dev) {
+    AzHandle* h = (AzHandle*)e;
+    if (!h) return AZSP_EINVAL;
+    if ((ownership_dev || score_dev || root_q_dev) && (!h->mem.stg_own || !h->mem.stg_rootq)) return AZSP_EINVAL;  // never enabled: nothing staged
+    h->harvest_own = ownership_dev;
+    h->harvest_score = score_dev;
+    h->harvest_rootq = root_q_dev;
     return AZSP_OK;
 }
 
@@ -1524,15 +1602,26 @@ int azsp_resblock_tiled(const void* x, const void* w1, const float* b1, const vo
                      [&] { return azb::launch_resblock_tiled(x, w1, b1, w2, b2, y, (long long)boards, S, C, stream); });
 }
 
-int azsp_replay_gather(const int8_t* ring_states, const float* ring_pi, const float* ring_z, const int64_t* idx, int32_t batch, int32_t channels,
-                       int32_t n, int32_t A, int32_t op, int32_t state_dtype, void* out_states, float* out_pi, float* out_z, void* stream) {
+int azsp_replay_gather_aux(const int8_t* ring_states, const float* ring_pi, const float* ring_z, const int64_t* idx, int32_t batch, int32_t channels,
+                           int32_t n, int32_t A, int32_t op, int32_t state_dtype, void* out_states, float* out_pi, float* out_z,
+                           const int8_t* ring_own, const float* ring_score, const float* ring_root_q, float* out_own, float* out_score,
+                           float* out_root_q, void* stream) {
     if (!ring_states || !ring_pi || !ring_z || !idx || !out_states || !out_pi || !out_z || batch < 0 || channels < 1 || n < 1 ||
         (A != n * n && A != n * n + 1) || op < 0 || op > 7 || state_dtype < AZSP_FEAT_I8 || state_dtype > AZSP_FEAT_F16)
         return AZSP_EINVAL;
+    if (!ring_own != !out_own || !ring_score != !out_score || !ring_root_q != !out_root_q) return AZSP_EINVAL;  // a ring without its output, or the reverse
     if (batch == 0) return AZSP_OK;
-    ReplayGatherArgs a = {ring_states, ring_pi, ring_z, (const long long*)idx, out_states, out_pi, out_z, batch, channels, n, A, op, state_dtype};
-    const long long total = (long long)batch * ((long long)channels * n * n + A + 1);
+    ReplayGatherArgs a = {ring_states, ring_pi, ring_z, (const long long*)idx, out_states, out_pi, out_z, batch, channels, n, A, op, state_dtype,
+                          ring_own, ring_score, ring_root_q, out_own, out_score, out_root_q};
+    const bool aux = ring_own || ring_score || ring_root_q;
+    const long long total = (long long)batch * ((long long)channels * n * n + A + 1 + (aux ? (long long)n * n + 2 : 0));
     return azb::launch_replay_gather(a, total, stream) == 0 ? AZSP_OK : AZSP_EDEVICE;
+}
+
+int azsp_replay_gather(const int8_t* ring_states, const float* ring_pi, const float* ring_z, const int64_t* idx, int32_t batch, int32_t channels,
+                       int32_t n, int32_t A, int32_t op, int32_t state_dtype, void* out_states, float* out_pi, float* out_z, void* stream) {
+    return azsp_replay_gather_aux(ring_states, ring_pi, ring_z, idx, batch, channels, n, A, op, state_dtype, out_states, out_pi, out_z, nullptr,
+                                  nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 static int az_stem_tiled(const void* x, const void* w, const float* bias, void* y, int64_t boards, int32_t S, int32_t C, int32_t pad, int32_t relu,

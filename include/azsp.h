@@ -466,6 +466,32 @@ int azsp_set_gumbel(void* engine, int32_t m, double c_visit, double c_scale);
  * a drop-in caller commits.  AZSP_EINVAL before the mode was enabled for the first time.  Does not synchronise. */
 int azsp_read_gumbel_moves(void* engine, int32_t* move_dev, void* stream);
 
+/* Auxiliary training targets per sample (KataGo, Wu 2019, 4.1; no counterpart in the reference actor: opt-in, off by default).  With the
+ * feature on, actor mode stages next to every sample what the engine computes anyway and otherwise drops:
+ *   root value: the search's own value estimate root_Q of the sample's move, the value azsp_get_search reports in AZSP_SQ_ROOT_Q
+ *     (a Python float on a fresh root, an np.float32 quotient on a kept sub-tree), stored as float.  It is the mover's view already.
+ *   owner boards of the game's FINAL position, once per game: ob = black | (rb & ~rw), ow = white | (rw & ~rb), rb / rw = the empty
+ *     points reachable through empty points from a black / white stone -- the two sets whose sizes are AZSP_GR_AREA_BLACK / _WHITE
+ *     (Tromp-Taylor area, no dead-stone removal: envs/go_engine.py:123-152).  Go, every kind of game end: two passes and max_steps score
+ *     that position anyway; a resignation leaves the board as it was, so its owner boards are those of the position at the
+ *     resignation, while AZSP_GR_AREA_* stay 0 for that game as they always did.  Gomoku: ob / ow are the stones of the final board.
+ * azsp_harvest_aux hands them out in the mover's perspective, s = +1 for a sample whose mover is black, -1 for white (the bit that
+ * selects the colour plane of the state):
+ *   ownership int8[cap][N*N]: s * (bit(ob, p) - bit(ow, p)): +1 the mover's point, -1 the opponent's, 0 nobody's;
+ *   score float[cap]: Go: s * (float)((double)|ob| - ((double)|ow| + komi)), go_finish's expression (envs/go_engine.py:509-516), so for a
+ *     game ended by score it is area black - area white - komi seen by the mover; Gomoku: the sample's z;
+ *   root_q float[cap]: the staged root value, unchanged.
+ * on != 0: the first such call allocates the staging rows on the engine's device (and leaves it selected, like
+ * azsp_set_forced_playouts).  Holds for the moves recorded and the games finished after the call; what was staged earlier, or with the
+ * feature off again, reads 0.  Actor mode only: AZSP_EINVAL with stop_after_move.  states, pi, z, the game rows, the move log,
+ * azsp_get_search and every other output are what they are without this call.  The effect on playing strength is a training
+ * experiment; it has not been measured. */
+int azsp_set_aux_targets(void* engine, int32_t on);
+/* Optional outputs of azsp_harvest next to azsp_harvest_moves: ownership_dev int8[sample_capacity][N*N], score_dev and root_q_dev
+ * float[sample_capacity] as defined above; each may be NULL (the default) on its own.  AZSP_EINVAL (any non-NULL) before the feature was
+ * enabled for the first time.  Buffers must stay valid for every later harvest. */
+int azsp_harvest_aux(void* engine, int8_t* ownership_dev, float* score_dev, float* root_q_dev);
+
 /* counters_host uint64[16]: simulations, best_child calls, backup edges, leaves, duplicate leaves, terminal hits,
  * moves, games, root evaluations, nodes created, game-rounds, buffer stalls, speculative record prefetches of the select phase and
  * how many of them were used. */
@@ -617,6 +643,15 @@ int64_t azsp_small_batch_waves(int64_t waves);
 int azsp_replay_gather(const int8_t* ring_states_dev, const float* ring_pi_dev, const float* ring_z_dev, const int64_t* idx_dev, int32_t batch,
                        int32_t channels, int32_t board_size, int32_t num_actions, int32_t op, int32_t state_dtype, void* out_states_dev,
                        float* out_pi_dev, float* out_z_dev, void* stream);
+/* azsp_replay_gather plus the auxiliary rings of azsp_harvest_aux in the SAME launch: out_own[b] = T_op(ring_own[idx[b]]) as float
+ * [batch][N][N] -- the same op as the state planes: an ownership map that is not turned with its board is a wrong target -- and
+ * out_score[b] = ring_score[idx[b]], out_root_q[b] = ring_root_q[idx[b]], gathered like z.  ring_own int8 [capacity][N][N], ring_score and
+ * ring_root_q float [capacity].  Each of the three ring / output pairs may be NULL (AZSP_EINVAL for a ring without its output or the
+ * reverse); with all three NULL this is azsp_replay_gather. */
+int azsp_replay_gather_aux(const int8_t* ring_states_dev, const float* ring_pi_dev, const float* ring_z_dev, const int64_t* idx_dev, int32_t batch,
+                           int32_t channels, int32_t board_size, int32_t num_actions, int32_t op, int32_t state_dtype, void* out_states_dev,
+                           float* out_pi_dev, float* out_z_dev, const int8_t* ring_own_dev, const float* ring_score_dev,
+                           const float* ring_root_q_dev, float* out_own_dev, float* out_score_dev, float* out_root_q_dev, void* stream);
 
 /* Stem of the evaluator (core/network.py:98-108 conv_block: conv3x3 17 -> C + BatchNorm + ReLU) on the tiled layout: the
  * input is the feature tensor azsp_select writes with feature_dtype = AZSP_FEAT_BF16_TILED (2K+1 planes, 17 at num_stack K = 8,

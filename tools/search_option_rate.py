@@ -1,4 +1,5 @@
-"""What an opt-in search rule (SearchOptions.of: playout_cap, leaf_symmetry, forced_playouts, gumbel) costs an actor.
+"""What an opt-in rule of the actor (SearchOptions.of: playout_cap, leaf_symmetry, forced_playouts, gumbel; aux_targets)
+costs it.
 
 Runs the headline shape of bench.py (9x9 Go, 4096 games, 200 simulations, 8 leaves per round, 10 x 128 network, fp32-class
 evaluator) twice on the same build, with the same staggered openings and the same number of untimed and timed rounds: once with the
@@ -23,7 +24,10 @@ gumbel (--value M, default 16): select chooses the considered action in front of
   `--child-first` swaps the order inside a pair).  Printed: moves/s of every run in the order they ran, the parent's spread (max - min
   over its runs), and child - parent pair by pair.  The off path may be slower than the parent by no more than that spread.
 
-    python tools/search_option_rate.py --option {playout_cap,leaf_symmetry,forced_playouts,gumbel} [--value ...] [--steps 300] [--preroll 200]
+aux_targets (no value): the end of a move stores the root value, the end of a game the owner boards, every harvest (`--harvest-every`) writes
+  and clones the three extra outputs.  The searches of the two runs are the same here: nothing but the extra outputs differs.
+
+    python tools/search_option_rate.py --option {playout_cap,leaf_symmetry,forced_playouts,gumbel,aux_targets} [--value ...] [--steps 300] [--preroll 200]
 """
 import argparse
 import json
@@ -118,7 +122,22 @@ class Gumbel(Extra):
         return int(text or 16)
 
 
-OPTIONS = dict(playout_cap=PlayoutCap, leaf_symmetry=LeafSymmetry, forced_playouts=ForcedPlayouts, gumbel=Gumbel)
+class AuxTargets(Extra):
+    samples = 0
+
+    @staticmethod
+    def parse(text):
+        return True
+
+    def after_harvest(self, z, games):
+        self.samples += int(z.shape[0])
+        assert not self.on or self.act.last_harvest_aux.root_q.shape == z.shape
+
+    def row(self, cnt, dt):
+        return dict(samples_harvested=self.samples)
+
+
+OPTIONS = dict(playout_cap=PlayoutCap, leaf_symmetry=LeafSymmetry, forced_playouts=ForcedPlayouts, gumbel=Gumbel, aux_targets=AuxTargets)
 
 
 def bench_line(tree, steps, warmup):
