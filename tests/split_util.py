@@ -138,16 +138,16 @@ def split_resblock(bnd, x, ws, bs, device):
     return yf, y2, from_split(dll, yf, B, S, C)
 
 
-def split_stem(dll, x, w, b, pad, exact=False, relu=1):
-    """azsp_split_features -> azsp_stem_split (or _exact) on the GPU with a private range record: (raw split-layout y as f16 words on the
+def split_stem(dll, x, w, b, pad, exact=False, relu=1, device="cuda"):
+    """azsp_split_features -> azsp_stem_split (or _exact) on `device` with a private range record: (raw split-layout y as f16 words on the
     host, y as fp32 [B,C,S,S], (events, max_abs) of the private record)."""
     B, cin, n, _ = x.shape
     C, S = w.shape[0], n + 2 * (pad - 1)
-    rec = new_record("cuda")
-    feat, ys = to_split_features(dll, x, "cuda", rec), _split_zeros(dll, B, S, C, "cuda")
+    rec = new_record(device)
+    feat, ys = to_split_features(dll, x, device, rec), _split_zeros(dll, B, S, C, device)
     w32 = torch.zeros(C, 32, 3, 3)
     w32[:, :cin] = w
-    wsp, bb = split_params(w32, b, "cuda")
+    wsp, bb = split_params(w32, b, device)
     stem = dll.azsp_stem_split_exact if exact else dll.azsp_stem_split
     assert stem(feat.data_ptr(), wsp.data_ptr(), bb.data_ptr(), ys.data_ptr(), B, n, C, pad, relu, rec.data_ptr(), None) == 0
     y = from_split(dll, ys, B, S, C)
