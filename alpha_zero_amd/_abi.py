@@ -41,6 +41,7 @@ SYMBOLS = [
     "azsp_set_forced_playouts", "azsp_read_target_policies",
     "azsp_set_gumbel", "azsp_read_gumbel_moves",
     "azsp_set_aux_targets", "azsp_harvest_aux", "azsp_replay_gather_aux",
+    "azsp_set_policy_surprise", "azsp_harvest_surprise", "azsp_replay_add_weighted",
 ]
 
 COUNTER_NAMES = ["sims", "node_visits", "backup_edges", "leaves", "dup_leaves", "terminal_hits", "moves", "games", "root_evals",
@@ -101,6 +102,8 @@ class Binding:
             "azsp_set_gumbel": [V, I, C.c_double, C.c_double], "azsp_read_gumbel_moves": [V, V, V],
             "azsp_set_aux_targets": [V, I], "azsp_harvest_aux": [V, V, V, V],
             "azsp_replay_gather_aux": [V, V, V, V, I, I, I, I, I, I, V, V, V, V, V, V, V, V, V, V],
+            "azsp_set_policy_surprise": [V, I, C.c_double, I], "azsp_harvest_surprise": [V, V, V],
+            "azsp_replay_add_weighted": [V, V, V, C.c_int64, C.c_int64, V, V, V, I, I, I, I, V, V, V, V, V, V, V, V, V, V],
         }
         for k in ("azsp_conv3x3_tiled", "azsp_stem_tiled", "azsp_head_tiled", "azsp_fc_heads"):  # the f16 variants take the same arguments
             sig[k + "_f16"] = sig[k]

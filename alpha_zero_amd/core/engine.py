@@ -58,6 +58,7 @@ class EngineConfig:
     forced_playouts: object = None   # None | k >= 0,
     gumbel: object = None            # None | m | (m, c_visit, c_scale)
     aux_targets: bool = False        # auxiliary training targets per sample (Engine.set_aux_targets; harvest(with_aux=True))
+    policy_surprise: object = None   # policy surprise weighting (Engine.set_policy_surprise; harvest(with_surprise=True)): None | frac | (frac, include_fast)
 
 
 def leaf_symmetry_mode(mode):
@@ -96,6 +97,21 @@ def gumbel_params(gumbel):
             and is_num(gumbel[2]):
         return int(gumbel[0]), float(gumbel[1]), float(gumbel[2])
     raise ValueError(f"gumbel must be None (off), an integer m >= 0 or (m, c_visit, c_scale) with finite c_visit, c_scale >= 0, got {gumbel!r}")
+
+
+def policy_surprise_params(value):
+    """The azsp_set_policy_surprise arguments (on, frac, include_fast) of a `policy_surprise` value: None = off, a number frac in [0, 1]
+    = on with that share of every game's weight handed out by surprise (fast moves of a playout cap take no part), or
+    (frac, include_fast).  Anything else raises ValueError naming these."""
+    is_frac = lambda v: (not isinstance(v, (bool, str)) and isinstance(v, (int, float, np.integer, np.floating))  # noqa: E731
+                         and 0.0 <= float(v) <= 1.0)
+    if value is None:
+        return 0, 0.0, 0
+    if is_frac(value):
+        return 1, float(value), 0
+    if isinstance(value, (tuple, list)) and len(value) == 2 and is_frac(value[0]) and isinstance(value[1], (bool, np.bool_)):
+        return 1, float(value[0]), int(bool(value[1]))
+    raise ValueError(f"policy_surprise must be None (off), a number frac in [0, 1] or (frac, include_fast: bool), got {value!r}")
 
 
 EXCLUSIVE = "gumbel and forced_playouts cannot be on together: both decide what the root selects"
@@ -226,6 +242,10 @@ class Engine:
         self._harvest_aux_bufs = None
         if cfg.aux_targets:
             self.set_aux_targets(True)  # before the first move is recorded
+        self.policy_surprise = False  # has been on at least once, so the staging row exists (harvest(with_surprise=True))
+        self._harvest_surprise_bufs = None
+        if cfg.policy_surprise is not None:
+            self.set_policy_surprise(cfg.policy_surprise)  # before the first move is recorded
 
     # -- plumbing ---------------------------------------------------------------------------------
     def _ck(self, rc, what):
@@ -476,6 +496,19 @@ class Engine:
         self._ck(self.b.dll.azsp_set_aux_targets(self.h, int(bool(on))), "azsp_set_aux_targets")
         self.aux_targets = self.aux_targets or bool(on)
 
+    def set_policy_surprise(self, value):
+        """Policy surprise weighting (azsp_set_policy_surprise; KataGo, Wu 2019; the reference actor has none).  value: None = off, frac
+        in [0, 1] or (frac, include_fast), policy_surprise_params.  On, the engine stages with every recorded move the KL divergence
+        of its policy target from the root's raw prior, and `harvest(with_surprise=True)` hands out that surprise and the weight of
+        every row: a share 1 - frac of a game's full-search rows spread evenly over them, a share frac over the rows in proportion
+        to their surprise (with include_fast the fast moves of a playout cap too).  The batched actor only (an AzspError on a
+        stop_after_move engine).  On / off holds for the moves recorded from now on (what was staged with it off reads 0, and a game
+        without surprise is weighted `full`); frac and include_fast hold for the harvests from now on.  Samples, game rows, logs and
+        searches are untouched."""
+        on, frac, fast = policy_surprise_params(value)
+        self._ck(self.b.dll.azsp_set_policy_surprise(self.h, on, frac, fast), "azsp_set_policy_surprise")
+        self.policy_surprise = self.policy_surprise or bool(on)
+
     def gumbel_moves(self):
         """int32[G] on the engine's device: a* of every slot's last finished Gumbel root search, -1 before the first and after a fast move
         (azsp_read_gumbel_moves).  Only once the mode has been enabled.  Nothing is synchronised."""
@@ -492,13 +525,16 @@ class Engine:
         return out
 
     # -- samples ----------------------------------------------------------------------------------------
-    def harvest(self, sample_capacity=None, max_games=None, with_moves=False, with_class=False, with_aux=False):
+    def harvest(self, sample_capacity=None, max_games=None, with_moves=False, with_class=False, with_aux=False, with_surprise=False):
         """Returns (states int8[n,2K+1,N,N], pi float32[n,A], z float32[n], games int32[k,GR_COUNT]) -- device tensors + host meta;
         with_moves=True appends moves int16[n] (the move played from every sample's position, -1 = resigned); with_class=True then
         appends full uint8[n] (1 = the sample's move was a full search, 0 = a fast move of the playout cap; all 1 with the cap off).
         with_aux=True (only once aux targets have been enabled) then appends ownership int8[n,N,N] (+1 the mover's point, -1 the
         opponent's, 0 nobody's, in the game's final position), score float32[n] (Go: the final area score with komi seen by the mover;
         Gomoku: z) and root_q float32[n] (the root value of the sample's search): include/azsp.h, azsp_set_aux_targets.
+        with_surprise=True (only once policy surprise weighting has been enabled) then appends surprise float32[n] (the KL divergence of
+        the sample's policy target from its root's raw prior) and weight float32[n] (how often the row is to be written into the training
+        data; DeviceReplay.add_harvest(weights=)): include/azsp.h, azsp_set_policy_surprise.
         The per-game extras of the same call (azsp_harvest_extra) are left in `self.last_extra` int32[k,GX_COUNT].
         ALIASING: the device tensors are views of buffers this engine re-uses -- the NEXT harvest() overwrites them in place.
         Consume (or .clone()) them before harvesting again; SelfPlayActor.harvest_tensors(clone=True) does the latter."""
@@ -520,6 +556,11 @@ class Engine:
                                           torch.empty((st.shape[0],), dtype=torch.float32, device=self.device))
             self._ck(self.b.dll.azsp_harvest_aux(self.h, *([t.data_ptr() for t in self._harvest_aux_bufs] if with_aux else [None] * 3)),
                      "azsp_harvest_aux")
+        if with_surprise or self._harvest_surprise_bufs is not None:  # (as above: no call from an engine that never asked)
+            if with_surprise and (self._harvest_surprise_bufs is None or self._harvest_surprise_bufs[0].shape[0] < st.shape[0]):
+                self._harvest_surprise_bufs = tuple(torch.empty((st.shape[0],), dtype=torch.float32, device=self.device) for _ in range(2))
+            self._ck(self.b.dll.azsp_harvest_surprise(self.h, *([t.data_ptr() for t in self._harvest_surprise_bufs] if with_surprise else [None] * 2)),
+                     "azsp_harvest_surprise")
         games = np.zeros((mg, _abi.GR_COUNT), dtype=np.int32)
         extra = np.zeros((mg, _abi.GX_COUNT), dtype=np.int32)
         self._ck(self.b.dll.azsp_harvest_extra(self.h, extra.ctypes.data), "azsp_harvest_extra")
@@ -536,6 +577,8 @@ class Engine:
             out += (clbuf[:n],)
         if with_aux:
             out += tuple(t[:n] for t in self._harvest_aux_bufs)
+        if with_surprise:
+            out += tuple(t[:n] for t in self._harvest_surprise_bufs)
         return out
 
     def counters(self, reset=False):

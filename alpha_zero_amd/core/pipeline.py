@@ -47,7 +47,7 @@ import warnings  # noqa: E402
 
 import torch  # noqa: E402
 
-from .engine import Engine, EngineConfig, SearchOptions, check_num_stack  # noqa: E402
+from .engine import Engine, EngineConfig, SearchOptions, check_num_stack, policy_surprise_params  # noqa: E402
 from .network import AlphaZeroNet, InferenceNet, capture_graph, widen_for_kernels  # noqa: E402
 from .replay import Transition  # noqa: E402
 
@@ -114,7 +114,8 @@ class SelfPlayActor:
                  resign_threshold=-1.0, komi=7.5, num_to_win=5, seed=1, rank=0, device="cuda", net_dtype=torch.float32,
                  use_graph=True, training_steps=0, binding=None, root_noise=True, deterministic=False, tiled_features=None, engine_kw=None,
                  use_split_evaluator=True, auto_widen=None, num_stack=8, split_any_board=False, playout_cap=None,
-                 leaf_symmetry=None, forced_playouts=None, prune_policy_target=True, gumbel=None, aux_targets=False):
+                 leaf_symmetry=None, forced_playouts=None, prune_policy_target=True, gumbel=None, aux_targets=False,
+                 policy_surprise=None):
         """net_dtype: precision class of the leaf evaluator.  The default is the REFERENCE'S: fp32 (pipeline.py:91-123 evaluates in fp32,
         no autocast anywhere) -- on the hand-written split-precision kernels (hi + lo f16 pairs, three MFMA products, fp32 accumulation:
         include/azsp.h azsp_conv3x3_split) for 9x9 x {128, 64} and 13x13 Gomoku x 64 networks, on library fp32 convolutions (announced
@@ -136,7 +137,12 @@ class SelfPlayActor:
         flags in `last_harvest_full`.
         aux_targets: True = every sample carries the auxiliary training targets (Engine.set_aux_targets: ownership of the final position,
         final score, root value of its search, all in the mover's perspective); `harvest_tensors()` leaves them in `last_harvest_aux`.
-        Off by default; not with a drop-in engine (engine_kw stop_after_move: ValueError), which records no samples."""
+        Off by default; not with a drop-in engine (engine_kw stop_after_move: ValueError), which records no samples.
+        policy_surprise: None, frac or (frac, include_fast) (Engine.set_policy_surprise): every sample carries the KL divergence of its
+        policy target from its root's raw prior and the weight that follows from it; `harvest_tensors()` leaves them in
+        `last_harvest_surprise` / `last_harvest_weight`, and `DeviceReplay.add_harvest(weights=actor.last_harvest_weight)` writes every
+        row as often as its weight says -- with include_fast also the fast moves of a playout cap that `keep=last_harvest_full` drops.
+        Off by default; not with a drop-in engine (ValueError)."""
         opt = SearchOptions.of(leaf_symmetry, forced_playouts, prune_policy_target, gumbel, playout_cap, num_simulations)  # ValueError before anything is built
         from .. import _lib
 
@@ -183,9 +189,15 @@ class SelfPlayActor:
         if self.aux_targets and self.cfg.stop_after_move:
             raise ValueError("aux_targets needs the batched actor: a drop-in engine (stop_after_move) records no samples")
         self.cfg.aux_targets = self.aux_targets
+        if policy_surprise is not None:
+            self.cfg.policy_surprise = policy_surprise
+        self.policy_surprise = policy_surprise_params(self.cfg.policy_surprise)[0] != 0  # (ValueError for a malformed value, before the engine is built)
+        if self.policy_surprise and self.cfg.stop_after_move:
+            raise ValueError("policy_surprise needs the batched actor: a drop-in engine (stop_after_move) records no samples")
         self.engine = Engine(self.binding, self.cfg, device=self.device, prune_policy_target=self.prune_policy_target, playout_cap=self.playout_cap)
         self.last_harvest_full = torch.zeros(0, dtype=torch.bool, device=self.device)
         self.last_harvest_aux = None  # HarvestAux of the last harvest_tensors() (aux_targets=True only)
+        self.last_harvest_surprise = self.last_harvest_weight = None  # float32[n] of the last harvest_tensors() (policy_surprise only)
         self.engine.reset_games()
         self._graph = None
         self.rounds = 0
@@ -286,11 +298,15 @@ class SelfPlayActor:
         """(states, pi, z, games) of the finished games as device tensors.  The tensors are views of buffers the engine re-uses: the
         next harvest overwrites them in place.  clone=True returns private copies (for consumers that keep them across harvests,
         e.g. an asynchronous learner or a replay insert on another stream).  With aux_targets the auxiliary targets of the same rows
-        are left in `last_harvest_aux` (ownership int8[n,N,N], score float32[n], root_q float32[n]; views or clones like the rest)."""
-        got = self.engine.harvest(with_class=True, with_aux=self.aux_targets)
+        are left in `last_harvest_aux` (ownership int8[n,N,N], score float32[n], root_q float32[n]; views or clones like the rest).
+        With policy_surprise the surprise and the weight of the same rows are left in `last_harvest_surprise` / `last_harvest_weight`
+        (float32[n] each; views or clones like the rest)."""
+        got = self.engine.harvest(with_class=True, with_aux=self.aux_targets, with_surprise=self.policy_surprise)
         st, pi, z, games, full = got[:5]
         if self.aux_targets:
-            self.last_harvest_aux = HarvestAux(*(t.clone() if clone else t for t in got[5:]))
+            self.last_harvest_aux = HarvestAux(*(t.clone() if clone else t for t in got[5:8]))
+        if self.policy_surprise:
+            self.last_harvest_surprise, self.last_harvest_weight = (t.clone() if clone else t for t in got[-2:])
         self._check_evaluator_range()
         self.last_harvest_clamped = self.clamp_window.mask(games[:, _abi.GR_UID]) if len(games) else np.zeros(0, dtype=bool)
         self.clamped_games += int(self.last_harvest_clamped.sum())

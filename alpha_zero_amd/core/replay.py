@@ -25,7 +25,9 @@ class DeviceReplay:
     `add_game` / `sample` / `get_state` / `set_state` keep the reference's host-side signatures.
     aux_targets=True (no counterpart in the reference: opt-in) adds three rings for the auxiliary targets of `Engine.harvest(with_aux=True)`
     -- ownership int8[capacity, N, N], score and root_q float32[capacity] -- written with the samples (`aux=`) and gathered by
-    `sample_device(with_aux=True)` in the same launch, the ownership under the same dihedral op as the state planes."""
+    `sample_device(with_aux=True)` in the same launch, the ownership under the same dihedral op as the state planes.
+    `add_samples(weights=)` / `add_harvest(weights=)` (policy surprise weighting, no counterpart in the reference: opt-in) write every row as
+    often as its weight says (`azsp_replay_add_weighted`); the ring then holds plain rows, and every read is what it was."""
 
     def __init__(self, capacity, random_state, board_size, num_actions, channels=17, device="cuda", binding=None, pi_dtype=np.float64,
                  aux_targets=False):
@@ -62,14 +64,50 @@ class DeviceReplay:
         if aux is not None and (len(aux) != 3 or any(int(t.shape[0]) != n for t in aux)):
             raise ValueError(f"`aux` must be (ownership, score, root_q) with one row per sample ({n})")
 
-    def add_samples(self, states, pi, z, num_games=1, aux=None):
+    def _add_weighted(self, states, pi, z, aux, weights):
+        """Row i is appended c_i = floor(w_i) + (u_i < w_i - floor(w_i)) times, u = random_state.random_sample(n): one uniform per row,
+        rows with integer weights included.  One count-and-scan launch and one scatter launch (azsp_replay_add_weighted); the host reads
+        the total (4 bytes) to advance num_samples_added."""
+        import ctypes
+
+        import torch
+
+        n = int(z.shape[0])
+        w = torch.as_tensor(weights).to(self.device, torch.float32).reshape(-1).contiguous()
+        if w.shape[0] != n:
+            raise ValueError(f"`weights` must hold one weight per sample ({n}), got {w.shape[0]}")
+        u = torch.from_numpy(np.asarray(self.random_state.random_sample(n), dtype=np.float64)).to(self.device)
+        if n == 0:
+            return
+        states = torch.as_tensor(states).to(self.device, torch.int8).reshape((n,) + self.states.shape[1:]).contiguous()
+        pi = torch.as_tensor(pi).to(self.device, torch.float32).reshape(n, self.A).contiguous()
+        z = torch.as_tensor(z).to(self.device, torch.float32).reshape(n).contiguous()
+        rings = (self.ownership, self.score, self.root_q) if aux is not None else ()
+        srcs = [torch.as_tensor(t).to(self.device, ring.dtype).reshape((n,) + ring.shape[1:]).contiguous() for ring, t in zip(rings, aux or ())]
+        ofs = torch.empty((n + 1,), dtype=torch.int32, device=self.device)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream) if self.device.type == "cuda" else None
+        rc = self.b.dll.azsp_replay_add_weighted(self.states.data_ptr(), self.pi.data_ptr(), self.z.data_ptr(), self.capacity, self.num_samples_added,
+                                                 states.data_ptr(), pi.data_ptr(), z.data_ptr(), n, self.C, self.N, self.A, w.data_ptr(), u.data_ptr(),
+                                                 *([t.data_ptr() for t in rings] or [None] * 3), *([t.data_ptr() for t in srcs] or [None] * 3),
+                                                 ofs.data_ptr(), stream)
+        if rc != 0:
+            raise RuntimeError(f"azsp_replay_add_weighted failed with code {rc}")
+        self.num_samples_added += int(ofs[n])  # (synchronises: the sources may be re-used once this returns)
+
+    def add_samples(self, states, pi, z, num_games=1, aux=None, weights=None):
         """Appends samples in order (device or host tensors): the ring positions the reference's per-transition loop
         would have written (:55-68).  More samples than the capacity keep only the last `capacity` (the earlier ones
-        would have been overwritten by the same call).  aux: (ownership, score, root_q) of the same rows, with aux_targets."""
+        would have been overwritten by the same call).  aux: (ownership, score, root_q) of the same rows, with aux_targets.
+        weights: an optional float per sample (e.g. the actor's `last_harvest_weight`): the row is written floor(w) times and once more
+        with probability w - floor(w) (a NaN or negative weight: never), as if the rows had been repeated that often and then appended."""
         import torch
 
         n = int(z.shape[0])
         self._check_aux(aux, n)
+        if weights is not None:
+            self._add_weighted(states, pi, z, aux, weights)
+            self.num_games_added += num_games
+            return
         if n:
             states = torch.as_tensor(states).to(self.device, torch.int8)
             pi = torch.as_tensor(pi).to(self.device, torch.float32)
@@ -86,10 +124,14 @@ class DeviceReplay:
             self.num_samples_added += n
         self.num_games_added += num_games
 
-    def add_harvest(self, states, pi, z, games, keep=None, aux=None):
+    def add_harvest(self, states, pi, z, games, keep=None, aux=None, weights=None):
         """Everything `SelfPlayActor.harvest_tensors()` returned: finished games, concatenated in harvest order.  keep: an optional
         bool per sample (e.g. the actor's `last_harvest_full` under a playout cap): only those rows are stored, in order; the games
-        count as before.  aux: the actor's `last_harvest_aux` of the same harvest (with aux_targets), filtered by `keep` like the samples."""
+        count as before.  aux: the actor's `last_harvest_aux` of the same harvest (with aux_targets), filtered by `keep` like the samples.
+        weights: the actor's `last_harvest_weight` of the same harvest (policy surprise weighting) instead of `keep` (both: ValueError):
+        every row is stored as often as its weight says, `add_samples(weights=)`; a fast move has weight 0 unless it earned a share."""
+        if weights is not None and keep is not None:
+            raise ValueError("`weights` and `keep` cannot be given together: a weight of 0 drops a row")
         self._check_aux(aux, int(z.shape[0]))
         if keep is not None:
             import torch
@@ -100,7 +142,7 @@ class DeviceReplay:
             states, pi, z = (torch.as_tensor(t)[k.to(torch.as_tensor(t).device)] for t in (states, pi, z))
             if aux is not None:
                 aux = tuple(torch.as_tensor(t)[k.to(torch.as_tensor(t).device)] for t in aux)
-        self.add_samples(states, pi, z, num_games=len(games), aux=aux)
+        self.add_samples(states, pi, z, num_games=len(games), aux=aux, weights=weights)
 
     def add_game(self, game_seq):
         import torch

@@ -87,6 +87,10 @@ struct AzCfg {
     // owner bitboards of the final position.  AzMem::stg_own / stg_rootq are null until the first enabling call; once they exist, a
     // move or a game end with the feature off stages zeros, so that a harvest never reads what an earlier game left there.
     int aux;
+    // policy surprise weighting (azsp_set_policy_surprise; 0 = off): record_sample stages the KL divergence of the recorded policy target
+    // from the root's raw prior.  AzMem::stg_surprise is null until the first enabling call; once it exists, a move recorded with the
+    // feature off stages 0.  (The game weights are the harvest's: OpHarvest.)
+    int surprise;
 };
 
 struct AzMem {
@@ -107,6 +111,7 @@ struct AzMem {
     int* stg_hdr;            // [G][2][16]  see SH_*
     u64* stg_own;            // [G][2][2][W]        owner bitboards (black, white) of the game's final position; null until azsp_set_aux_targets
     float* stg_rootq;        // [G][2][stage_cap]   root value of the sample's search, mover's perspective; null until azsp_set_aux_targets
+    float* stg_surprise;     // [G][2][stage_cap]   KL(policy target || root prior) of the sample's search; null until azsp_set_policy_surprise
     // move log (tests / shim): per game per logged move
     double* log_pi;          // [G][log_cap][A]
     float* log_childN;       // [G][log_cap][A]
@@ -1647,6 +1652,33 @@ template <class Wv, int N, int GAME> struct Engine {
         return mv;
     }
 
+    // Policy surprise of the search that just ended (azsp_set_policy_surprise): KL(pi || P / Z) in float64, pi = the target row record_sample
+    // stages (sc.pi), P = the root's prior row as the evaluator gave it (expand_node stores it unmasked; noise and the Gumbel base row live
+    // in rootP), Z = its mass on the root's legal actions.  The 1e-45 floor is apply_gumbel's.
+    AZ_HD float policy_surprise() {
+        const S& s = hdr(gr.root).st;
+        const float* rp = rowP(gr.root);
+        const double z = Wv::sum_f64([&](int lane) -> double {
+            double part = 0.0;
+            for (int a = lane; a < A; a += AZ_WAVE)
+                if (action_legal(s, a)) part += (double)rp[a];
+            return part;
+        });
+        double kl = Wv::sum_f64([&](int lane) -> double {
+            double part = 0.0;
+            for (int a = lane; a < A; a += AZ_WAVE) {
+                const double t = sc.pi[a];
+                if (t > 0.0) {
+                    const double p = (double)rp[a];
+                    part += t * (log(t) - log(p > 1e-45 ? p : 1e-45));
+                }
+            }
+            return part;
+        });
+        kl += z > 0.0 ? log(z) : 0.0;
+        return (float)(kl > 0.0 ? kl : 0.0);
+    }
+
     AZ_HD void record_sample(double rq) {
         int* sh = m.stg_hdr + ((size_t)g * 2 + gr.cur_buf) * SH_COUNT;
         const int k = sh[SH_LEN];
@@ -1658,6 +1690,8 @@ template <class Wv, int N, int GAME> struct Engine {
         u64* pl = m.stg_planes + idx * 16 * W;
         float* pi = m.stg_pi + idx * A;
         const int me = gr.env.to_play;
+        float surprise = 0.0f;
+        if (m.stg_surprise && c.surprise) surprise = policy_surprise();
         // observation BEFORE the move, mover's perspective (pipeline.py:323): the history ring itself
         Wv::lanes([&](int lane) {
             for (int t = lane; t < 16 * W; t += AZ_WAVE) {
@@ -1669,6 +1703,7 @@ template <class Wv, int N, int GAME> struct Engine {
         if (Wv::first()) {
             m.stg_meta[idx] = (unsigned char)((me == 0 ? AZ_META_BLACK : 0) | ((gr.sim_budget & AZ_SB_FAST) ? AZ_META_FAST : 0));
             if (m.stg_rootq) m.stg_rootq[idx] = c.aux ? (float)rq : 0.0f;
+            if (m.stg_surprise) m.stg_surprise[idx] = surprise;
             sh[SH_LEN] = k + 1;
         }
         Wv::sync();

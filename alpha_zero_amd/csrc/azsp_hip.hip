@@ -39,6 +39,35 @@ __global__ void __launch_bounds__(256) k_replay_gather(const ReplayGatherArgs a,
         az_replay_gather_elem(a, t);
 }
 
+__global__ void __launch_bounds__(256) k_replay_scatter(const ReplayAddArgs a, long long total) {
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x)
+        az_replay_scatter_elem(a, t);
+}
+
+// One workgroup walks the rows in chunks of its size: thread t owns row base + t, the chunk's counts are scanned in LDS, the chunks' totals
+// carried on (64-bit: ofs saturates, az_replay_ofs).
+__global__ void __launch_bounds__(1024) k_replay_count(const float* __restrict__ weights, const double* __restrict__ unif, int* __restrict__ ofs, int n) {
+    __shared__ long long sc[1024];
+    const int t = (int)threadIdx.x;
+    long long carry = 0;
+    for (int base = 0; base < n; base += 1024) {
+        const int i = base + t;
+        const long long c = i < n ? az_replay_copies(weights[i], unif[i]) : 0;
+        sc[t] = c;
+        __syncthreads();
+        for (int d = 1; d < 1024; d <<= 1) {  // inclusive Hillis-Steele scan of the chunk's counts
+            const long long a = t >= d ? sc[t - d] : 0;
+            __syncthreads();
+            sc[t] += a;
+            __syncthreads();
+        }
+        if (i < n) ofs[i] = az_replay_ofs(carry + sc[t] - c);
+        carry += sc[1023];
+        __syncthreads();  // the next chunk overwrites sc
+    }
+    if (t == 0) ofs[n] = az_replay_ofs(carry);
+}
+
 __global__ void __launch_bounds__(256) k_bias_act(const BiasActArgs a) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < a.nvec; i += (long long)gridDim.x * blockDim.x)
         az_bias_act_vec(a, i);
@@ -150,6 +179,14 @@ int launch_replay_gather(const ReplayGatherArgs& a, long long total, void* st) {
     long long blocks = (total + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
     return launch_k(k_replay_gather, (unsigned)blocks, 256, 0, st, a, total);
+}
+int launch_replay_count(const float* weights, const double* unif, int* ofs, int n, void* st) {
+    return launch_k(k_replay_count, 1, 1024, 0, st, weights, unif, ofs, n);
+}
+int launch_replay_scatter(const ReplayAddArgs& a, long long total, void* st) {
+    long long blocks = (total + 255) / 256;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    return launch_k(k_replay_scatter, (unsigned)blocks, 256, 0, st, a, total);
 }
 int launch_harvest_scan(const int* len, int* ofs, int* counts, int n2, int rot, int cap, int max_games, void* st) {
     return launch_k(k_harvest_scan, 1, 1024, 0, st, len, ofs, counts, n2, rot, cap, max_games);

@@ -478,6 +478,15 @@ AZ_HD void az_harvest_scan_range(const int* len, int* ofs, int n2, int rot, int 
         ofs[2 * idx + 1] = gi;
     }
 }
+// Policy surprise weighting (KataGo, Wu 2019): the weight of one row of a game with nf full-search rows whose participating rows'
+// surprises sum to ssum.  A share 1 - frac of the game's weight nf goes to the full rows evenly, a share frac to the participating rows
+// in proportion to their surprise; a game without surprise is weighted uniformly.  float64, in exactly this operation order.
+AZ_HD float az_surprise_weight(bool full, int include_fast, double frac, double nf, double ssum, float surprise) {
+    const double fk = full ? 1.0 : 0.0;
+    if (!(ssum > 0.0)) return (float)fk;
+    const double share = (full || include_fast) ? frac * nf * (double)surprise / ssum : 0.0;
+    return (float)((1.0 - frac) * fk + share);
+}
 struct OpHarvest {
     int8_t* states;
     float* pi;
@@ -493,6 +502,11 @@ struct OpHarvest {
     int8_t* own;      // [cap][NP]  +1 the mover's point, -1 the opponent's, 0 nobody's, in the game's final position
     float* score;     // [cap]      Go: area(mover) - area(opponent) -+ komi of the final position; Gomoku: z
     float* rootq;     // [cap]      root value of the sample's search
+    // optional policy surprise weighting (azsp_harvest_surprise; non-null only once the staging row exists)
+    float* surprise;  // [cap]      the staged KL(policy target || root prior) of the sample's search
+    float* weight;    // [cap]      how often the row is to be written into the training data: az_surprise_weight over its game
+    double frac;      // share of a game's weight handed out by surprise, in [0, 1]
+    int include_fast; // fast moves of the playout cap take part in the surprise share
     template <class E> AZ_HD void operator()(E& e) const {
         const int NP = E::NP, A = E::A, W = E::W;
         const bool go = E::GAME_ID == AZ_GO;
@@ -519,6 +533,16 @@ struct OpHarvest {
                     cw += __builtin_popcountll(ob[W + w]);
                 }
                 black_score = (double)cb - ((double)cw + e.c.rc.komi);
+            }
+            // the game's sums of the weights, once per staging buffer: wave-uniform, sequential, in row order (this order is the contract)
+            double nf = 0.0, ssum = 0.0;
+            if (weight) {
+                const size_t row0 = ((size_t)e.g * 2 + b) * e.c.stage_cap;
+                for (int k = 0; k < len; ++k) {
+                    const bool full = !(e.m.stg_meta[row0 + k] & AZ_META_FAST);
+                    if (full) nf += 1.0;
+                    if (full || include_fast) ssum += (double)e.m.stg_surprise[row0 + k];
+                }
             }
             for (int k = 0; k < len; ++k) {
                 const size_t idx = ((size_t)e.g * 2 + b) * e.c.stage_cap + k;
@@ -549,6 +573,8 @@ struct OpHarvest {
                     z[start + k] = zk;
                     if (score) score[start + k] = go ? (float)(black ? black_score : -black_score) : zk;
                     if (rootq) rootq[start + k] = e.m.stg_rootq[idx];
+                    if (surprise) surprise[start + k] = e.m.stg_surprise[idx];
+                    if (weight) weight[start + k] = az_surprise_weight(!(meta & AZ_META_FAST), include_fast, frac, nf, ssum, e.m.stg_surprise[idx]);
                     if (moves) moves[start + k] = e.m.stg_move[idx];
                     if (klass) klass[start + k] = (meta & AZ_META_FAST) ? 0 : 1;
                 }
@@ -682,6 +708,79 @@ AZ_HD void az_replay_gather_elem(const ReplayGatherArgs& a, long long t) {
     if (t < a.batch && a.rq) a.oq[t] = a.rq[a.idx[t]];
 }
 
+// Weighted replay add (azsp_replay_add_weighted; policy surprise weighting): row i of the source is written c_i times, c_i drawn from its
+// weight by stochastic rounding.  Two launches: one workgroup counts and scans (ofs[n + 1], the exclusive prefix of c_i), then a flat element
+// kernel over the SOURCE elements scatters every element it read once to the ring rows of its copies.
+// c = floor(w) + (u < w - floor(w)), w = the float weight widened to double and clamped to [0, 2^20]; a NaN or negative weight gives 0.
+#define AZ_REPLAY_MAX_WEIGHT 1048576.0
+AZ_HD int az_replay_copies(float weight, double u) {
+    double w = (double)weight;
+    if (!(w > 0.0)) return 0;
+    if (w > AZ_REPLAY_MAX_WEIGHT) w = AZ_REPLAY_MAX_WEIGHT;
+    const long long fl = (long long)w;  // floor: w >= 0
+    return (int)fl + (u < w - (double)fl ? 1 : 0);
+}
+// a prefix as ofs holds it: saturated at INT32_MAX, so that ofs stays monotone and every difference a count >= 0 whatever the weights are
+AZ_HD int az_replay_ofs(long long prefix) { return prefix > 0x7fffffffLL ? 0x7fffffff : (int)prefix; }
+// rows [lo, hi) with the exclusive prefix of everything before lo; returns the prefix after hi - 1
+AZ_HD long long az_replay_count_range(const float* weights, const double* unif, int* ofs, int lo, int hi, long long prefix) {
+    for (int i = lo; i < hi; ++i) {
+        ofs[i] = az_replay_ofs(prefix);
+        prefix += az_replay_copies(weights[i], unif[i]);
+    }
+    return prefix;
+}
+struct ReplayAddArgs {
+    int8_t* rs;         // ring states [capacity][ch][n][n]
+    float* rp;          // ring pi [capacity][A]
+    float* rz;          // ring z [capacity]
+    const int8_t* ss;   // source rows, the same layouts
+    const float* sp;
+    const float* sz;
+    const int* ofs;     // [rows + 1] exclusive prefix of the copies, ofs[rows] = total
+    long long capacity, added;  // ring rows; rows written before this add (num_samples_added)
+    int rows, ch, n, A;
+    // auxiliary rings and sources, each pair null or not: ownership [.][n][n], score and root value [.]
+    int8_t* ro;
+    float* rsc;
+    float* rq;
+    const int8_t* so;
+    const float* ssc;
+    const float* sq;
+};
+// element e of source row i (row length per) -> the same element of the ring rows of the row's copies.  Of an add larger than the ring only
+// the last `capacity` copies land (add_samples' `skip`), so no ring row has two writers.
+template <class T> AZ_HD void az_replay_scatter_copies(const ReplayAddArgs& a, T* ring, const T* src, long long per, long long t) {
+    const long long i = t / per, e = t - i * per;
+    const long long first = a.ofs[i], end = a.ofs[i + 1], total = a.ofs[a.rows];
+    long long j = total - a.capacity > first ? total - a.capacity : first;
+    if (j >= end) return;
+    const T v = src[t];
+    for (; j < end; ++j) ring[((a.added + j) % a.capacity) * per + e] = v;
+}
+AZ_HD void az_replay_scatter_elem(const ReplayAddArgs& a, long long t) {
+    const int np = a.n * a.n;
+    const long long per = (long long)a.ch * np;
+    if (t < a.rows * per) return az_replay_scatter_copies(a, a.rs, a.ss, per, t);
+    t -= a.rows * per;
+    if (t < (long long)a.rows * a.A) return az_replay_scatter_copies(a, a.rp, a.sp, (long long)a.A, t);
+    t -= (long long)a.rows * a.A;
+    if (t < a.rows) return az_replay_scatter_copies(a, a.rz, a.sz, 1LL, t);
+    // the auxiliary ranges follow: [rows][np] ownership, [rows] score, [rows] root value (the launch covers them only with aux rings)
+    t -= a.rows;
+    if (t < (long long)a.rows * np) {
+        if (a.ro) az_replay_scatter_copies(a, a.ro, a.so, (long long)np, t);
+        return;
+    }
+    t -= (long long)a.rows * np;
+    if (t < a.rows) {
+        if (a.rsc) az_replay_scatter_copies(a, a.rsc, a.ssc, 1LL, t);
+        return;
+    }
+    t -= a.rows;
+    if (t < a.rows && a.rq) az_replay_scatter_copies(a, a.rq, a.sq, 1LL, t);
+}
+
 // Fused conv epilogue: 8 consecutive channels (16 B of bf16/fp16, 32 B of fp32) per work item, fp32 math, one rounding.
 struct BiasActArgs {
     void* y;
@@ -792,6 +891,10 @@ struct AzHandle {
     int8_t* harvest_own = nullptr;     // optional per-sample auxiliary outputs of azsp_harvest (azsp_harvest_aux)
     float* harvest_score = nullptr;
     float* harvest_rootq = nullptr;
+    float* harvest_surprise = nullptr;  // optional per-sample policy surprise outputs of azsp_harvest (azsp_harvest_surprise)
+    float* harvest_weight = nullptr;
+    double surprise_frac = 0.0;         // azsp_set_policy_surprise: the parameters of the harvest's game weights
+    int surprise_fast = 0;
     uint8_t* harvest_class = nullptr;  // optional per-sample search class output of azsp_harvest (azsp_harvest_search_class)
     int* d_gextra = nullptr;           // [d_games_cap][4] per-game extras (azsp_harvest_extra)
     int32_t* harvest_extra = nullptr;  // host destination of the extras, optional
@@ -814,6 +917,22 @@ template <int N, int GAME, class Op> int launch(const AzCfg& c, const AzMem& m, 
 int launch_dihedral(const DihedralArgs& a, long long total, void* stream);
 int launch_bias_act(const BiasActArgs& a, void* stream);
 int launch_replay_gather(const ReplayGatherArgs& a, long long total, void* stream);
+// weighted replay add: ofs[n + 1] = exclusive prefix of az_replay_copies (one workgroup), then the scatter over `total` source elements
+#if defined(__HIPCC__)
+int launch_replay_count(const float* weights, const double* unif, int* ofs, int n, void* stream);
+int launch_replay_scatter(const ReplayAddArgs& a, long long total, void* stream);
+#else
+// A build without the device compiler (the host twin of the CPU test tier) has no kernels: the two launches are the plain loops over the
+// same element functions, here, so that such a backend need not define them.
+inline int launch_replay_count(const float* weights, const double* unif, int* ofs, int n, void*) {
+    ofs[n] = az_replay_ofs(az_replay_count_range(weights, unif, ofs, 0, n, 0));
+    return 0;
+}
+inline int launch_replay_scatter(const ReplayAddArgs& a, long long total, void*) {
+    for (long long t = 0; t < total; ++t) az_replay_scatter_elem(a, t);
+    return 0;
+}
+#endif
 // exclusive scan of the staging-buffer lengths in rotated buffer order -> ofs[n2][2], counts[0..1] = samples / games handed out
 int launch_harvest_scan(const int* len, int* ofs, int* counts, int n2, int rot, int cap, int max_games, void* stream);
 // returns 0 ok, 1 unsupported shape, -1 launch error
@@ -1334,7 +1453,7 @@ int azsp_harvest(void* e, int8_t* states, float* pi, float* z, int32_t cap, int3
         return AZSP_EDEVICE;
     }
     OpHarvest op = {states, pi, z, cap, h->d_games, max_games, h->d_hofs, h->harvest_moves, h->d_gextra, h->harvest_class,
-                    h->harvest_own, h->harvest_score, h->harvest_rootq};
+                    h->harvest_own, h->harvest_score, h->harvest_rootq, h->harvest_surprise, h->harvest_weight, h->surprise_frac, h->surprise_fast};
     rc = az_run(h, op, stream);
     if (rc) return rc;
     int cnt[4];
@@ -1389,6 +1508,29 @@ int azsp_harvest_aux(void* e, int8_t* ownership_dev, float* score_dev, float* ro
     h->harvest_own = ownership_dev;
     h->harvest_score = score_dev;
     h->harvest_rootq = root_q_dev;
+    return AZSP_OK;
+}
+
+int azsp_set_policy_surprise(void* e, int32_t on, double frac, int32_t include_fast) {
+    AzHandle* h = (AzHandle*)e;
+    if (!h || h->cfg.stop_after_move || !(frac >= 0.0 && frac <= 1.0)) return AZSP_EINVAL;  // a drop-in engine records no samples
+    if (on && !h->mem.stg_surprise) {  // the first enabling call allocates the staging row: never a launch path
+        if (azb::set_device(h->pub.device) != 0) return AZSP_EDEVICE;  // the engine's device, as azsp_create selects it
+        h->mem.stg_surprise = az_new<float>(h, (size_t)h->cfg.G * 2 * h->cfg.stage_cap);  // (zero-initialised, like every engine allocation)
+        if (!h->mem.stg_surprise) return AZSP_ENOMEM;
+    }
+    h->cfg.surprise = on ? 1 : 0;  // AzCfg travels by value with every launch: the moves recorded after this call
+    h->surprise_frac = frac;       // the harvests after this call
+    h->surprise_fast = include_fast ? 1 : 0;
+    return AZSP_OK;
+}
+
+int azsp_harvest_surprise(void* e, float* surprise_dev, float* weight_dev) {
+    AzHandle* h = (AzHandle*)e;
+    if (!h) return AZSP_EINVAL;
+    if ((surprise_dev || weight_dev) && !h->mem.stg_surprise) return AZSP_EINVAL;  // never enabled: nothing staged
+    h->harvest_surprise = surprise_dev;
+    h->harvest_weight = weight_dev;
     return AZSP_OK;
 }
 
@@ -1616,6 +1758,23 @@ int azsp_replay_gather_aux(const int8_t* ring_states, const float* ring_pi, cons
     const bool aux = ring_own || ring_score || ring_root_q;
     const long long total = (long long)batch * ((long long)channels * n * n + A + 1 + (aux ? (long long)n * n + 2 : 0));
     return azb::launch_replay_gather(a, total, stream) == 0 ? AZSP_OK : AZSP_EDEVICE;
+}
+
+int azsp_replay_add_weighted(int8_t* ring_states, float* ring_pi, float* ring_z, int64_t capacity, int64_t added, const int8_t* src_states,
+                             const float* src_pi, const float* src_z, int32_t rows, int32_t channels, int32_t n, int32_t A, const float* weights,
+                             const double* uniforms, int8_t* ring_own, float* ring_score, float* ring_root_q, const int8_t* src_own,
+                             const float* src_score, const float* src_root_q, int32_t* ofs, void* stream) {
+    if (!ring_states || !ring_pi || !ring_z || !ofs || capacity < 1 || added < 0 || rows < 0 || channels < 1 || n < 1 || (A != n * n && A != n * n + 1))
+        return AZSP_EINVAL;
+    if (rows > 0 && (!src_states || !src_pi || !src_z || !weights || !uniforms)) return AZSP_EINVAL;
+    if (!ring_own != !src_own || !ring_score != !src_score || !ring_root_q != !src_root_q) return AZSP_EINVAL;  // a ring without its source, or the reverse
+    if (rows == 0) return azb::zero(ofs, sizeof(int32_t), stream) == 0 ? AZSP_OK : AZSP_EDEVICE;
+    if (azb::launch_replay_count(weights, uniforms, ofs, rows, stream)) return AZSP_EDEVICE;
+    ReplayAddArgs a = {ring_states, ring_pi, ring_z, src_states, src_pi, src_z, ofs, (long long)capacity, (long long)added, rows, channels, n, A,
+                       ring_own, ring_score, ring_root_q, src_own, src_score, src_root_q};
+    const bool aux = ring_own || ring_score || ring_root_q;
+    const long long total = (long long)rows * ((long long)channels * n * n + A + 1 + (aux ? (long long)n * n + 2 : 0));
+    return azb::launch_replay_scatter(a, total, stream) == 0 ? AZSP_OK : AZSP_EDEVICE;
 }
 
 int azsp_replay_gather(const int8_t* ring_states, const float* ring_pi, const float* ring_z, const int64_t* idx, int32_t batch, int32_t channels,

@@ -492,6 +492,31 @@ int azsp_set_aux_targets(void* engine, int32_t on);
  * enabled for the first time.  Buffers must stay valid for every later harvest. */
 int azsp_harvest_aux(void* engine, int8_t* ownership_dev, float* score_dev, float* root_q_dev);
 
+/* Policy surprise weighting (KataGo, Wu 2019, "Policy Surprise Weighting"; no counterpart in the reference actor: opt-in, off by default):
+ * how often each sample of a game is written into the training data follows how much its search's policy target disagrees with the
+ * network's own prior, while the number of rows per game stays what it was.  With the feature on, actor mode stages next to every sample
+ *   surprise = (float) max(KL, 0),  KL = sum over a with pi(a) > 0 of pi(a) (log pi(a) - log max((double)P(a), 1e-45)) + (Z > 0 ? log Z : 0),
+ * in float64, where pi is the float64 row the sample records (the plain policy at its temperature, the pruned target of forced playouts or
+ * the Gumbel pi': the surprise is measured on the target the learner is trained towards -- after warm-up the reference's sharpened
+ * policy), P the root's prior row as the evaluator returned it (float32, unmasked, before Dirichlet noise) and Z the sum of (double)P(a)
+ * over the actions legal at the root.  The sums are wave reductions; their order is not part of the contract.
+ * azsp_harvest computes the weights of every game it hands out from the game's staged rows k = 0 .. len - 1:
+ *   full_k = 1 unless row k was a fast move of the playout cap (all 1 with the cap off);  part_k = full_k or include_fast;
+ *   Nf = sum of full_k;  S = sum over k ascending with part_k of (double)surprise_k  (sequential, in row order);
+ *   w_k = S > 0 ? (1 - frac) full_k + (part_k ? frac Nf (double)surprise_k / S : 0) : full_k;   weight_k = (float)w_k,
+ * float64 in exactly this operation order.  The weights of a game sum to Nf up to rounding; frac = 0 gives weight == full; a game without
+ * surprise is weighted uniformly.  With include_fast a fast move whose cheap search found something the prior did not see earns a place.
+ * on != 0: the first such call allocates the staging row on the engine's device (and leaves it selected, like azsp_set_aux_targets).
+ * `on` holds for the moves recorded after the call (what was staged earlier, or with the feature off again, reads 0); frac and
+ * include_fast hold for the harvests after the call.  Actor mode only: AZSP_EINVAL with stop_after_move, and for frac outside [0, 1].
+ * states, pi, z, the game rows, the move log, azsp_get_search and every other output are what they are without this call.  The effect on
+ * playing strength is a training experiment; it has not been measured. */
+int azsp_set_policy_surprise(void* engine, int32_t on, double frac, int32_t include_fast);
+/* Optional outputs of azsp_harvest next to azsp_harvest_moves: surprise_dev and weight_dev float[sample_capacity] as defined above; each may
+ * be NULL (the default) on its own.  AZSP_EINVAL (any non-NULL) before the feature was enabled for the first time.  Buffers must stay
+ * valid for every later harvest. */
+int azsp_harvest_surprise(void* engine, float* surprise_dev, float* weight_dev);
+
 /* counters_host uint64[16]: simulations, best_child calls, backup edges, leaves, duplicate leaves, terminal hits,
  * moves, games, root evaluations, nodes created, game-rounds, buffer stalls, speculative record prefetches of the select phase and
  * how many of them were used. */
@@ -652,6 +677,20 @@ int azsp_replay_gather_aux(const int8_t* ring_states_dev, const float* ring_pi_d
                            int32_t channels, int32_t board_size, int32_t num_actions, int32_t op, int32_t state_dtype, void* out_states_dev,
                            float* out_pi_dev, float* out_z_dev, const int8_t* ring_own_dev, const float* ring_score_dev,
                            const float* ring_root_q_dev, float* out_own_dev, float* out_score_dev, float* out_root_q_dev, void* stream);
+/* Weighted append to the replay ring (policy surprise weighting; no counterpart in the reference: opt-in): source row i is written
+ *   c_i = floor(w_i) + (u_i < w_i - floor(w_i))
+ * times, w_i = weights_dev[i] widened to double and clamped to [0, 2^20] (a NaN or negative weight gives 0 copies), u_i = uniforms_dev[i],
+ * one float64 uniform in [0, 1) per row.  The copies go to the ring rows (added + ofs[i] + j) % capacity, j < c_i, ofs = the exclusive
+ * prefix of c: the rows the reference's per-transition loop would write for the source repeated c_i times (np.repeat), `added` = the rows
+ * written before this call.  If the copies outnumber the ring only the last `capacity` land.  Two launches on `stream`: one workgroup
+ * counts and scans into ofs_dev int32[rows + 1] (ofs_dev[rows] = the total, which the caller reads to advance `added`; prefixes saturate
+ * at INT32_MAX), then one flat kernel over the source elements reads each once and writes its copies.  The auxiliary ring / source pairs
+ * of azsp_harvest_aux may each be NULL (AZSP_EINVAL for a ring without its source or the reverse).  Layouts as azsp_replay_gather_aux. */
+int azsp_replay_add_weighted(int8_t* ring_states_dev, float* ring_pi_dev, float* ring_z_dev, int64_t capacity, int64_t added,
+                             const int8_t* src_states_dev, const float* src_pi_dev, const float* src_z_dev, int32_t rows, int32_t channels,
+                             int32_t board_size, int32_t num_actions, const float* weights_dev, const double* uniforms_dev, int8_t* ring_own_dev,
+                             float* ring_score_dev, float* ring_root_q_dev, const int8_t* src_own_dev, const float* src_score_dev,
+                             const float* src_root_q_dev, int32_t* ofs_dev, void* stream);
 
 /* Stem of the evaluator (core/network.py:98-108 conv_block: conv3x3 17 -> C + BatchNorm + ReLU) on the tiled layout: the
  * input is the feature tensor azsp_select writes with feature_dtype = AZSP_FEAT_BF16_TILED (2K+1 planes, 17 at num_stack K = 8,

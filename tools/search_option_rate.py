@@ -1,5 +1,5 @@
-"""What an opt-in rule of the actor (SearchOptions.of: playout_cap, leaf_symmetry, forced_playouts, gumbel; aux_targets)
-costs it.
+"""What an opt-in rule of the actor (SearchOptions.of: playout_cap, leaf_symmetry, forced_playouts, gumbel; aux_targets; policy_surprise;
+DESIGN 7.6 - 7.11) costs it.
 
 Runs the headline shape of bench.py (9x9 Go, 4096 games, 200 simulations, 8 leaves per round, 10 x 128 network, fp32-class
 evaluator) twice on the same build, with the same staggered openings and the same number of untimed and timed rounds: once with the
@@ -27,7 +27,12 @@ gumbel (--value M, default 16): select chooses the considered action in front of
 aux_targets (no value): the end of a move stores the root value, the end of a game the owner boards, every harvest (`--harvest-every`) writes
   and clones the three extra outputs.  The searches of the two runs are the same here: nothing but the extra outputs differs.
 
-    python tools/search_option_rate.py --option {playout_cap,leaf_symmetry,forced_playouts,gumbel,aux_targets} [--value ...] [--steps 300] [--preroll 200]
+policy_surprise (--value FRAC or FRAC,1 to include fast moves; default 0.5): the end of a move takes 2 A float64 logs and one wave
+  reduction, every harvest sums each game's surprises and writes two more outputs.  The searches of the two runs are the same.
+  `--replay-adds ROWS` (default 0 = skip) then times DeviceReplay.add_samples against add_samples(weights=) on ROWS random 9x9 rows
+  with weights around 1: a warm-up, then `--windows` windows of 10 calls each, microseconds per call with the spread between windows.
+
+    python tools/search_option_rate.py --option {playout_cap,leaf_symmetry,forced_playouts,gumbel,aux_targets,policy_surprise} [--value ...] [--steps 300] [--preroll 200]
 """
 import argparse
 import json
@@ -137,7 +142,53 @@ class AuxTargets(Extra):
         return dict(samples_harvested=self.samples)
 
 
-OPTIONS = dict(playout_cap=PlayoutCap, leaf_symmetry=LeafSymmetry, forced_playouts=ForcedPlayouts, gumbel=Gumbel, aux_targets=AuxTargets)
+class PolicySurprise(Extra):
+    samples, weight = 0, 0.0
+
+    @staticmethod
+    def parse(text):
+        frac, _, fast = (text or "0.5").partition(",")
+        return (float(frac), fast.strip() not in ("", "0"))
+
+    def after_harvest(self, z, games):
+        self.samples += int(z.shape[0])
+        if self.on:
+            assert self.act.last_harvest_weight.shape == z.shape
+            self.weight = self.weight + self.act.last_harvest_weight.sum()  # (a device scalar; read after the clock stops)
+
+    def row(self, cnt, dt):
+        return dict(samples_harvested=self.samples, weight_harvested=round(float(self.weight), 1))
+
+
+def replay_add_rate(args):
+    """add_samples against add_samples(weights=) on the same `--replay-adds` rows: microseconds per call, per window of 10 calls."""
+    from alpha_zero_amd.core.replay import DeviceReplay
+
+    n, rows, dev = args.board, args.replay_adds, torch.device("cuda")
+    g = torch.Generator().manual_seed(3)
+    st = (torch.rand(rows, 17, n, n, generator=g) > 0.6).to(torch.int8).to(dev)
+    pi = torch.rand(rows, n * n + 1, generator=g).to(dev)
+    z = torch.randint(-1, 2, (rows,), generator=g).float().to(dev)
+    w = (torch.rand(rows, generator=g) * 2).to(dev)  # mean 1: about as many rows written as the plain add writes
+    rep = DeviceReplay(1 << 18, np.random.RandomState(1), n, n * n + 1, device=dev)
+    out = {}
+    for name, kw in (("add_samples", {}), ("add_samples_weighted", dict(weights=w))):
+        for _ in range(5):
+            rep.add_samples(st, pi, z, **kw)
+        wins = []
+        for _ in range(args.windows):
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            for _ in range(10):
+                rep.add_samples(st, pi, z, **kw)
+            torch.cuda.synchronize(dev)
+            wins.append((time.perf_counter() - t0) / 10 * 1e6)
+        out[name] = dict(us_per_call=[round(v, 1) for v in wins], mean=round(float(np.mean(wins)), 1), spread=round(max(wins) - min(wins), 1))
+    print(json.dumps(dict(replay_adds=dict(rows=rows, **out))), flush=True)
+
+
+OPTIONS = dict(playout_cap=PlayoutCap, leaf_symmetry=LeafSymmetry, forced_playouts=ForcedPlayouts, gumbel=Gumbel, aux_targets=AuxTargets,
+               policy_surprise=PolicySurprise)
 
 
 def bench_line(tree, steps, warmup):
@@ -230,11 +281,15 @@ def main():
     ap.add_argument("--bench-steps", type=int, default=20)
     ap.add_argument("--bench-warmup", type=int, default=5)
     ap.add_argument("--no-on", action="store_true", help="only the off path against the parent")
+    ap.add_argument("--replay-adds", type=int, default=0, help="policy_surprise: rows of one replay add to time, plain against weighted (0 = skip)")
+    ap.add_argument("--windows", type=int, default=5)
     args = ap.parse_args()
     kind = OPTIONS[args.option]
     args.steps, args.preroll = args.steps or kind.steps, kind.preroll if args.preroll is None else args.preroll
     if args.parent:
         off_against_parent(args)
+    if args.replay_adds:
+        replay_add_rate(args)
     if args.no_on:
         return
     off = run(args, None)
