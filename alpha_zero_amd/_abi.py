@@ -39,7 +39,7 @@ SYMBOLS = [
     "azsp_set_budgets", "azsp_set_playout_cap", "azsp_harvest_search_class",
     "azsp_set_leaf_symmetry", "azsp_leaf_symmetries",
     "azsp_set_forced_playouts", "azsp_read_target_policies",
-    "azsp_set_gumbel", "azsp_read_gumbel_moves",
+    "azsp_set_gumbel", "azsp_read_gumbel_moves", "azsp_set_fpu",
     "azsp_set_aux_targets", "azsp_harvest_aux", "azsp_replay_gather_aux",
     "azsp_set_policy_surprise", "azsp_harvest_surprise", "azsp_replay_add_weighted",
 ]
@@ -100,6 +100,7 @@ class Binding:
             "azsp_set_leaf_symmetry": [V, I], "azsp_leaf_symmetries": [V, V, V],
             "azsp_set_forced_playouts": [V, C.c_double, I], "azsp_read_target_policies": [V, V, V],
             "azsp_set_gumbel": [V, I, C.c_double, C.c_double], "azsp_read_gumbel_moves": [V, V, V],
+            "azsp_set_fpu": [V, I, C.c_double, C.c_double],
             "azsp_set_aux_targets": [V, I], "azsp_harvest_aux": [V, V, V, V],
             "azsp_replay_gather_aux": [V, V, V, V, I, I, I, I, I, I, V, V, V, V, V, V, V, V, V, V],
             "azsp_set_policy_surprise": [V, I, C.c_double, I], "azsp_harvest_surprise": [V, V, V],

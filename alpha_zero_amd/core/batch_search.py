@@ -21,11 +21,12 @@ from .engine import Engine, EngineConfig, SearchOptions
 
 
 def dropin_engine(game, board_size, num_games, num_simulations, num_parallel, c_puct_base, c_puct_init, root_noise, komi=7.5, max_steps=0,
-                  num_to_win=5, num_stack=8, binding=None, device=None, leaf_symmetry=None, forced_playouts=None, gumbel=None):
+                  num_to_win=5, num_stack=8, binding=None, device=None, leaf_symmetry=None, forced_playouts=None, gumbel=None,
+                  fpu_reduction=None):
     """The engine of a drop-in search, `uct_search`'s with one game and a BatchSearch's with `capacity`: it stops after every move
     (`stop_after_move`), hands out int8 observation planes and logs no moves.  Without a `binding` it runs the product library on the GPU.
-    leaf_symmetry, forced_playouts, gumbel: SearchOptions.of."""
-    SearchOptions.of(leaf_symmetry, forced_playouts, gumbel=gumbel)  # ValueError before anything is built
+    leaf_symmetry, forced_playouts, gumbel, fpu_reduction: SearchOptions.of."""
+    SearchOptions.of(leaf_symmetry, forced_playouts, gumbel=gumbel, fpu_reduction=fpu_reduction)  # ValueError before anything is built
     if binding is None:
         from .. import _lib
 
@@ -33,7 +34,7 @@ def dropin_engine(game, board_size, num_games, num_simulations, num_parallel, c_
     cfg = EngineConfig(game=game, board_size=board_size, num_games=num_games, num_parallel=num_parallel, num_simulations=num_simulations,
                        c_puct_base=c_puct_base, c_puct_init=c_puct_init, root_noise=root_noise, komi=komi, max_steps=max_steps or 0,
                        num_to_win=num_to_win, num_stack=num_stack, stop_after_move=True, feature_dtype=_abi.FEAT_I8, log_moves=False,
-                       leaf_symmetry=leaf_symmetry, forced_playouts=forced_playouts, gumbel=gumbel)
+                       leaf_symmetry=leaf_symmetry, forced_playouts=forced_playouts, gumbel=gumbel, fpu_reduction=fpu_reduction)
     return Engine(binding, cfg, device=device)
 
 
@@ -228,13 +229,13 @@ class BatchSearch:
 
     def __init__(self, game, board_size, capacity, num_simulations, num_parallel=1, c_puct_base=19652.0, c_puct_init=1.25, root_noise=False,
                  komi=7.5, max_steps=0, num_to_win=5, num_stack=8, binding=None, device=None, leaf_symmetry=None, forced_playouts=None,
-                 gumbel=None):
-        """leaf_symmetry, forced_playouts, gumbel: SearchOptions.of.  What they mean here: with gumbel the move to commit is
+                 gumbel=None, fpu_reduction=None):
+        """leaf_symmetry, forced_playouts, gumbel, fpu_reduction: SearchOptions.of.  What they mean here: with gumbel the move to commit is
         `results().gumbel_move` and the sample to record `results().target_pi`; `search(noise=...)` takes the Gumbel(0, 1) rows (None:
         drawn here with np.random.gumbel) and root_noise is ignored.  With forced_playouts the move is still to be chosen from
         `results().pi`, the sample to record is `results().target_pi` (None when both are off).  Under leaf_symmetry `eval_func` --
         host callback or resident evaluator -- is handed every leaf position under that board symmetry."""
-        opt = SearchOptions.of(leaf_symmetry, forced_playouts, gumbel=gumbel)
+        opt = SearchOptions.of(leaf_symmetry, forced_playouts, gumbel=gumbel, fpu_reduction=fpu_reduction)
         if capacity < 1:
             raise ValueError(f"capacity must be at least 1, got {capacity}")
         check_num_simulations(num_simulations)
@@ -242,16 +243,18 @@ class BatchSearch:
         self.game, self.capacity, self.num_simulations, self.num_parallel = game, int(capacity), int(num_simulations), int(num_parallel)
         self.key = _key(game, board_size, komi, max_steps, num_to_win, num_stack)
         self.eng = dropin_engine(game, board_size, self.capacity, num_simulations, num_parallel, c_puct_base, c_puct_init, root_noise, komi,
-                                 max_steps, num_to_win, num_stack, binding, device, leaf_symmetry, forced_playouts, gumbel)
+                                 max_steps, num_to_win, num_stack, binding, device, leaf_symmetry, forced_playouts, gumbel, fpu_reduction)
         self.slots = np.zeros(0, dtype=np.int64)  # the active slots (a position is loaded, or a sub-tree was kept), ascending
         self._status = np.full(self.capacity, _abi.ST_IDLE, dtype=np.int32)  # host mirror of the slots' status after load / search / commit
         self._budgets_set = False  # an earlier search left per-slot budgets in the engine (search(num_simulations=...))
 
     @classmethod
-    def for_env(cls, env, capacity, num_simulations, num_parallel=1, c_puct_base=19652.0, c_puct_init=1.25, root_noise=False):
-        """A BatchSearch for positions of `env`'s game, board size, komi / max_steps / num_to_win and num_stack, on `env`'s backend."""
+    def for_env(cls, env, capacity, num_simulations, num_parallel=1, c_puct_base=19652.0, c_puct_init=1.25, root_noise=False,
+                fpu_reduction=None):
+        """A BatchSearch for positions of `env`'s game, board size, komi / max_steps / num_to_win and num_stack, on `env`'s backend.
+        fpu_reduction: SearchOptions.of."""
         return cls(capacity=capacity, num_simulations=num_simulations, num_parallel=num_parallel, c_puct_base=c_puct_base, c_puct_init=c_puct_init,
-                   root_noise=root_noise, **env_settings(env))
+                   root_noise=root_noise, fpu_reduction=fpu_reduction, **env_settings(env))
 
     def close(self):
         if self.eng is not None:

@@ -56,7 +56,8 @@ class EngineConfig:
     device_index: int = 0
     leaf_symmetry: object = None     # the opt-in search rules, as SearchOptions.of takes them: None | "random" | 0..7,
     forced_playouts: object = None   # None | k >= 0,
-    gumbel: object = None            # None | m | (m, c_visit, c_scale)
+    gumbel: object = None            # None | m | (m, c_visit, c_scale),
+    fpu_reduction: object = None     # None | r | (r_tree, r_root)
     aux_targets: bool = False        # auxiliary training targets per sample (Engine.set_aux_targets; harvest(with_aux=True))
     policy_surprise: object = None   # policy surprise weighting (Engine.set_policy_surprise; harvest(with_surprise=True)): None | frac | (frac, include_fast)
 
@@ -99,6 +100,21 @@ def gumbel_params(gumbel):
     raise ValueError(f"gumbel must be None (off), an integer m >= 0 or (m, c_visit, c_scale) with finite c_visit, c_scale >= 0, got {gumbel!r}")
 
 
+def fpu_params(value):
+    """The azsp_set_fpu arguments (on, r_tree, r_root) of an `fpu_reduction` value: None = off, a finite number r >= 0 = that reduction
+    at every node, or (r_tree, r_root) = below the root and at it (KataGo: (0.2, 0.1)).  0 is on: an unvisited child is then worth its
+    parent's value.  Anything else raises ValueError naming these."""
+    is_num = lambda v: (not isinstance(v, (bool, str, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating))  # noqa: E731
+                        and math.isfinite(float(v)) and float(v) >= 0.0)
+    if value is None:
+        return 0, 0.0, 0.0
+    if is_num(value):
+        return 1, float(value), float(value)
+    if isinstance(value, (tuple, list)) and len(value) == 2 and is_num(value[0]) and is_num(value[1]):
+        return 1, float(value[0]), float(value[1])
+    raise ValueError(f"fpu_reduction must be None (off), a finite number r >= 0 or (r_tree, r_root) of two such numbers, got {value!r}")
+
+
 def policy_surprise_params(value):
     """The azsp_set_policy_surprise arguments (on, frac, include_fast) of a `policy_surprise` value: None = off, a number frac in [0, 1]
     = on with that share of every game's weight handed out by surprise (fast moves of a playout cap take no part), or
@@ -120,15 +136,17 @@ EXCLUSIVE = "gumbel and forced_playouts cannot be on together: both decide what 
 @dataclass(frozen=True)
 class SearchOptions:
     """The opt-in search rules of one engine, validated: what EngineConfig, dropin_engine, BatchSearch, SelfPlayActor and
-    run_selfplay_actor_loop take as `leaf_symmetry`, `forced_playouts`, `prune_policy_target`, `gumbel` and `playout_cap`."""
+    run_selfplay_actor_loop take as `leaf_symmetry`, `forced_playouts`, `prune_policy_target`, `gumbel`, `playout_cap` and `fpu_reduction`."""
     leaf_symmetry: object = None         # as given: None | "random" | 0..7
     forced_k: float = 0.0                # 0.0 = off
     prune_policy_target: bool = True
     gumbel: tuple = (0, 50.0, 1.0)       # (m, c_visit, c_scale), m = 0 = off
     playout_cap: object = None           # None | (fast_simulations, full_prob)
+    fpu: tuple = (0, 0.0, 0.0)           # (on, r_tree, r_root)
 
     @classmethod
-    def of(cls, leaf_symmetry=None, forced_playouts=None, prune_policy_target=True, gumbel=None, playout_cap=None, num_simulations=None):
+    def of(cls, leaf_symmetry=None, forced_playouts=None, prune_policy_target=True, gumbel=None, playout_cap=None, num_simulations=None,
+           fpu_reduction=None):
         """The one place these values are checked (ValueError naming the allowed ones); the reference search has none of the rules and
         all are off by default.
         leaf_symmetry: None, "random" or an op 0..7 (Engine.set_leaf_symmetry): every leaf position is evaluated under that board
@@ -144,9 +162,12 @@ class SearchOptions:
         and records softmax(logits + sigma(completed Q)) as the pi row.  Not together with forced_playouts.
         playout_cap: None or (fast_simulations, full_prob) (Engine.set_playout_cap; the batched actor only): a move is a full search
         (the slot's budget, root noise) with probability full_prob, else a fast one of fast_simulations (1..num_simulations, the upper
-        end checked where `num_simulations` is given) without noise that only moves the game on."""
+        end checked where `num_simulations` is given) without noise that only moves the game on.
+        fpu_reduction: None, r or (r_tree, r_root), finite and >= 0 (Engine.set_fpu_reduction; first-play urgency reduction as in Leela
+        Zero and KataGo, (0.2, 0.1) there): an unvisited child is scored with its parent's own value minus r sqrt(prior mass of the
+        visited children) in place of a draw.  Every search follows it, fast moves too; under gumbel it holds below the root."""
         leaf_symmetry_mode(leaf_symmetry)
-        k, g = forced_playouts_k(forced_playouts), gumbel_params(gumbel)
+        k, g, fpu = forced_playouts_k(forced_playouts), gumbel_params(gumbel), fpu_params(fpu_reduction)
         if g[0] > 0 and k > 0.0:
             raise ValueError(EXCLUSIVE)
         if playout_cap is not None:
@@ -155,7 +176,7 @@ class SearchOptions:
             if isinstance(fast, bool) or not isinstance(fast, (int, np.integer)) or not 1 <= fast <= top or not 0.0 <= float(prob) <= 1.0:
                 raise ValueError(f"playout_cap must be (fast_simulations in 1..{num_simulations}, full_prob in [0, 1]), got {playout_cap!r}")
             playout_cap = (int(fast), float(prob))
-        return cls(leaf_symmetry, k, bool(prune_policy_target), g, playout_cap)
+        return cls(leaf_symmetry, k, bool(prune_policy_target), g, playout_cap, fpu)
 
 
 MAX_NUM_STACK = 8  # the engine's history ring holds 8 boards (include/azsp.h AzspConfig.num_stack)
@@ -182,8 +203,9 @@ class Engine:
     """One engine = G concurrent games on one device.  `binding` comes from alpha_zero_amd._lib.load()."""
 
     def __init__(self, binding: Binding, cfg: EngineConfig, device="cuda", prune_policy_target=True, playout_cap=None):
-        """cfg.leaf_symmetry / .forced_playouts / .gumbel, prune_policy_target and playout_cap: SearchOptions.of."""
-        opt = SearchOptions.of(cfg.leaf_symmetry, cfg.forced_playouts, prune_policy_target, cfg.gumbel, playout_cap, cfg.num_simulations)
+        """cfg.leaf_symmetry / .forced_playouts / .gumbel / .fpu_reduction, prune_policy_target and playout_cap: SearchOptions.of."""
+        opt = SearchOptions.of(cfg.leaf_symmetry, cfg.forced_playouts, prune_policy_target, cfg.gumbel, playout_cap, cfg.num_simulations,
+                               cfg.fpu_reduction)
         self.b, self.cfg, self.device = binding, cfg, torch.device(device)
         self.on_launch = None
         check_num_stack(cfg.num_stack)
@@ -238,6 +260,9 @@ class Engine:
             self.set_gumbel(opt.gumbel)
         if opt.playout_cap is not None:
             self.set_playout_cap(*opt.playout_cap)  # before the first root: the first move of every game draws its class too
+        self.fpu_reduction = None  # what is on now: None or (r_tree, r_root)
+        if opt.fpu[0]:
+            self.set_fpu_reduction(opt.fpu[1:])  # before the first select
         self.aux_targets = False  # has been on at least once, so the staging rows exist (harvest(with_aux=True))
         self._harvest_aux_bufs = None
         if cfg.aux_targets:
@@ -486,6 +511,16 @@ class Engine:
         self._ck(self.b.dll.azsp_set_gumbel(self.h, m, C.c_double(cv), C.c_double(cs)), "azsp_set_gumbel")
         self._gumbel_m = m
         self.gumbel = self.gumbel or m > 0
+
+    def set_fpu_reduction(self, value):
+        """First-play urgency reduction (azsp_set_fpu; Leela Zero, KataGo; the reference search scores an unvisited child as a draw):
+        None = off, r or (r_tree, r_root) = at a node with value Q = W / N an unvisited child takes Q - r sqrt(sum of the priors of the
+        visited children) in place of -q, with r_root at the root of the search and r_tree below it; 0 is on (the parent's value).  A
+        visited child, the u term, the mask and the tie-break are untouched.  Holds for the selections from now on, a search in progress
+        included; fast moves of the playout cap follow it, a Gumbel root does below the root."""
+        on, rt, rr = fpu_params(value)
+        self._ck(self.b.dll.azsp_set_fpu(self.h, on, C.c_double(rt), C.c_double(rr)), "azsp_set_fpu")
+        self.fpu_reduction = (rt, rr) if on else None
 
     def set_aux_targets(self, on=True):
         """Auxiliary training targets per sample (azsp_set_aux_targets; KataGo, Wu 2019, 4.1; the reference actor has none): the

@@ -167,7 +167,7 @@ class DeviceEvaluator:
 
 
 def play_eval_games_parallel(game, board_size, players, num_simulations, num_parallel, c_puct_base, c_puct_init, komi=7.5, num_to_win=5,
-                             binding=None, device="cuda", max_rounds=1 << 20, openings=None, num_stack=8):
+                             binding=None, device="cuda", max_rounds=1 << 20, openings=None, num_stack=8, fpu_reduction=None):
     """SURVEY 8f-2 "many in parallel": G evaluation games of pipeline.py:815-867 advance in lock-step on ONE engine.
 
     players: one (black_eval, white_eval) pair per game; eval(states int8[B,2K+1,N,N], True) -> (list of pi, list of v) with the
@@ -179,13 +179,15 @@ def play_eval_games_parallel(game, board_size, players, num_simulations, num_par
     (only the G side-to-move flags do).  openings: optional list of G move lists played (env.step) before the first search, e.g.
     random openings for a match between two evaluators.  Returns per game dict(moves, game_length, game_result, num_passes, winner)
     -- the same games, move for move, as G sequential calls (tests/arena_checks.py); `moves` includes the opening moves.
-    num_stack: history boards per observation (K, 1..8); an evaluator that knows its network's input planes (`in_channels`) must take 2K+1."""
+    num_stack: history boards per observation (K, 1..8); an evaluator that knows its network's input planes (`in_channels`) must take 2K+1.
+    fpu_reduction: None, r or (r_tree, r_root) (SearchOptions.of): both players of every game search under that first-play urgency reduction."""
     import torch
 
     from .. import _abi, _lib
-    from .engine import Engine, EngineConfig
+    from .engine import Engine, EngineConfig, SearchOptions
     from .pipeline import game_stats_from_row
 
+    SearchOptions.of(fpu_reduction=fpu_reduction)  # ValueError before anything is built
     binding = binding or _lib.load(require_gpu=True)
     G = len(players)
     for pair in players:
@@ -196,7 +198,7 @@ def play_eval_games_parallel(game, board_size, players, num_simulations, num_par
     cfg = EngineConfig(game=game, board_size=board_size, num_games=G, num_parallel=num_parallel, num_simulations=num_simulations,
                        c_puct_base=c_puct_base, c_puct_init=c_puct_init, root_noise=False, deterministic=True, reuse_tree=False, warm_up_steps=-1,
                        komi=komi, num_to_win=num_to_win, resign_threshold=-1.0, stop_at_game_end=True, feature_dtype=_abi.FEAT_I8,
-                       num_stack=num_stack)
+                       num_stack=num_stack, fpu_reduction=fpu_reduction)
     eng = Engine(binding, cfg, device=device)
     try:
         eng.reset_games()
@@ -282,7 +284,8 @@ def play_eval_games_parallel(game, board_size, players, num_simulations, num_par
 def eval_many_against_prev_ckpt(game, board_size, players, elos, num_simulations, num_parallel, c_puct_base, c_puct_init, **kw):
     """G evaluation games at once + the Elo bookkeeping of eval_against_prev_ckpt applied in game order: `elos` is one (black_elo,
     white_elo) pair of EloRating objects per game (the same objects may appear in several games, e.g. one checkpoint against its
-    predecessor G times).  Returns the list of stats dicts (the evaluation.csv columns, pipeline.py:851-866)."""
+    predecessor G times).  Returns the list of stats dicts (the evaluation.csv columns, pipeline.py:851-866).  kw: the keywords of
+    play_eval_games_parallel, among them fpu_reduction=None | r | (r_tree, r_root): both players of every game search under it."""
     res = play_eval_games_parallel(game, board_size, players, num_simulations, num_parallel, c_puct_base, c_puct_init, **kw)
     black_id = 1
     out = []

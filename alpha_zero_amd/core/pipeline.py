@@ -115,7 +115,7 @@ class SelfPlayActor:
                  use_graph=True, training_steps=0, binding=None, root_noise=True, deterministic=False, tiled_features=None, engine_kw=None,
                  use_split_evaluator=True, auto_widen=None, num_stack=8, split_any_board=False, playout_cap=None,
                  leaf_symmetry=None, forced_playouts=None, prune_policy_target=True, gumbel=None, aux_targets=False,
-                 policy_surprise=None):
+                 policy_surprise=None, fpu_reduction=None):
         """net_dtype: precision class of the leaf evaluator.  The default is the REFERENCE'S: fp32 (pipeline.py:91-123 evaluates in fp32,
         no autocast anywhere) -- on the hand-written split-precision kernels (hi + lo f16 pairs, three MFMA products, fp32 accumulation:
         include/azsp.h azsp_conv3x3_split) for 9x9 x {128, 64} and 13x13 Gomoku x 64 networks, on library fp32 convolutions (announced
@@ -132,7 +132,7 @@ class SelfPlayActor:
         the caller disabled the kernels' feature layouts); True / False force it.
         num_stack: history boards per observation (the env's num_stack, 1..8): the engine writes 2 * num_stack + 1 planes, which must be
         the network's input channels.
-        playout_cap, leaf_symmetry, forced_playouts, prune_policy_target, gumbel: the opt-in search rules, SearchOptions.of.  Under a
+        playout_cap, leaf_symmetry, forced_playouts, prune_policy_target, gumbel, fpu_reduction: the opt-in search rules, SearchOptions.of.  Under a
         playout cap every move is recorded; `harvest()` hands the learner the full-search samples only, `harvest_tensors()` leaves the
         flags in `last_harvest_full`.
         aux_targets: True = every sample carries the auxiliary training targets (Engine.set_aux_targets: ownership of the final position,
@@ -143,11 +143,13 @@ class SelfPlayActor:
         `last_harvest_surprise` / `last_harvest_weight`, and `DeviceReplay.add_harvest(weights=actor.last_harvest_weight)` writes every
         row as often as its weight says -- with include_fast also the fast moves of a playout cap that `keep=last_harvest_full` drops.
         Off by default; not with a drop-in engine (ValueError)."""
-        opt = SearchOptions.of(leaf_symmetry, forced_playouts, prune_policy_target, gumbel, playout_cap, num_simulations)  # ValueError before anything is built
+        opt = SearchOptions.of(leaf_symmetry, forced_playouts, prune_policy_target, gumbel, playout_cap, num_simulations,
+                               fpu_reduction)  # ValueError before anything is built
         from .. import _lib
 
         self.leaf_symmetry, self.forced_playouts, self.prune_policy_target = opt.leaf_symmetry, opt.forced_k, opt.prune_policy_target
         self.gumbel, self.playout_cap = opt.gumbel if gumbel is not None else None, opt.playout_cap
+        self.fpu_reduction = opt.fpu[1:] if opt.fpu[0] else None
         self.num_stack = check_num_stack(num_stack)
         check_input_channels(network, self.num_stack)
 
@@ -180,7 +182,7 @@ class SelfPlayActor:
                            else _abi.FEAT_F16_SPLIT if self.split_features else _FEAT_OF[net_dtype]),
             training_steps=training_steps, seed=seed, rank=rank, num_stack=self.num_stack,
             device_index=self.device.index or 0, leaf_symmetry=leaf_symmetry,  # (set before the first root is selected)
-            forced_playouts=forced_playouts, gumbel=gumbel)
+            forced_playouts=forced_playouts, gumbel=gumbel, fpu_reduction=fpu_reduction)
         for k, v in (engine_kw or {}).items():  # further EngineConfig fields (move logs, max_plies, ...: tests and diagnostics)
             if not hasattr(self.cfg, k):
                 raise TypeError(f"unknown engine option {k}")
@@ -432,13 +434,14 @@ def run_selfplay_actor_loop(seed, rank, network, device, data_queue, env, num_si
                             warm_up_steps, check_resign_after_steps, disable_resign_ratio, save_sgf_dir=None, save_sgf_interval=0,
                             logs_dir=None, load_ckpt=None, log_level="INFO", var_ckpt=None, var_resign_threshold=None,
                             ckpt_event=None, stop_event=None, num_games=4096, net_dtype=torch.float32, harvest_every=64, binding=None,
-                            playout_cap=None, leaf_symmetry=None, forced_playouts=None, gumbel=None):
+                            playout_cap=None, leaf_symmetry=None, forced_playouts=None, gumbel=None, fpu_reduction=None):
     """Same role and argument list as the reference actor entry point (pipeline.py:166-189), extended by
     `num_games`: one call drives `num_games` games on `device` and puts (game_seq, stats) tuples on
     `data_queue` exactly as `num_games` reference actors would.  `net_dtype` defaults to the reference's evaluator precision (fp32,
-    see SelfPlayActor).  `playout_cap`, `leaf_symmetry`, `forced_playouts`, `gumbel`: the opt-in search rules, SearchOptions.of; under a
+    see SelfPlayActor).  `playout_cap`, `leaf_symmetry`, `forced_playouts`, `gumbel`, `fpu_reduction`: the opt-in search rules, SearchOptions.of; under a
     playout cap the queued game_seq hold the full-search samples only, and the queued pi rows are the rule's policy targets."""
-    SearchOptions.of(leaf_symmetry, forced_playouts, gumbel=gumbel, playout_cap=playout_cap, num_simulations=num_simulations)
+    SearchOptions.of(leaf_symmetry, forced_playouts, gumbel=gumbel, playout_cap=playout_cap, num_simulations=num_simulations,
+                     fpu_reduction=fpu_reduction)
     import os
 
     game = "go" if env.has_pass_move else "gomoku"
@@ -454,7 +457,7 @@ def run_selfplay_actor_loop(seed, rank, network, device, data_queue, env, num_si
                           resign_threshold=thr, komi=getattr(env, "komi", 7.5), num_to_win=getattr(env, "num_to_win", 5),
                           seed=seed, rank=rank, device=device, net_dtype=net_dtype, training_steps=training_steps, binding=binding,
                           num_stack=getattr(env, "num_stack", 8), playout_cap=playout_cap, leaf_symmetry=leaf_symmetry,
-                          forced_playouts=forced_playouts, gumbel=gumbel)
+                          forced_playouts=forced_playouts, gumbel=gumbel, fpu_reduction=fpu_reduction)
     actor.drop_clamped_games = True  # the learner never sees a game that ran on a clamping evaluator (the reference's fp32 has no range)
     writer = None
     if logs_dir:  # per-actor statistics file with the reference's columns (pipeline.py:196, :268-271; logs/go/9x9/actor0.csv)

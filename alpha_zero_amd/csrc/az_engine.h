@@ -612,6 +612,59 @@ template <class Wv, int N, int GAME> struct Engine {
         });
     }
 
+    // First-play urgency reduction (azsp_set_fpu; include/azsp.h states the rule): puct_argmax with the value of an unvisited child
+    // replaced.  qself = Q_self of the node r (descend<true> hands it down), red = r_root at the root of the search, r_tree below it.
+    // on (wave-uniform): an unvisited child (N = 0) takes fpu - W in place of -q, with fpu = qself - red * sqrt(mass) and mass = the
+    // float64 sum of the priors of the visited children -- the prior the u term uses --, a lane's own elements in ascending lane + 64 j,
+    // then the butterfly of Wave::sum_f64.  At a noisy root the float64 fpu enters the float64 sum, everywhere else it is rounded to
+    // float32 once.  !on: every expression is puct_argmax's.  Only select<GUM, true> (OpSelectFpu, OpSelectGumbelFpu) reaches this function: the one more
+    // wave reduction and the three wave-uniform values do not fit the 128 VGPRs of the plain 9x9 select kernel (forced_child).
+    AZ_HD int puct_argmax_fpu(const SR& r, bool at_root, double pbc64, float sq32, bool on, double red, double qself) {
+        const S& s = hdr_of(r).st;
+        const float pbc32 = (float)pbc64;
+        const bool noisy = at_root && hs_noisy;
+        u64 lg[W];
+        for (int i = 0; i < W; ++i) lg[i] = Wv::uni(s.legal[i]);
+        const bool pass_ok = GAME == AZ_GO && !(Wv::uni((int)s.flags) & AZF_TERMINAL);
+        cnt[AZC_NODE_VISITS]++;
+        double fpu64 = 0.0;
+        if (on) {
+            const double mass = Wv::sum_f64([&](int lane) -> double {
+                double part = 0.0;
+                for (int j = 0; j < EPL; ++j) {
+                    const int a = lane + 64 * j;
+                    if (a < A && r.rN[a] > 0.0f) part = part + (noisy ? sc.rP64[a] : (double)r.rP[a]);
+                }
+                return part;
+            });
+            fpu64 = qself - red * sqrt(mass);
+        }
+        const float fpu32 = (float)fpu64;
+        return Wv::argmax_first([&](int lane, double& best, int& bi) {
+            for (int j = 0; j < EPL; ++j) {
+                const int a = lane + 64 * j;
+                if (a >= A) continue;
+                if (!(a < NP ? (j < W && ((lg[j < W ? j : 0] >> lane) & 1ull) != 0) : pass_ok)) continue;
+                const float n = r.rN[a], w = r.rW[a];
+                const float q = w / (n > 0.0f ? n : 1.0f);
+                const float rr = sq32 / (1.0f + n);
+                const bool plain = n > 0.0f || !on;
+                double sco;
+                if (noisy) {
+                    const double u = (pbc64 * sc.rP64[a]) * (double)rr;
+                    sco = (plain ? (double)(-q) : fpu64 - (double)w) + u;
+                } else {
+                    const float u = (pbc32 * r.rP[a]) * rr;
+                    sco = (double)((plain ? -q : fpu32 - w) + u);
+                }
+                if (bi < 0 || sco > best) {
+                    best = sco;
+                    bi = a;
+                }
+            }
+        });
+    }
+
     // Forced playouts (KataGo, Wu 2019, 3.2) at the root: with n_eff(a) = N(a) + v(a) -- v(a) = leaves of the current batch whose path starts
     // with a (sc.fv): virtual loss touches W only, so the in-flight descents are counted here -- and T_eff = sum N + leaves of the batch,
     // a legal child is forced when n_eff > 0 and n_eff^2 < (k P(a)) T_eff, in float64 as written (no square root).  P(a) is the prior the
@@ -743,7 +796,11 @@ template <class Wv, int N, int GAME> struct Engine {
 
     // One descent from the root.  Returns 0 = leaf reached (unexpanded, non-terminal), 1 = terminal.
     // On return `leaf_state` holds the leaf's position (used for the observation planes).
-    AZ_HD int descend(int& node_out, int& depth_out, S& leaf_state) {
+    // FPU (select<GUM, true> only): every arg-max is puct_argmax_fpu, with Q_self of the node it is at -- Tree.Q of the oracle: the root's
+    // W / N as Python floats while it is fresh and as np.float32 after a re-root, below the root the float32 W / N of the edge the
+    // descent came by, 0 without a visit -- and r_root at depth 0, r_tree below.  A Gumbel root chooses by gumbel_child(): no rule there.
+    template <bool FPU = false> AZ_HD int descend(int& node_out, int& depth_out, S& leaf_state, int fpu_on = 0, double fpu_tree = 0.0,
+                                                  double fpu_root = 0.0) {
         const int root = hs_root;
         int node = root, depth = 0, n_self = hs_rootN;
         if (hs_tabN != hs_rootN) {  // the root's table entries change only when its visit count does (terminal backups)
@@ -759,9 +816,16 @@ template <class Wv, int N, int GAME> struct Engine {
         // writes a node record between the prefetch and its use (one wave owns the game), so a stale hint merely wastes a load.
         int cur_is_nxt = 0;   // which LDS record holds `node` at levels >= 1: 0 = sc.cur, 1 = sc.nxt
         int spec = -1;        // node whose record sits in the OTHER record (valid when >= 0)
+        double qself = 0.0;
+        if (FPU && hs_rootN > 0) qself = hs_fresh ? hs_rootW / (double)hs_rootN : (double)((float)hs_rootW / (float)hs_rootN);
         for (;;) {
             const SR& r = depth == 0 ? sc.root : (cur_is_nxt ? sc.nxt : sc.cur);  // the root record lives in LDS for the whole round
-            int mv = puct_argmax(r, depth == 0, pbc64, sq32);
+            int mv;
+            if (FPU)
+                mv = puct_argmax_fpu(r, depth == 0, pbc64, sq32, fpu_on && !(depth == 0 && hs_noisy == AZ_ROOT_GUMBEL), depth == 0 ? fpu_root : fpu_tree,
+                                     qself);
+            else
+                mv = puct_argmax(r, depth == 0, pbc64, sq32);
             if (depth == 0) {  // forced playouts (select()): a forced child of the root goes first
                 const int f = Wv::uni(sc.fsel);
                 mv = f >= 0 ? f : mv;
@@ -770,6 +834,10 @@ template <class Wv, int N, int GAME> struct Engine {
             const int hint = Wv::uni((int)r.rH[mv]);
             n_self = Wv::uni((int)r.rN[mv]);
             table_entry(n_self, false, pbc64, sq32);  // the child's pb_c / sqrt: in flight while its record is staged
+            if (FPU) {
+                const float wsel = Wv::uni(r.rW[mv]), nsel = Wv::uni(r.rN[mv]);
+                qself = nsel > 0.0f ? (double)(wsel / nsel) : 0.0;
+            }
             if (Wv::first()) {
                 if (depth < AZ_PATH_CAP) {
                     sc.path[depth] = (node << 16) | mv;
@@ -1004,7 +1072,11 @@ template <class Wv, int N, int GAME> struct Engine {
     // ---- select phase -------------------------------------------------------------------------
     // GUM: the Gumbel root rule is compiled in.  The batched actor's select kernel has no register to spare (forced_child), so the rule
     // lives in an instantiation of its own (OpSelectGumbel), launched once the mode has been enabled; select<false> is the kernel it was.
-    template <bool GUM> AZ_HD void select(void* feat, unsigned char* valid) {
+    // FPU: the first-play urgency reduction is compiled in (puct_argmax_fpu), for the same reason in instantiations of its own
+    // (OpSelectFpu = select<false, true>, OpSelectGumbelFpu = select<true, true>; they carry the rule's three values, so that AzCfg and
+    // with it every kernel's argument block stay as they were), launched once azsp_set_fpu has enabled the rule; with fpu_on = 0 they
+    // select what select<GUM, false> selects.
+    template <bool GUM, bool FPU = false> AZ_HD void select(void* feat, unsigned char* valid, int fpu_on = 0, double fpu_tree = 0.0, double fpu_root = 0.0) {
         unsigned char* vrow = valid + (size_t)g * c.P;
         if (Wv::first()) {
             sc.free_base = -(1 << 30);  // no staged free-stack window yet
@@ -1114,7 +1186,7 @@ template <class Wv, int N, int GAME> struct Engine {
                     if (Wv::first()) sc.fsel = f;
                     Wv::sync();
                 }
-                const int term = descend(node, depth, leaf);
+                const int term = descend<FPU>(node, depth, leaf, fpu_on, fpu_tree, fpu_root);
                 cnt[AZC_SIMS]++;
                 if (term) {
                     // mcts_v2.py:407-411 / :604-608: back up -reward, node stays unexpanded

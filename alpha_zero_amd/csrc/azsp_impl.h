@@ -89,6 +89,30 @@ struct OpSelectGumbel {
         e.flush_counters();
     }
 };
+// OpSelect with the first-play urgency reduction compiled in (azsp_set_fpu), and the rule's values: on = 0 selects as OpSelect does
+struct OpSelectFpu {
+    void* feat;
+    unsigned char* valid;
+    int on;
+    double r_tree, r_root;
+    template <class E> AZ_HD void operator()(E& e) const {
+        e.template select<false, true>(feat, valid, on, r_tree, r_root);
+        e.cnt[AZC_ROUNDS]++;
+        e.flush_counters();
+    }
+};
+// ... and OpSelectGumbel with it: an engine that has enabled both rules
+struct OpSelectGumbelFpu {
+    void* feat;
+    unsigned char* valid;
+    int on;
+    double r_tree, r_root;
+    template <class E> AZ_HD void operator()(E& e) const {
+        e.template select<true, true>(feat, valid, on, r_tree, r_root);
+        e.cnt[AZC_ROUNDS]++;
+        e.flush_counters();
+    }
+};
 struct OpBeginMove {
     int warm;
     template <class E> AZ_HD void operator()(E& e) const {
@@ -135,6 +159,8 @@ struct OpStatus {
 // does not matter for the handful of games of a drop-in caller).  priors / values may live in page-locked HOST memory (read over PCIe:
 // a few hundred bytes); status / q / valid / fault flags / the leaves' observation planes are written straight to page-locked host
 // memory: the host needs one launch and one stream synchronisation per call, no copy commands.
+// TWIN: OpDropinStepFpu below repeats this body with another select instantiation -- a change here (the read-back, the fault word) goes
+// into both.
 struct OpDropinStep {
     const float* priors;  // null: first call of a search (nothing to back up)
     const float* values;
@@ -171,6 +197,40 @@ struct OpDropinStep {
         for (long long b0 = 0; b0 < n; b0 += AZ_WAVE)
             E::Wave::lanes([&](int lane) {
                 if (b0 + lane < n) feat_out[lo + b0 + lane] = src[b0 + lane];
+            });
+    }
+};
+// OpDropinStep once azsp_set_fpu has enabled the rule (as OpSelectFpu stands for OpSelect).  The body is OpDropinStep's with the other
+// select instantiation, written out a second time: routing both through one member template changed OpDropinStep's instruction stream.
+struct OpDropinStepFpu {
+    OpDropinStep s;
+    int on;
+    double r_tree, r_root;
+    template <class E> AZ_HD void operator()(E& e) const {
+        if (s.priors) {
+            e.backup_phase(s.priors, s.values);
+            E::Wave::sync();
+            e.endmove_phase();
+            E::Wave::sync();
+        }
+        e.template select<true, true>(s.feat, s.valid, on, r_tree, r_root);
+        e.cnt[AZC_ROUNDS]++;
+        e.flush_counters();
+        E::Wave::sync();
+        OpStatus st = {s.status, s.q};
+        st(e);
+        if (E::Wave::first()) s.fault[e.g] = *e.m.err;
+        const int P = e.c.P;
+        E::Wave::lanes([&](int lane) {
+            if (lane < P) s.valid_out[(size_t)e.g * P + lane] = s.valid[(size_t)e.g * P + lane];
+        });
+        const long long lo = (long long)e.g * s.game_feat_bytes;
+        long long n = s.feat_bytes - lo;
+        n = n < 0 ? 0 : (n > s.game_feat_bytes ? s.game_feat_bytes : n);
+        const unsigned char* src = (const unsigned char*)s.feat + lo;
+        for (long long b0 = 0; b0 < n; b0 += AZ_WAVE)
+            E::Wave::lanes([&](int lane) {
+                if (b0 + lane < n) s.feat_out[lo + b0 + lane] = src[b0 + lane];
             });
     }
 };
@@ -900,6 +960,10 @@ struct AzHandle {
     int32_t* harvest_extra = nullptr;  // host destination of the extras, optional
     unsigned char* pin = nullptr;      // page-locked staging of azsp_dropin_step (one packed upload + one packed read-back per call)
     size_t pin_bytes = 0;
+    // first-play urgency reduction (azsp_set_fpu): the values the select launches carry; fpu_seen = enabled at least once, so the
+    // instantiations with the rule compiled in are the ones launched (az_select)
+    int fpu_on = 0, fpu_seen = 0;
+    double fpu_tree = 0.0, fpu_root = 0.0;
 };
 
 namespace azb {  // implemented by the backend translation unit
@@ -1293,7 +1357,18 @@ static int az_select_launched(AzHandle* h, int rc, int g0, int g1) {
 // under it may still be in flight after it was turned off), else the plain one.  An engine that has enabled the mode once pays for
 // the larger kernel (9x9: three waves per SIMD instead of four) for the rest of its life, also with m = 0 again: whether a slot still
 // has a Gumbel root is known on the device only, and an actor is built with the mode on or off, not switched.
+// The same holds for the first-play urgency reduction: once azsp_set_fpu has enabled it the engine launches an instantiation that holds
+// the rule (with the Gumbel root too if that has been enabled), with the values of the last call -- the selections from now on, a
+// search in progress included.
 static int az_select(AzHandle* h, void* feat, uint8_t* valid, void* stream, int g0, int g1) {
+    if (h->fpu_seen && h->mem.gum_n0) {
+        OpSelectGumbelFpu op = {feat, valid, h->fpu_on, h->fpu_tree, h->fpu_root};
+        return az_select_launched(h, az_run(h, op, stream, g0, g1), g0, g1);
+    }
+    if (h->fpu_seen) {
+        OpSelectFpu op = {feat, valid, h->fpu_on, h->fpu_tree, h->fpu_root};
+        return az_select_launched(h, az_run(h, op, stream, g0, g1), g0, g1);
+    }
     if (h->mem.gum_n0) {
         OpSelectGumbel op = {feat, valid};
         return az_select_launched(h, az_run(h, op, stream, g0, g1), g0, g1);
@@ -1384,7 +1459,13 @@ int azsp_dropin_step(void* e, const float* priors_host, const float* values_host
     // (priors_dev / values_dev stay the caller's tensors for the separate entries; this entry reads the staging directly)
     OpDropinStep op = {priors_host ? (const float*)pin : nullptr, priors_host ? (const float*)(pin + o_val) : nullptr, feat_dev, valid_dev,
                        (int*)(pin + o_st), (double*)(pin + o_q), (int*)(pin + o_err), pin + o_valid, pin + o_feat, (long long)feat_bytes, (long long)game_feat};
-    int rc = az_select_launched(h, az_run(h, op, stream), 0, h->cfg.G);
+    int rc;
+    if (h->fpu_seen) {
+        OpDropinStepFpu fop = {op, h->fpu_on, h->fpu_tree, h->fpu_root};
+        rc = az_select_launched(h, az_run(h, fop, stream), 0, h->cfg.G);
+    } else {
+        rc = az_select_launched(h, az_run(h, op, stream), 0, h->cfg.G);
+    }
     if (rc) return rc;
     if (azb::sync(stream)) {
         h->err = std::string("synchronisation failed: ") + azb::backend_error();
@@ -1607,6 +1688,17 @@ int azsp_set_gumbel(void* e, int32_t m, double c_visit, double c_scale) {
     h->cfg.gumbel_m = m;  // AzCfg travels by value with every launch: the searches whose root row is formed after this call
     h->cfg.gumbel_cv = c_visit;
     h->cfg.gumbel_cs = c_scale;
+    return AZSP_OK;
+}
+
+int azsp_set_fpu(void* e, int32_t on, double r_tree, double r_root) {
+    AzHandle* h = (AzHandle*)e;
+    if (!h || !(r_tree >= 0.0) || !(r_tree <= 1.7976931348623157e308) || !(r_root >= 0.0) || !(r_root <= 1.7976931348623157e308))
+        return AZSP_EINVAL;  // negative, NaN, infinite
+    h->fpu_on = on ? 1 : 0;  // travels by value with every select launch (OpSelectFpu): the selections after this call
+    h->fpu_tree = r_tree;
+    h->fpu_root = r_root;
+    if (on) h->fpu_seen = 1;
     return AZSP_OK;
 }
 

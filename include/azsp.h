@@ -43,6 +43,8 @@
  *   azsp_set_gumbel                   no counterpart in the reference: opt-in.  Gumbel root search (Danihelka et al. 2022): sequential
  *                                     halving at the root and the completed-Q policy target; azsp_read_gumbel_moves hands a drop-in
  *                                     caller the move
+ *   azsp_set_fpu                      no counterpart in the reference: opt-in.  First-play urgency reduction (Leela Zero, KataGo): what an
+ *                                     unvisited child is worth in the PUCT selection
  *   azsp_replay_gather                UniformReplay.sample + batch tensors + random transformation (core/replay.py:72-83,
  *                                      core/pipeline.py:636-643)
  *   azsp_dihedral                     apply_horizontal_flip / apply_vertical_flip / apply_rotation
@@ -465,6 +467,34 @@ int azsp_set_gumbel(void* engine, int32_t m, double c_visit, double c_scale);
 /* move_dev int32[G]: a* of each slot's most recent finished Gumbel root search, -1 before the first and after a fast move -- the move
  * a drop-in caller commits.  AZSP_EINVAL before the mode was enabled for the first time.  Does not synchronise. */
 int azsp_read_gumbel_moves(void* engine, int32_t* move_dev, void* stream);
+
+/* First-play urgency reduction (Leela Zero; KataGo's fpuReductionMax = 0.2, rootFpuReductionMax = 0.1; no counterpart in the reference:
+ * opt-in, off by default).  The reference scores an unvisited child with Q = 0, a draw (mcts_v2.py:99-109: -q + u with q = W / max(N, 1)).
+ * With the rule on, the selection at a node i whose mover chooses among the legal actions a is, expression for expression:
+ *   Q_self(i)  = W(i) / N(i), the node's own statistics as they are stored when the selection runs (its parent's row; the root's own
+ *                slots for the root; virtual losses of descents in flight included), 0 if N(i) = 0 -- Tree.Q(i) of the reference's
+ *                arithmetic: a float64 quotient of two Python floats on a freshly created root, a float32 quotient of two np.float32
+ *                everywhere else (a re-used root, every node below the root);
+ *   mass(i)    = sum of (double)P(i, a) over the actions a < A with N(i, a) > 0, P being the prior the u term of that node uses (the
+ *                float64 row at a root with Dirichlet noise, else the float32 prior), accumulated in float64 in this order: lane l of 64
+ *                adds its own elements a = l, l + 64, l + 128, ... in ascending order to 0.0, then the 64 partial sums are combined by the
+ *                butterfly v[l] = v[l] + v[l ^ o] for o = 32, 16, 8, 4, 2, 1;
+ *   fpu(i)     = (double)Q_self(i) - r * sqrt(mass(i)) in float64, r = r_root at the root of the search, r = r_tree below it;
+ *   a child with N(i, a) > 0 is scored as it is without the rule;
+ *   a child with N(i, a) = 0 takes fpu(i) - W(i, a) in place of -q: at a root with Dirichlet noise (the float64 scores)
+ *                (fpu - (double)W) + u in float64; everywhere else ((float)fpu - W) + u in float32, fpu rounded to float32 once.
+ *                W(i, a) of an unvisited child is the number of descents in flight through it (virtual loss touches W only), so a leaf that
+ *                is being evaluated keeps repelling the next descent of its batch.
+ * The u term, the legal mask, the first-maximum tie-break and lazy child creation are untouched.  (0, 0) is a valid setting -- an
+ * unvisited child is then worth its parent's value -- and is not off: off is on = 0, with which every expression is the reference's.
+ * Forced playouts: the forced child is still tested in front of the arg-max, and the pruning of the policy target scores visited
+ * children only.  Gumbel root search: the root's choice and the completed-Q target are unchanged, the rule holds below the root with
+ * r_tree.  Playout cap: fast moves follow the rule too.  Nothing else is touched: pi, child_N, Q, samples and targets are produced by
+ * the same code from another search.
+ * r_tree, r_root: finite and >= 0, else AZSP_EINVAL (also with on = 0).  Holds for the selections launched after the call, those of a
+ * search in progress included.  An engine that has had the rule on launches the select kernel that holds it for the rest of its life
+ * (DESIGN 7.12).  The effect on playing strength is a training experiment; it has not been measured. */
+int azsp_set_fpu(void* engine, int32_t on, double r_tree, double r_root);
 
 /* Auxiliary training targets per sample (KataGo, Wu 2019, 4.1; no counterpart in the reference actor: opt-in, off by default).  With the
  * feature on, actor mode stages next to every sample what the engine computes anyway and otherwise drops:

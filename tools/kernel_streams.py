@@ -55,7 +55,7 @@ def main():
         if pat not in name or name not in ra and name not in rb:  # (kernels only: the code object's other symbols have no resource note)
             continue
         if name not in sa or name not in sb:
-            print(f"only in {'a' if name in sa else 'b'}: {name}")
+            print(f"only in {'a' if name in sa else 'b'}: {name}\n    resources (vgpr+agpr, agpr, sgpr, lds, scratch): {(ra if name in sa else rb).get(name)}")
             diff += 1
             continue
         ia, ib = sa[name], sb[name]

@@ -1,5 +1,5 @@
-"""What an opt-in rule of the actor (SearchOptions.of: playout_cap, leaf_symmetry, forced_playouts, gumbel; aux_targets; policy_surprise;
-DESIGN 7.6 - 7.11) costs it.
+"""What an opt-in rule of the actor (SearchOptions.of: playout_cap, leaf_symmetry, forced_playouts, gumbel, fpu_reduction; aux_targets;
+policy_surprise) costs it.
 
 Runs the headline shape of bench.py (9x9 Go, 4096 games, 200 simulations, 8 leaves per round, 10 x 128 network, fp32-class
 evaluator) twice on the same build, with the same staggered openings and the same number of untimed and timed rounds: once with the
@@ -24,6 +24,12 @@ gumbel (--value M, default 16): select chooses the considered action in front of
   `--child-first` swaps the order inside a pair).  Printed: moves/s of every run in the order they ran, the parent's spread (max - min
   over its runs), and child - parent pair by pair.  The off path may be slower than the parent by no more than that spread.
 
+fpu_reduction (--value R or R_TREE,R_ROOT, default 0.2,0.1, KataGo's): select takes one more wave reduction per tree level, in the kernel
+  that holds the rule.  The tree changes shape (deeper, narrower), so each run also reports, per simulation, the tree levels walked
+  (node_visits), the hint prefetches and the hint hits: a change of the select time is the reduction's or the descents'.  A third run
+  builds the actor with the rule on and turns it off before the first round: the plain search in the kernel that holds the rule, which
+  an engine keeps launching once it has enabled it (`off_after_on_over_off`).  `--parent DIR` as under gumbel.
+
 aux_targets (no value): the end of a move stores the root value, the end of a game the owner boards, every harvest (`--harvest-every`) writes
   and clones the three extra outputs.  The searches of the two runs are the same here: nothing but the extra outputs differs.
 
@@ -32,7 +38,7 @@ policy_surprise (--value FRAC or FRAC,1 to include fast moves; default 0.5): the
   `--replay-adds ROWS` (default 0 = skip) then times DeviceReplay.add_samples against add_samples(weights=) on ROWS random 9x9 rows
   with weights around 1: a warm-up, then `--windows` windows of 10 calls each, microseconds per call with the spread between windows.
 
-    python tools/search_option_rate.py --option {playout_cap,leaf_symmetry,forced_playouts,gumbel,aux_targets,policy_surprise} [--value ...] [--steps 300] [--preroll 200]
+    python tools/search_option_rate.py --option {playout_cap,leaf_symmetry,forced_playouts,gumbel,fpu_reduction,aux_targets,policy_surprise} [--value ...] [--steps 300] [--preroll 200]
 """
 import argparse
 import json
@@ -127,6 +133,18 @@ class Gumbel(Extra):
         return int(text or 16)
 
 
+class FpuReduction(Extra):
+    @staticmethod
+    def parse(text):
+        r = tuple(float(v) for v in (text or "0.2,0.1").split(","))
+        return r if len(r) == 2 else r[0]
+
+    def row(self, cnt, dt):
+        sims = max(1, cnt["sims"])
+        return dict(node_visits_per_sim=round(cnt["node_visits"] / sims, 3), hint_prefetches_per_sim=round(cnt["hint_prefetches"] / sims, 3),
+                    hint_hits_per_sim=round(cnt["hint_hits"] / sims, 3))
+
+
 class AuxTargets(Extra):
     samples = 0
 
@@ -187,8 +205,8 @@ def replay_add_rate(args):
     print(json.dumps(dict(replay_adds=dict(rows=rows, **out))), flush=True)
 
 
-OPTIONS = dict(playout_cap=PlayoutCap, leaf_symmetry=LeafSymmetry, forced_playouts=ForcedPlayouts, gumbel=Gumbel, aux_targets=AuxTargets,
-               policy_surprise=PolicySurprise)
+OPTIONS = dict(playout_cap=PlayoutCap, leaf_symmetry=LeafSymmetry, forced_playouts=ForcedPlayouts, gumbel=Gumbel, fpu_reduction=FpuReduction,
+               aux_targets=AuxTargets, policy_surprise=PolicySurprise)
 
 
 def bench_line(tree, steps, warmup):
@@ -218,14 +236,17 @@ def off_against_parent(args):
                                                   within_parent_spread=bool(np.mean(chi) >= np.mean(par) - spread)))), flush=True)
 
 
-def run(args, on):
+def run(args, on, then_off=False):
     """One run with the option at `on` (None = off): the actor, the staggered openings of bench.py (mixed game phases from the first
-    round), the untimed rounds, the timed rounds, the result row."""
+    round), the untimed rounds, the timed rounds, the result row.  then_off (fpu_reduction): the actor is built with the rule on and the
+    rule is turned off before the first round."""
     n, dev, kind = args.board, torch.device("cuda"), OPTIONS[args.option]
     torch.manual_seed(1)
     net = AlphaZeroNet((17, n, n), n * n + 1, args.blocks, args.filters, args.filters)
     act = SelfPlayActor(net, game="go", board_size=n, num_games=args.games, num_simulations=args.sims, num_parallel=args.parallel,
                         warm_up_steps=16, resign_threshold=-1.0, seed=1, device=dev, net_dtype=torch.float32, **{args.option: on}, **kind.actor_kw)
+    if then_off:
+        act.engine.set_fpu_reduction(None)
     extra = kind(args, act, on)
     rng = np.random.Generator(np.random.PCG64(1234))
     random_openings(act.engine, rng.integers(0, args.stagger + 1, size=args.games), rng)
@@ -247,7 +268,7 @@ def run(args, on):
     torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0
     cnt = act.counters()
-    res = {args.option: list(on) if isinstance(on, tuple) else on, "rounds": args.steps, "seconds": round(dt, 3),
+    res = {args.option: "off after on" if then_off else list(on) if isinstance(on, tuple) else on, "rounds": args.steps, "seconds": round(dt, 3),
            "moves_per_s": round(cnt["moves"] / dt, 1), "sims_per_s": round(cnt["sims"] / dt, 1)}
     if evs:
         phase = lambda a: round(float(np.mean([ev[a].elapsed_time(ev[a + 1]) for ev in evs])) * 1e3, 1)  # noqa: E731  (microseconds)
@@ -263,7 +284,7 @@ def run(args, on):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--option", required=True, choices=sorted(OPTIONS))
-    ap.add_argument("--value", default=None, help="the option's value in the on run: FAST,FULL_PROB | random or an op 0..7 | k | m")
+    ap.add_argument("--value", default=None, help="the option's value in the on run: FAST,FULL_PROB | random or an op 0..7 | k | m | r or r_tree,r_root")
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--preroll", type=int, default=None)
     ap.add_argument("--harvest-every", type=int, default=50)
@@ -275,7 +296,7 @@ def main():
     ap.add_argument("--parallel", type=int, default=8)
     ap.add_argument("--blocks", type=int, default=10)
     ap.add_argument("--filters", type=int, default=128)
-    ap.add_argument("--parent", default=None, help="gumbel: a built checkout of the parent commit: bench.py runs there and here, alternating")
+    ap.add_argument("--parent", default=None, help="gumbel, fpu_reduction: a built checkout of the parent commit: bench.py runs there and here, alternating")
     ap.add_argument("--pairs", type=int, default=3)
     ap.add_argument("--child-first", action="store_true")
     ap.add_argument("--bench-steps", type=int, default=20)
@@ -298,6 +319,10 @@ def main():
     print(json.dumps(on), flush=True)
     label, keys, digits = kind.ratios
     print(json.dumps({label: {key: round(on[key] / off[key], digits) if off[key] else None for key in keys}}))
+    if args.option == "fpu_reduction":
+        after = run(args, kind.parse(args.value), then_off=True)
+        print(json.dumps(after), flush=True)
+        print(json.dumps({"off_after_on_over_off": {key: round(after[key] / off[key], digits) if off[key] else None for key in keys}}))
 
 
 if __name__ == "__main__":
