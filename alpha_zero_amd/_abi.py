@@ -42,10 +42,11 @@ SYMBOLS = [
     "azsp_set_gumbel", "azsp_read_gumbel_moves", "azsp_set_fpu",
     "azsp_set_aux_targets", "azsp_harvest_aux", "azsp_replay_gather_aux",
     "azsp_set_policy_surprise", "azsp_harvest_surprise", "azsp_replay_add_weighted",
+    "azsp_set_visit_reduction", "azsp_harvest_weights",
 ]
 
 COUNTER_NAMES = ["sims", "node_visits", "backup_edges", "leaves", "dup_leaves", "terminal_hits", "moves", "games", "root_evals",
-                 "nodes_created", "game_rounds", "stalls", "hint_prefetches", "hint_hits"]
+                 "nodes_created", "game_rounds", "stalls", "hint_prefetches", "hint_hits", "reduced_moves"]
 
 
 class AzspConfig(C.Structure):
@@ -104,6 +105,7 @@ class Binding:
             "azsp_set_aux_targets": [V, I], "azsp_harvest_aux": [V, V, V, V],
             "azsp_replay_gather_aux": [V, V, V, V, I, I, I, I, I, I, V, V, V, V, V, V, V, V, V, V],
             "azsp_set_policy_surprise": [V, I, C.c_double, I], "azsp_harvest_surprise": [V, V, V],
+            "azsp_set_visit_reduction": [V, I, C.c_double, I, C.c_double], "azsp_harvest_weights": [V, V, V, V],
             "azsp_replay_add_weighted": [V, V, V, C.c_int64, C.c_int64, V, V, V, I, I, I, I, V, V, V, V, V, V, V, V, V, V],
         }
         for k in ("azsp_conv3x3_tiled", "azsp_stem_tiled", "azsp_head_tiled", "azsp_fc_heads"):  # the f16 variants take the same arguments

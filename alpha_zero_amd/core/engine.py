@@ -60,6 +60,7 @@ class EngineConfig:
     fpu_reduction: object = None     # None | r | (r_tree, r_root)
     aux_targets: bool = False        # auxiliary training targets per sample (Engine.set_aux_targets; harvest(with_aux=True))
     policy_surprise: object = None   # policy surprise weighting (Engine.set_policy_surprise; harvest(with_surprise=True)): None | frac | (frac, include_fast)
+    visit_reduction: object = None   # decided-game visit reduction (Engine.set_visit_reduction; harvest(with_base=True)): None | (threshold, lookback, min_simulations, min_weight)
 
 
 def leaf_symmetry_mode(mode):
@@ -128,6 +129,23 @@ def policy_surprise_params(value):
     if isinstance(value, (tuple, list)) and len(value) == 2 and is_frac(value[0]) and isinstance(value[1], (bool, np.bool_)):
         return 1, float(value[0]), int(bool(value[1]))
     raise ValueError(f"policy_surprise must be None (off), a number frac in [0, 1] or (frac, include_fast: bool), got {value!r}")
+
+
+def visit_reduction_params(value, num_simulations=None):
+    """The azsp_set_visit_reduction arguments (lookback, threshold, min_simulations, min_weight) of a `visit_reduction` value: None = off,
+    or (threshold in [0, 1), lookback in 1..8, min_simulations in 1..num_simulations, min_weight in [0, 1]).  Anything else raises
+    ValueError naming these."""
+    num = lambda v: not isinstance(v, (bool, str)) and isinstance(v, (int, float, np.integer, np.floating))  # noqa: E731
+    whole = lambda v: not isinstance(v, bool) and isinstance(v, (int, np.integer))  # noqa: E731
+    if value is None:
+        return 0, 0.0, 1, 1.0
+    if isinstance(value, (tuple, list)) and len(value) == 4:
+        t, look, sims, w = value
+        if (num(t) and 0.0 <= float(t) < 1.0 and whole(look) and 1 <= int(look) <= 8 and whole(sims) and int(sims) >= 1
+                and (num_simulations is None or int(sims) <= num_simulations) and num(w) and 0.0 <= float(w) <= 1.0):
+            return int(look), float(t), int(sims), float(w)
+    raise ValueError("visit_reduction must be None (off) or (threshold in [0, 1), lookback in 1..8, min_simulations in 1..num_simulations, "
+                     f"min_weight in [0, 1]), got {value!r}")
 
 
 EXCLUSIVE = "gumbel and forced_playouts cannot be on together: both decide what the root selects"
@@ -271,6 +289,10 @@ class Engine:
         self._harvest_surprise_bufs = None
         if cfg.policy_surprise is not None:
             self.set_policy_surprise(cfg.policy_surprise)  # before the first move is recorded
+        self.visit_reduction = False  # has been on at least once, so the staging row exists (harvest(with_base=True))
+        self._harvest_base_bufs = None
+        if cfg.visit_reduction is not None:
+            self.set_visit_reduction(cfg.visit_reduction)  # before the first move starts
 
     # -- plumbing ---------------------------------------------------------------------------------
     def _ck(self, rc, what):
@@ -544,6 +566,18 @@ class Engine:
         self._ck(self.b.dll.azsp_set_policy_surprise(self.h, on, frac, fast), "azsp_set_policy_surprise")
         self.policy_surprise = self.policy_surprise or bool(on)
 
+    def set_visit_reduction(self, value):
+        """Decided-game visit reduction (azsp_set_visit_reduction; KataGo's reduceVisits; the reference actor has none).  value: None = off
+        or (threshold, lookback, min_simulations, min_weight), visit_reduction_params.  Once one and the same side has led by more than
+        `threshold` in the root values of the last `lookback` searches of a game, a full move searches fewer simulations -- down to
+        min_simulations as the lead approaches 1 -- and its sample carries a base weight down to min_weight, which
+        `harvest(with_base=True)` hands out with the weight of every row.  The batched actor only (ValueError for a malformed value, an
+        AzspError on a stop_after_move engine).  Holds for the moves that start from now on; turning it on starts every game's history
+        over.  include/azsp.h states the rule."""
+        look, t, sims, w = visit_reduction_params(value, self.cfg.num_simulations)
+        self._ck(self.b.dll.azsp_set_visit_reduction(self.h, look, t, sims, w), "azsp_set_visit_reduction")
+        self.visit_reduction = self.visit_reduction or look > 0
+
     def gumbel_moves(self):
         """int32[G] on the engine's device: a* of every slot's last finished Gumbel root search, -1 before the first and after a fast move
         (azsp_read_gumbel_moves).  Only once the mode has been enabled.  Nothing is synchronised."""
@@ -560,7 +594,8 @@ class Engine:
         return out
 
     # -- samples ----------------------------------------------------------------------------------------
-    def harvest(self, sample_capacity=None, max_games=None, with_moves=False, with_class=False, with_aux=False, with_surprise=False):
+    def harvest(self, sample_capacity=None, max_games=None, with_moves=False, with_class=False, with_aux=False, with_surprise=False,
+                with_base=False):
         """Returns (states int8[n,2K+1,N,N], pi float32[n,A], z float32[n], games int32[k,GR_COUNT]) -- device tensors + host meta;
         with_moves=True appends moves int16[n] (the move played from every sample's position, -1 = resigned); with_class=True then
         appends full uint8[n] (1 = the sample's move was a full search, 0 = a fast move of the playout cap; all 1 with the cap off).
@@ -570,6 +605,9 @@ class Engine:
         with_surprise=True (only once policy surprise weighting has been enabled) then appends surprise float32[n] (the KL divergence of
         the sample's policy target from its root's raw prior) and weight float32[n] (how often the row is to be written into the training
         data; DeviceReplay.add_harvest(weights=)): include/azsp.h, azsp_set_policy_surprise.
+        with_base=True (only once the visit reduction has been enabled) then appends base float32[n] (the base weight of the sample's
+        move, 1.0 unless its search was reduced) and weight float32[n] (as above, with the base in it -- the same tensor if both are
+        asked for; base * full with policy surprise off): include/azsp.h, azsp_set_visit_reduction.
         The per-game extras of the same call (azsp_harvest_extra) are left in `self.last_extra` int32[k,GX_COUNT].
         ALIASING: the device tensors are views of buffers this engine re-uses -- the NEXT harvest() overwrites them in place.
         Consume (or .clone()) them before harvesting again; SelfPlayActor.harvest_tensors(clone=True) does the latter."""
@@ -591,11 +629,20 @@ class Engine:
                                           torch.empty((st.shape[0],), dtype=torch.float32, device=self.device))
             self._ck(self.b.dll.azsp_harvest_aux(self.h, *([t.data_ptr() for t in self._harvest_aux_bufs] if with_aux else [None] * 3)),
                      "azsp_harvest_aux")
+        if with_base and (self._harvest_base_bufs is None or self._harvest_base_bufs[0].shape[0] < st.shape[0]):
+            self._harvest_base_bufs = tuple(torch.empty((st.shape[0],), dtype=torch.float32, device=self.device) for _ in range(2))
         if with_surprise or self._harvest_surprise_bufs is not None:  # (as above: no call from an engine that never asked)
             if with_surprise and (self._harvest_surprise_bufs is None or self._harvest_surprise_bufs[0].shape[0] < st.shape[0]):
                 self._harvest_surprise_bufs = tuple(torch.empty((st.shape[0],), dtype=torch.float32, device=self.device) for _ in range(2))
-            self._ck(self.b.dll.azsp_harvest_surprise(self.h, *([t.data_ptr() for t in self._harvest_surprise_bufs] if with_surprise else [None] * 2)),
-                     "azsp_harvest_surprise")
+            if self._harvest_base_bufs is None:  # (an engine that asked for a base registers all three outputs below)
+                self._ck(self.b.dll.azsp_harvest_surprise(self.h, *([t.data_ptr() for t in self._harvest_surprise_bufs] if with_surprise else [None] * 2)),
+                         "azsp_harvest_surprise")
+        weight = None
+        if self._harvest_base_bufs is not None:
+            weight = self._harvest_surprise_bufs[1] if with_surprise else (self._harvest_base_bufs[1] if with_base else None)
+            self._ck(self.b.dll.azsp_harvest_weights(self.h, self._harvest_surprise_bufs[0].data_ptr() if with_surprise else None,
+                                                     weight.data_ptr() if weight is not None else None,
+                                                     self._harvest_base_bufs[0].data_ptr() if with_base else None), "azsp_harvest_weights")
         games = np.zeros((mg, _abi.GR_COUNT), dtype=np.int32)
         extra = np.zeros((mg, _abi.GX_COUNT), dtype=np.int32)
         self._ck(self.b.dll.azsp_harvest_extra(self.h, extra.ctypes.data), "azsp_harvest_extra")
@@ -614,6 +661,8 @@ class Engine:
             out += tuple(t[:n] for t in self._harvest_aux_bufs)
         if with_surprise:
             out += tuple(t[:n] for t in self._harvest_surprise_bufs)
+        if with_base:
+            out += (self._harvest_base_bufs[0][:n], weight[:n])
         return out
 
     def counters(self, reset=False):

@@ -47,7 +47,7 @@ import warnings  # noqa: E402
 
 import torch  # noqa: E402
 
-from .engine import Engine, EngineConfig, SearchOptions, check_num_stack, policy_surprise_params  # noqa: E402
+from .engine import Engine, EngineConfig, SearchOptions, check_num_stack, policy_surprise_params, visit_reduction_params  # noqa: E402
 from .network import AlphaZeroNet, InferenceNet, capture_graph, widen_for_kernels  # noqa: E402
 from .replay import Transition  # noqa: E402
 
@@ -115,7 +115,7 @@ class SelfPlayActor:
                  use_graph=True, training_steps=0, binding=None, root_noise=True, deterministic=False, tiled_features=None, engine_kw=None,
                  use_split_evaluator=True, auto_widen=None, num_stack=8, split_any_board=False, playout_cap=None,
                  leaf_symmetry=None, forced_playouts=None, prune_policy_target=True, gumbel=None, aux_targets=False,
-                 policy_surprise=None, fpu_reduction=None):
+                 policy_surprise=None, fpu_reduction=None, visit_reduction=None):
         """net_dtype: precision class of the leaf evaluator.  The default is the REFERENCE'S: fp32 (pipeline.py:91-123 evaluates in fp32,
         no autocast anywhere) -- on the hand-written split-precision kernels (hi + lo f16 pairs, three MFMA products, fp32 accumulation:
         include/azsp.h azsp_conv3x3_split) for 9x9 x {128, 64} and 13x13 Gomoku x 64 networks, on library fp32 convolutions (announced
@@ -142,7 +142,12 @@ class SelfPlayActor:
         policy target from its root's raw prior and the weight that follows from it; `harvest_tensors()` leaves them in
         `last_harvest_surprise` / `last_harvest_weight`, and `DeviceReplay.add_harvest(weights=actor.last_harvest_weight)` writes every
         row as often as its weight says -- with include_fast also the fast moves of a playout cap that `keep=last_harvest_full` drops.
-        Off by default; not with a drop-in engine (ValueError)."""
+        Off by default; not with a drop-in engine (ValueError).
+        visit_reduction: None or (threshold, lookback, min_simulations, min_weight) (Engine.set_visit_reduction): once one side has led
+        by more than `threshold` in the last `lookback` searches of a game, its moves are searched with fewer simulations and their
+        samples carry a base weight below 1; `harvest_tensors()` leaves the bases in `last_harvest_base` beside `last_harvest_full` and
+        the weights (base * full, or with policy_surprise the surprise weights with the base in them) in `last_harvest_weight`.  Off
+        by default; not with a drop-in engine (ValueError).  The reference-format `harvest()` has no weight column and ignores it."""
         opt = SearchOptions.of(leaf_symmetry, forced_playouts, prune_policy_target, gumbel, playout_cap, num_simulations,
                                fpu_reduction)  # ValueError before anything is built
         from .. import _lib
@@ -196,10 +201,16 @@ class SelfPlayActor:
         self.policy_surprise = policy_surprise_params(self.cfg.policy_surprise)[0] != 0  # (ValueError for a malformed value, before the engine is built)
         if self.policy_surprise and self.cfg.stop_after_move:
             raise ValueError("policy_surprise needs the batched actor: a drop-in engine (stop_after_move) records no samples")
+        if visit_reduction is not None:
+            self.cfg.visit_reduction = visit_reduction
+        self.visit_reduction = visit_reduction_params(self.cfg.visit_reduction, num_simulations)[0] != 0  # (ValueError for a malformed value, before the engine is built)
+        if self.visit_reduction and self.cfg.stop_after_move:
+            raise ValueError("visit_reduction needs the batched actor: a drop-in engine (stop_after_move) plays no games")
         self.engine = Engine(self.binding, self.cfg, device=self.device, prune_policy_target=self.prune_policy_target, playout_cap=self.playout_cap)
         self.last_harvest_full = torch.zeros(0, dtype=torch.bool, device=self.device)
         self.last_harvest_aux = None  # HarvestAux of the last harvest_tensors() (aux_targets=True only)
-        self.last_harvest_surprise = self.last_harvest_weight = None  # float32[n] of the last harvest_tensors() (policy_surprise only)
+        self.last_harvest_surprise = self.last_harvest_weight = None  # float32[n] of the last harvest_tensors() (policy_surprise only; the weight with visit_reduction too)
+        self.last_harvest_base = None  # float32[n] of the last harvest_tensors() (visit_reduction only)
         self.engine.reset_games()
         self._graph = None
         self.rounds = 0
@@ -302,13 +313,19 @@ class SelfPlayActor:
         e.g. an asynchronous learner or a replay insert on another stream).  With aux_targets the auxiliary targets of the same rows
         are left in `last_harvest_aux` (ownership int8[n,N,N], score float32[n], root_q float32[n]; views or clones like the rest).
         With policy_surprise the surprise and the weight of the same rows are left in `last_harvest_surprise` / `last_harvest_weight`
-        (float32[n] each; views or clones like the rest)."""
-        got = self.engine.harvest(with_class=True, with_aux=self.aux_targets, with_surprise=self.policy_surprise)
+        (float32[n] each; views or clones like the rest).  With visit_reduction the base weights are left in `last_harvest_base` and the
+        weights, which then carry the base, in `last_harvest_weight`."""
+        got = self.engine.harvest(with_class=True, with_aux=self.aux_targets, with_surprise=self.policy_surprise, with_base=self.visit_reduction)
         st, pi, z, games, full = got[:5]
         if self.aux_targets:
             self.last_harvest_aux = HarvestAux(*(t.clone() if clone else t for t in got[5:8]))
         if self.policy_surprise:
-            self.last_harvest_surprise, self.last_harvest_weight = (t.clone() if clone else t for t in got[-2:])
+            at = 8 if self.aux_targets else 5
+            self.last_harvest_surprise, self.last_harvest_weight = (t.clone() if clone else t for t in got[at:at + 2])
+        if self.visit_reduction:
+            self.last_harvest_base = got[-2].clone() if clone else got[-2]
+            if not self.policy_surprise:
+                self.last_harvest_weight = got[-1].clone() if clone else got[-1]
         self._check_evaluator_range()
         self.last_harvest_clamped = self.clamp_window.mask(games[:, _abi.GR_UID]) if len(games) else np.zeros(0, dtype=bool)
         self.clamped_games += int(self.last_harvest_clamped.sum())

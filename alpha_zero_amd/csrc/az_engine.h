@@ -29,6 +29,10 @@
 // GameRec::sim_budget: the low bits hold the slot's simulations per move, AZ_SB_FAST marks a fast move of the playout cap
 #define AZ_SB_SIMS_MASK 0xFFFF
 #define AZ_SB_FAST 0x10000
+// ... and bits 17-31 how many simulations the decided-game visit reduction takes off the move in progress (azsp_set_visit_reduction; 0 on a
+// fast move and with the rule off)
+#define AZ_SB_CUT_SHIFT 17
+#define AZ_VR_RING 8      // root values a slot remembers for the visit reduction
 // stg_meta: bit 0 = black to move, AZ_META_FAST = the sample's move was a fast search of the playout cap
 #define AZ_META_BLACK 1
 #define AZ_META_FAST 2
@@ -45,7 +49,8 @@ enum { AZ_FEAT_I8 = 0, AZ_FEAT_F32 = 1, AZ_FEAT_BF16 = 2, AZ_FEAT_F16 = 3, AZ_FE
 enum { AZB_FREE = 0, AZB_FILLING = 1, AZB_COMPLETE = 2 };
 // statistics counters (u64 each)
 enum { AZC_SIMS = 0, AZC_NODE_VISITS, AZC_BACKUP_EDGES, AZC_LEAVES, AZC_DUP_LEAVES, AZC_TERMINAL_HITS, AZC_MOVES,
-       AZC_GAMES, AZC_ROOT_EVALS, AZC_NODES_CREATED, AZC_ROUNDS, AZC_STALLS, AZC_HINT_PREFETCH, AZC_HINT_HITS, AZC_COUNT = 16 };
+       AZC_GAMES, AZC_ROOT_EVALS, AZC_NODES_CREATED, AZC_ROUNDS, AZC_STALLS, AZC_HINT_PREFETCH, AZC_HINT_HITS, AZC_REDUCED_MOVES,
+       AZC_COUNT = 16 };
 
 AZ_HD u64 az_bits_f64(double v) {
     u64 b;
@@ -91,6 +96,17 @@ struct AzCfg {
     // from the root's raw prior.  AzMem::stg_surprise is null until the first enabling call; once it exists, a move recorded with the
     // feature off stages 0.  (The game weights are the harvest's: OpHarvest.)
     int surprise;
+    // decided-game visit reduction (azsp_set_visit_reduction; vr_L = 0: off; include/azsp.h states the rule).  AzMem::vr / stg_base are null
+    // until the first enabling call.  vr_epoch counts the calls that turned the rule on: a slot whose VrSlot carries another epoch starts over.
+    int vr_L, vr_min, vr_epoch;
+    double vr_t, vr_w;
+};
+
+// per-slot state of the visit reduction: the ring of Black's root values, newest first, how many have been pushed, the prop of the move in progress
+struct VrSlot {
+    double ring[AZ_VR_RING];
+    double prop;
+    int seen, epoch;
 };
 
 struct AzMem {
@@ -112,6 +128,8 @@ struct AzMem {
     u64* stg_own;            // [G][2][2][W]        owner bitboards (black, white) of the game's final position; null until azsp_set_aux_targets
     float* stg_rootq;        // [G][2][stage_cap]   root value of the sample's search, mover's perspective; null until azsp_set_aux_targets
     float* stg_surprise;     // [G][2][stage_cap]   KL(policy target || root prior) of the sample's search; null until azsp_set_policy_surprise
+    float* stg_base;         // [G][2][stage_cap]   base weight of the sample (visit reduction); null until azsp_set_visit_reduction
+    VrSlot* vr;              // [G]                 visit reduction: ring, seen, prop; null until azsp_set_visit_reduction
     // move log (tests / shim): per game per logged move
     double* log_pi;          // [G][log_cap][A]
     float* log_childN;       // [G][log_cap][A]
@@ -293,13 +311,47 @@ template <class Wv, int N, int GAME> struct Engine {
         const int sb = Wv::uni(gr.sim_budget);
         int s = (sb & AZ_SB_FAST) ? c.cap_fast : (sb & AZ_SB_SIMS_MASK);
         if (s == 0) s = c.sims;
-        return s < 1 ? 1 : (s > c.sims ? c.sims : s);
+        s = s < 1 ? 1 : (s > c.sims ? c.sims : s);
+        s -= (int)((u32)sb >> AZ_SB_CUT_SHIFT);  // visit reduction: what begin_move_class() took off this move (0 with the rule off)
+        return s < 1 ? 1 : s;
+    }
+    // Visit reduction: the slot's state, started over if the rule has been turned on since the slot last used it.  (first lane only)
+    AZ_HD VrSlot& vr_slot() {
+        VrSlot& v = m.vr[g];
+        if (v.epoch != c.vr_epoch) {
+            v.epoch = c.vr_epoch;
+            v.seen = 0;
+            v.prop = 0.0;
+        }
+        return v;
+    }
+    // prop of the move that starts now: how far beyond vr_t one and the same side has led in all of the newest vr_L searches, as a share
+    // of 1 - vr_t.  float64 in exactly this operation order (include/azsp.h).
+    AZ_HD double vr_prop(const VrSlot& v) const {
+        const int L = c.vr_L;
+        if (v.seen < L) return 0.0;
+        double lo = v.ring[0], hi = v.ring[0];
+        for (int i = 1; i < L; ++i) {
+            lo = v.ring[i] < lo ? v.ring[i] : lo;
+            hi = v.ring[i] > hi ? v.ring[i] : hi;
+        }
+        const double d = lo > 0.0 ? lo : (hi < 0.0 ? -hi : 0.0);
+        double prop = d > c.vr_t ? (d - c.vr_t) / (1.0 - c.vr_t) : 0.0;
+        if (prop > 1.0) prop = 1.0;
+        return prop;
+    }
+    // A finished search of the batched actor pushes Black's view of its root value.  (first lane only)
+    AZ_HD void vr_push(double rq) {
+        VrSlot& v = vr_slot();
+        for (int i = AZ_VR_RING - 1; i > 0; --i) v.ring[i] = v.ring[i - 1];
+        v.ring[0] = gr.env.to_play == 0 ? rq : -rq;
+        v.seen += 1;
     }
     // Playout cap: the class of the move that starts now, from the game's own counter-based stream (a counter word of its own: the
     // Dirichlet stream uses `| action`, move sampling `| 0xFFF`, the leaf symmetry 0xFFD -- row_symmetry()).  Returns the move's
     // noise_pending.  (first lane only)
     AZ_HD int begin_move_class() {
-        int sb = gr.sim_budget & ~AZ_SB_FAST;
+        int sb = gr.sim_budget & AZ_SB_SIMS_MASK;
         int noise = c.gumbel_m > 0 ? AZ_ROOT_GUMBEL : c.root_noise;  // noise_pending names what is due (apply_noise): 1 = Dirichlet noise, 2 = the Gumbel base row
         if (c.cap_fast > 0 && !c.stop_after_move) {
             u32 r[4];
@@ -308,6 +360,25 @@ template <class Wv, int N, int GAME> struct Engine {
                 sb |= AZ_SB_FAST;
                 noise = 0;
             }
+        }
+        if (m.vr && !c.stop_after_move) {  // visit reduction: no randomness; a fast move keeps cap_fast and stages its prop all the same
+            VrSlot& v = vr_slot();
+            double prop = 0.0;
+            if (c.vr_L > 0) {
+                prop = vr_prop(v);
+                if (!(sb & AZ_SB_FAST)) {
+                    int full = sb & AZ_SB_SIMS_MASK;
+                    if (full == 0) full = c.sims;
+                    full = full < 1 ? 1 : (full > c.sims ? c.sims : full);  // (as game_sims() clamps it)
+                    const int mm = c.vr_min < full ? c.vr_min : full;
+                    const int cut = (int)(prop * (double)(full - mm));
+                    if (cut > 0) {
+                        sb |= (int)((u32)cut << AZ_SB_CUT_SHIFT);
+                        cnt[AZC_REDUCED_MOVES]++;
+                    }
+                }
+            }
+            v.prop = prop;
         }
         gr.sim_budget = sb;
         return noise;
@@ -446,6 +517,7 @@ template <class Wv, int N, int GAME> struct Engine {
             }
             gr.resign_disabled = rd;
             gr.status = AZS_NEED_ROOT;
+            if (m.vr) vr_slot().seen = 0;
         }
         Wv::lanes([&](int lane) {
             u64* flat = &gr.hist[0][0][0];
@@ -1776,6 +1848,7 @@ template <class Wv, int N, int GAME> struct Engine {
             m.stg_meta[idx] = (unsigned char)((me == 0 ? AZ_META_BLACK : 0) | ((gr.sim_budget & AZ_SB_FAST) ? AZ_META_FAST : 0));
             if (m.stg_rootq) m.stg_rootq[idx] = c.aux ? (float)rq : 0.0f;
             if (m.stg_surprise) m.stg_surprise[idx] = surprise;
+            if (m.stg_base) m.stg_base[idx] = c.vr_L > 0 ? (float)(1.0 - vr_slot().prop * (1.0 - c.vr_w)) : 1.0f;
             sh[SH_LEN] = k + 1;
         }
         Wv::sync();
@@ -1955,6 +2028,10 @@ template <class Wv, int N, int GAME> struct Engine {
             }
             Wv::sync();
             return;
+        }
+        if (m.vr && c.vr_L > 0) {  // visit reduction: the history grows in front of the move choice (reroot() starts the next move)
+            if (Wv::first()) vr_push(root_q());
+            Wv::sync();
         }
         int mv;
         if (gumbel) {

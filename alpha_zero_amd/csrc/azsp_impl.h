@@ -547,6 +547,14 @@ AZ_HD float az_surprise_weight(bool full, int include_fast, double frac, double 
     const double share = (full || include_fast) ? frac * nf * (double)surprise / ssum : 0.0;
     return (float)((1.0 - frac) * fk + share);
 }
+// ... and with the base weights of the decided-game visit reduction (azsp_set_visit_reduction): the class becomes fb = base * full, the
+// surprise base * surprise; nf and ssum are the sums of those.  With every base 1.0 these are the bits of az_surprise_weight.
+AZ_HD float az_base_weight(bool full, int include_fast, double frac, double nf, double ssum, float surprise, float base) {
+    const double fb = (double)base * (full ? 1.0 : 0.0);
+    if (!(ssum > 0.0)) return (float)fb;
+    const double share = (full || include_fast) ? frac * nf * ((double)base * (double)surprise) / ssum : 0.0;
+    return (float)((1.0 - frac) * fb + share);
+}
 struct OpHarvest {
     int8_t* states;
     float* pi;
@@ -567,6 +575,8 @@ struct OpHarvest {
     float* weight;    // [cap]      how often the row is to be written into the training data: az_surprise_weight over its game
     double frac;      // share of a game's weight handed out by surprise, in [0, 1]
     int include_fast; // fast moves of the playout cap take part in the surprise share
+    // optional base weight of the visit reduction (azsp_harvest_weights; non-null only once the staging row exists)
+    float* base;      // [cap]      the staged 1 - prop (1 - min_weight) of the sample's move
     template <class E> AZ_HD void operator()(E& e) const {
         const int NP = E::NP, A = E::A, W = E::W;
         const bool go = E::GAME_ID == AZ_GO;
@@ -596,12 +606,21 @@ struct OpHarvest {
             }
             // the game's sums of the weights, once per staging buffer: wave-uniform, sequential, in row order (this order is the contract)
             double nf = 0.0, ssum = 0.0;
+            const float* sbase = e.m.stg_base;          // null: the visit reduction was never on, the weights are az_surprise_weight's
+            const float* ssurprise = e.m.stg_surprise;  // null: policy surprise was never on, every surprise is 0
             if (weight) {
                 const size_t row0 = ((size_t)e.g * 2 + b) * e.c.stage_cap;
                 for (int k = 0; k < len; ++k) {
                     const bool full = !(e.m.stg_meta[row0 + k] & AZ_META_FAST);
-                    if (full) nf += 1.0;
-                    if (full || include_fast) ssum += (double)e.m.stg_surprise[row0 + k];
+                    const double sk = ssurprise ? (double)ssurprise[row0 + k] : 0.0;
+                    if (sbase) {
+                        const double bk = (double)sbase[row0 + k];
+                        if (full) nf += bk;
+                        if (full || include_fast) ssum += bk * sk;
+                    } else {
+                        if (full) nf += 1.0;
+                        if (full || include_fast) ssum += sk;
+                    }
                 }
             }
             for (int k = 0; k < len; ++k) {
@@ -634,7 +653,12 @@ struct OpHarvest {
                     if (score) score[start + k] = go ? (float)(black ? black_score : -black_score) : zk;
                     if (rootq) rootq[start + k] = e.m.stg_rootq[idx];
                     if (surprise) surprise[start + k] = e.m.stg_surprise[idx];
-                    if (weight) weight[start + k] = az_surprise_weight(!(meta & AZ_META_FAST), include_fast, frac, nf, ssum, e.m.stg_surprise[idx]);
+                    if (weight) {
+                        const float sk = ssurprise ? ssurprise[idx] : 0.0f;
+                        weight[start + k] = sbase ? az_base_weight(!(meta & AZ_META_FAST), include_fast, frac, nf, ssum, sk, sbase[idx])
+                                                  : az_surprise_weight(!(meta & AZ_META_FAST), include_fast, frac, nf, ssum, sk);
+                    }
+                    if (base) base[start + k] = sbase[idx];
                     if (moves) moves[start + k] = e.m.stg_move[idx];
                     if (klass) klass[start + k] = (meta & AZ_META_FAST) ? 0 : 1;
                 }
@@ -953,6 +977,7 @@ struct AzHandle {
     float* harvest_rootq = nullptr;
     float* harvest_surprise = nullptr;  // optional per-sample policy surprise outputs of azsp_harvest (azsp_harvest_surprise)
     float* harvest_weight = nullptr;
+    float* harvest_base = nullptr;      // optional per-sample base weight output of azsp_harvest (azsp_harvest_weights)
     double surprise_frac = 0.0;         // azsp_set_policy_surprise: the parameters of the harvest's game weights
     int surprise_fast = 0;
     uint8_t* harvest_class = nullptr;  // optional per-sample search class output of azsp_harvest (azsp_harvest_search_class)
@@ -1534,7 +1559,8 @@ int azsp_harvest(void* e, int8_t* states, float* pi, float* z, int32_t cap, int3
         return AZSP_EDEVICE;
     }
     OpHarvest op = {states, pi, z, cap, h->d_games, max_games, h->d_hofs, h->harvest_moves, h->d_gextra, h->harvest_class,
-                    h->harvest_own, h->harvest_score, h->harvest_rootq, h->harvest_surprise, h->harvest_weight, h->surprise_frac, h->surprise_fast};
+                    h->harvest_own, h->harvest_score, h->harvest_rootq, h->harvest_surprise, h->harvest_weight, h->surprise_frac, h->surprise_fast,
+                    h->harvest_base};
     rc = az_run(h, op, stream);
     if (rc) return rc;
     int cnt[4];
@@ -1612,6 +1638,41 @@ int azsp_harvest_surprise(void* e, float* surprise_dev, float* weight_dev) {
     if ((surprise_dev || weight_dev) && !h->mem.stg_surprise) return AZSP_EINVAL;  // never enabled: nothing staged
     h->harvest_surprise = surprise_dev;
     h->harvest_weight = weight_dev;
+    return AZSP_OK;
+}
+
+int azsp_set_visit_reduction(void* e, int32_t lookback, double threshold, int32_t min_simulations, double min_weight) {
+    AzHandle* h = (AzHandle*)e;
+    if (!h || h->cfg.stop_after_move) return AZSP_EINVAL;  // a drop-in engine plays no games
+    if (lookback < 0 || lookback > AZ_VR_RING || !(threshold >= 0.0 && threshold < 1.0) || min_simulations < 1 ||
+        min_simulations > h->cfg.sims || !(min_weight >= 0.0 && min_weight <= 1.0))
+        return AZSP_EINVAL;  // (a NaN fails its comparison)
+    if (lookback > 0 && h->cfg.sims > 32767) return AZSP_EINVAL;  // the simulations taken off a move live in 15 bits of GameRec::sim_budget
+    if (lookback > 0 && !h->mem.vr) {  // the first enabling call allocates the slot state and the staging row: never a launch path
+        if (azb::set_device(h->pub.device) != 0) return AZSP_EDEVICE;  // the engine's device, as azsp_create selects it
+        float* sb = az_new<float>(h, (size_t)h->cfg.G * 2 * h->cfg.stage_cap);  // (zero-initialised, like every engine allocation: nothing
+        VrSlot* vr = az_new<VrSlot>(h, (size_t)h->cfg.G);                       // staged yet is read; epoch 0 is never the current one)
+        if (!sb || !vr) return AZSP_ENOMEM;
+        h->mem.stg_base = sb;
+        h->mem.vr = vr;
+    }
+    if (lookback > 0 && h->cfg.vr_L == 0) h->cfg.vr_epoch += 1;  // turned on: every slot starts its history over (seen = 0)
+    h->cfg.vr_L = lookback;  // AzCfg travels by value with every launch: the moves that start after this call
+    h->cfg.vr_t = threshold;
+    h->cfg.vr_min = min_simulations;
+    h->cfg.vr_w = min_weight;
+    return AZSP_OK;
+}
+
+int azsp_harvest_weights(void* e, float* surprise_dev, float* weight_dev, float* base_dev) {
+    AzHandle* h = (AzHandle*)e;
+    if (!h) return AZSP_EINVAL;
+    if (surprise_dev && !h->mem.stg_surprise) return AZSP_EINVAL;  // never enabled: nothing staged
+    if (base_dev && !h->mem.stg_base) return AZSP_EINVAL;
+    if (weight_dev && !h->mem.stg_surprise && !h->mem.stg_base) return AZSP_EINVAL;
+    h->harvest_surprise = surprise_dev;
+    h->harvest_weight = weight_dev;
+    h->harvest_base = base_dev;
     return AZSP_OK;
 }
 

@@ -547,9 +547,47 @@ int azsp_set_policy_surprise(void* engine, int32_t on, double frac, int32_t incl
  * valid for every later harvest. */
 int azsp_harvest_surprise(void* engine, float* surprise_dev, float* weight_dev);
 
+/* Decided-game visit reduction (KataGo's reduceVisits / reducedVisitsMin / reducedVisitsWeight; no counterpart in the reference actor:
+ * opt-in, off by default): once one and the same side has clearly led in the last `lookback` searches of a game, the remaining moves are
+ * searched with fewer simulations and their samples carry less weight.  Unlike resignation the game goes on and keeps recording.
+ * azsp_set_visit_reduction(engine, lookback L, threshold t, min_simulations m, min_weight w):
+ *   L = 0 turns the rule off.  AZSP_EINVAL outside 0 <= L <= 8, 0 <= t < 1, 1 <= m <= num_simulations, 0 <= w <= 1, for a NaN, for a
+ *   drop-in engine (stop_after_move), as azsp_set_playout_cap, and for L > 0 on an engine with num_simulations > 32767.  The call holds
+ *   for the moves that start after it.
+ * 1. History.  Every finished search of a batched-actor game pushes b = (mover is Black) ? rq : -rq onto the slot's ring, rq = the double
+ *    the move log holds as AZSP_SQ_ROOT_Q -- full and fast moves alike, a Gumbel root too.  The ring has 8 entries, newest first; the
+ *    push happens in front of the move choice.  `seen` counts the pushes; a new game and a call that turns the rule on (L > 0 after
+ *    L = 0 or after no call) set it to 0.  A call that changes L while the rule is on keeps ring and seen: L is read when it is used.
+ * 2. At the start of a move, after the playout cap's class draw (untouched; this rule has no randomness and no Philox word):
+ *      seen < L: prop = 0;  else lo = min, hi = max of the newest L entries,  d = lo > 0 ? lo : (hi < 0 ? -hi : 0),
+ *      prop = d > t ? (d - t) / (1 - t) : 0;  prop > 1: prop = 1.      float64 in this operation order, no FMA contraction.
+ * 3. Budget.  full = the slot's simulations of a full move (azsp_set_budgets or the engine's, clamped into [1, num_simulations]),
+ *    m' = min(m, full).  A full-class move searches s = full - (int)(prop * (double)(full - m')) simulations (the cast truncates), + P
+ *    in parallel mode as ever; a fast move keeps its fast simulations.  Everything else about the move is what it would be at a slot
+ *    budget of s: root noise as configured, forced playouts and pruning on, the Gumbel schedule built from s.  A kept sub-tree whose
+ *    root already holds the budget's visits owes no simulation.
+ * 4. Base weight.  Every recorded sample stages base = (float)(1 - prop * (1 - w)) with the prop of its own move (fast moves too) and
+ *    the w in force when it is recorded.  The staging row and the slot state are allocated by the first call with L > 0 on the engine's
+ *    device (which it leaves selected), never by a launch; from then on a move recorded with the rule off, or one that was in progress
+ *    when the rule was turned on, stages 1.0f.
+ * 5. Harvest.  With fb_k = (double)base_k * full_k the weights of azsp_set_policy_surprise become
+ *      Nf = sum fb_k;  S = sum over k ascending with part_k of (double)base_k * (double)surprise_k;
+ *      w_k = S > 0 ? (1 - frac) fb_k + (part_k ? frac Nf ((double)base_k * (double)surprise_k) / S : 0) : fb_k;  weight_k = (float)w_k,
+ *    sequential in row order.  With policy surprise off (frac = 0, every surprise 0) weight_k = base_k * full_k; with every base 1.0 the
+ *    weights are the bits they are without this rule.
+ * 6. counters_host[14] counts the moves started with s < full.
+ * With the rule never turned on, every output of the engine is the bytes it was.  Playing strength is a training experiment; it has not
+ * been measured. */
+int azsp_set_visit_reduction(void* engine, int32_t lookback, double threshold, int32_t min_simulations, double min_weight);
+/* azsp_harvest_surprise with a third optional output, base_dev float[sample_capacity]: the staged base weight of every row.  It sets all
+ * three registrations.  AZSP_EINVAL for surprise_dev before policy surprise was first enabled, for base_dev before the visit reduction
+ * was, and for weight_dev before either (with only one of them ever on, the other's values are surprise 0 / base 1).  Buffers must stay
+ * valid for every later harvest. */
+int azsp_harvest_weights(void* engine, float* surprise_dev, float* weight_dev, float* base_dev);
+
 /* counters_host uint64[16]: simulations, best_child calls, backup edges, leaves, duplicate leaves, terminal hits,
- * moves, games, root evaluations, nodes created, game-rounds, buffer stalls, speculative record prefetches of the select phase and
- * how many of them were used. */
+ * moves, games, root evaluations, nodes created, game-rounds, buffer stalls, speculative record prefetches of the select phase,
+ * how many of them were used, and the moves started with a reduced budget (azsp_set_visit_reduction). */
 int azsp_counters(void* engine, uint64_t* counters_host, int32_t reset, void* stream);
 
 /* Dihedral-8 transform of a batch (no engine needed): op 0 identity, 1 h-flip, 2 v-flip, 3/4/5 = rot90/180/270

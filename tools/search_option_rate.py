@@ -1,5 +1,5 @@
 """What an opt-in rule of the actor (SearchOptions.of: playout_cap, leaf_symmetry, forced_playouts, gumbel, fpu_reduction; aux_targets;
-policy_surprise) costs it.
+policy_surprise; visit_reduction) costs it.
 
 Runs the headline shape of bench.py (9x9 Go, 4096 games, 200 simulations, 8 leaves per round, 10 x 128 network, fp32-class
 evaluator) twice on the same build, with the same staggered openings and the same number of untimed and timed rounds: once with the
@@ -38,7 +38,13 @@ policy_surprise (--value FRAC or FRAC,1 to include fast moves; default 0.5): the
   `--replay-adds ROWS` (default 0 = skip) then times DeviceReplay.add_samples against add_samples(weights=) on ROWS random 9x9 rows
   with weights around 1: a warm-up, then `--windows` windows of 10 calls each, microseconds per call with the spread between windows.
 
-    python tools/search_option_rate.py --option {playout_cap,leaf_symmetry,forced_playouts,gumbel,fpu_reduction,aux_targets,policy_surprise} [--value ...] [--steps 300] [--preroll 200]
+visit_reduction (--value THRESHOLD,LOOKBACK,MIN_SIMULATIONS,MIN_WEIGHT, default 0,2,20,0.25): the start of a move reads the slot's ring of
+  root values, the end of a search pushes onto it, every harvest writes the base weights and the weights.  The bench network has
+  random weights and its root values stay near 0, so the default threshold is 0: a move is reduced as soon as one side has led, by
+  however little, in the last two searches, and by the share of the lead.  Each run reports the share of moves started with a reduced
+  budget (reduced_moves / moves), simulations per move and the mean base weight harvested.  `--parent DIR` as under gumbel.
+
+    python tools/search_option_rate.py --option {playout_cap,leaf_symmetry,forced_playouts,gumbel,fpu_reduction,aux_targets,policy_surprise,visit_reduction} [--value ...] [--steps 300] [--preroll 200]
 """
 import argparse
 import json
@@ -178,6 +184,26 @@ class PolicySurprise(Extra):
         return dict(samples_harvested=self.samples, weight_harvested=round(float(self.weight), 1))
 
 
+class VisitReduction(Extra):
+    samples, base = 0, 0.0
+
+    @staticmethod
+    def parse(text):
+        t, look, sims, w = (text or "0,2,20,0.25").split(",")
+        return float(t), int(look), int(sims), float(w)
+
+    def after_harvest(self, z, games):
+        self.samples += int(z.shape[0])
+        if self.on:
+            assert self.act.last_harvest_base.shape == self.act.last_harvest_weight.shape == z.shape
+            self.base = self.base + self.act.last_harvest_base.sum()  # (a device scalar; read after the clock stops)
+
+    def row(self, cnt, dt):
+        moves = max(1, cnt["moves"])
+        return dict(reduced_share=round(cnt.get("reduced_moves", 0) / moves, 4), sims_per_move=round(cnt["sims"] / moves, 1),
+                    samples_harvested=self.samples, mean_base=round(float(self.base) / self.samples, 4) if self.on and self.samples else None)
+
+
 def replay_add_rate(args):
     """add_samples against add_samples(weights=) on the same `--replay-adds` rows: microseconds per call, per window of 10 calls."""
     from alpha_zero_amd.core.replay import DeviceReplay
@@ -206,7 +232,7 @@ def replay_add_rate(args):
 
 
 OPTIONS = dict(playout_cap=PlayoutCap, leaf_symmetry=LeafSymmetry, forced_playouts=ForcedPlayouts, gumbel=Gumbel, fpu_reduction=FpuReduction,
-               aux_targets=AuxTargets, policy_surprise=PolicySurprise)
+               aux_targets=AuxTargets, policy_surprise=PolicySurprise, visit_reduction=VisitReduction)
 
 
 def bench_line(tree, steps, warmup):
@@ -296,7 +322,7 @@ def main():
     ap.add_argument("--parallel", type=int, default=8)
     ap.add_argument("--blocks", type=int, default=10)
     ap.add_argument("--filters", type=int, default=128)
-    ap.add_argument("--parent", default=None, help="gumbel, fpu_reduction: a built checkout of the parent commit: bench.py runs there and here, alternating")
+    ap.add_argument("--parent", default=None, help="gumbel, fpu_reduction, visit_reduction: a built checkout of the parent commit: bench.py runs there and here, alternating")
     ap.add_argument("--pairs", type=int, default=3)
     ap.add_argument("--child-first", action="store_true")
     ap.add_argument("--bench-steps", type=int, default=20)
